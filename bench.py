@@ -15,7 +15,10 @@ One "step" = one pass of the hot path (geometry -> accumulate -> misfit) over a 
 its own contiguous shard of the trial list (weak scaling) and the per-source global misfits are
 all-gathered over RCCL; `python bench.py --gpus N` starts the N ranks itself.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`.  A plain run does only what the headline figure
+needs: set up, warm up, time --steps steps, print the line.  `--full` adds everything else -- `cpu_baseline`, the other arithmetic
+contract, the host-inclusive rate, the secondary workloads, the sweep and HBM blocks and the measured copy bandwidth.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -244,6 +247,27 @@ def _finite(x):
     if isinstance(x, float) and not np.isfinite(x):
         return None
     return x
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs`: every array as <outdir>/<name>.npy in float32 (float64 stays float64).  Over `limit` bytes in all, the
+    arrays keep a fixed sample of their rows (seeded, the same rows for arrays of the same length), so that two builds run with
+    the same arguments write the same elements."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        frac = limit / float(total)
+        for k, v in arrays.items():
+            keep = max(1, int(len(v) * frac))
+            rows = np.sort(np.random.default_rng(12345).choice(len(v), keep, replace=False))
+            arrays[k] = np.ascontiguousarray(v[rows])
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
 
 
 def measured_copy_bandwidth(torch, device):
@@ -653,6 +677,8 @@ def sweep(args, torch, dist, rank, local_rank, ngpus, force_dist):
         elapsed = float(t.item())
     if rank == 0:
         allg = np.asarray(allg)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"global_misfits": allg.ravel(), "misfits": m, "norm_factors": n})
         best = int(np.nanargmin(np.where(np.isfinite(allg), allg, np.inf)))
         # where the list holds the source the references were made from, that is where the minimum has to be
         full = synthetic.workload(args.workload, N, 0)
@@ -688,10 +714,17 @@ def main():
     ap.add_argument("--sweep", type=int, default=0,
                     help="strong scaling: ONE pass over a fixed trial list of this many sources (cfg5: its 10^5-point grid), split over "
                          "the ranks, host discretiser and transfers included; reports wall seconds and evals/s")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary figure (cfg3-100pt) of the default run")
+    ap.add_argument("--no-also", action="store_true", help="skip the secondary figures (other contract, host-inclusive, cfg3's also_* blocks) of a --full run")
     ap.add_argument("--samples", type=int, default=4096)
     ap.add_argument("--piece", type=int, default=0, help="host_inclusive: sources per piece of the one-call evaluation (0: the library's default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: CPU baseline, the other arithmetic contract, host-inclusive "
+                         "rate, the secondary workloads, the sweep and HBM blocks, the measured copy bandwidth (off: a plain run sets up, "
+                         "warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy: global_misfits "
+                         "(gathered, in trial order), misfits and norm_factors (rank 0's trial sources) -- at most 64 MB in all")
     args = ap.parse_args()
 
     if args.gpus is None:
@@ -830,10 +863,12 @@ def main():
         scale = args.batch / prof["batch"] if prof else 0.0
         traffic = prof["hbm_bytes_per_launch"] * scale if prof.get("hbm_bytes_per_launch") else None
         avg_ms = float(ms[1]) / launches_acc
-        try:
-            copy_gbs = measured_copy_bandwidth(torch, torch.device("cuda", local_rank))
-        except Exception:
-            copy_gbs = None
+        copy_gbs = None
+        if args.full:                                # (a run of its own: 1 GiB copies)
+            try:
+                copy_gbs = measured_copy_bandwidth(torch, torch.device("cuda", local_rank))
+            except Exception:
+                copy_gbs = None
         kernel = "accumulate_kernel (KIWI_HIP_ACCUM=direct)" if os.environ.get("KIWI_HIP_ACCUM") == "direct" else \
             ("accumulate_cellw_kernel<NG,FUSE,COMPACT> (cell runs, a tile per wave; + accumulate_grouped_kernel for the pairs it leaves)" if npts > 0.5 * ncent
              else ("accumulate_grouped_kernel<10,256> (runs of sources sharing their tiles)" if wl["sourcetype"] == "moment_tensor"
@@ -906,17 +941,20 @@ def main():
             except Exception as ex:              # noqa: BLE001
                 return {"error": "%s: %s" % (type(ex).__name__, str(ex)[:300])}
 
-        if ngpus == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            gm, gn, _ = p.get_misfits()
+            dump_outputs(args.dump_outputs, {"global_misfits": np.asarray(allg).ravel(), "misfits": gm, "norm_factors": gn})
+        if ngpus == 1 and args.full and not args.no_cpu_baseline:
             gm, gn, gg = p.get_misfits()
             out["cpu_baseline"] = secondary(cpu_baseline, wl, gf, recv, refs, tapers, np.asarray(allg), gm, gn)
         else:
             out["cpu_baseline"] = None
-        if ngpus == 1 and not args.no_also:
+        if ngpus == 1 and args.full and not args.no_also:
             out["other_contract"] = secondary(other_contract, p, args.batch, flops_eval)
             # the whole path (discretiser + transfers included) for the same trial sources, against the resident-input figure
             longer = synthetic.workload(args.workload, 4 * args.batch, 0)["trials"] if wl["crust"] is not None else None
             out["host_inclusive"] = secondary(host_inclusive, p, wl, value, piece=args.piece, longer=longer)
-        if ngpus == 1 and args.workload == "cfg3" and not args.no_also:
+        if ngpus == 1 and args.workload == "cfg3" and args.full and not args.no_also:
             out["also"] = secondary(also_cfg3_100pt, p, local_rank, args.samples)
             # the other BASELINE.json configurations and the unfriendly reading of cfg3, driver-timed: three steps each, own roofline
             # block, a short CPU baseline on the same trial sources

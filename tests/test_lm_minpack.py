@@ -1,7 +1,8 @@
 """Levenberg-Marquardt pin: the product's fp32 lmdif with batched forward differences (kiwi_amd/csrc/kiwi_host_lm.hpp,
 C-ABI kiwi_hip_lmdif) against the reference's own sminpack -- committed outputs (tests/golden/lm_vectors.npz, made by
-tests/golden/make_golden_lm.py) and, where oracle/_ref is present, the live library.  Bit for bit: x, residuals, info
-and the number of function evaluations.  No device involved."""
+tests/golden/make_golden_lm.py) and the reference's answers from more starting points: the live library where oracle/_ref is
+present, else tests/golden/ref_calls_lm.npz (tests/ref_calls.py).  Bit for bit: x, residuals, info and the number of function
+evaluations.  No device involved."""
 import os
 import warnings
 
@@ -11,6 +12,8 @@ import pytest
 import lm_problems as P
 from kiwi_amd import lib as klib
 from kiwi_amd import lm
+from oracle import ko
+from ref_calls import RefCalls
 
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "lm_vectors.npz"))
 CASES = [(s, p[0]) for s in P.SETTINGS for p in P.PROBLEMS]
@@ -33,10 +36,8 @@ def test_lmdif_matches_the_reference_minpack_golden(sname, pname):
 
 
 def test_lmdif_matches_the_live_reference_build():
-    from oracle import ko
     R = ko.ref()
-    if R is None or not hasattr(R, "ref_lmdif"):
-        pytest.skip("oracle/_ref not built")
+    REF = RefCalls("lm", R is not None and hasattr(R, "ref_lmdif"))
     warnings.simplefilter("ignore")
     rng = np.random.default_rng(5)
     for sname, st in P.SETTINGS.items():
@@ -44,9 +45,10 @@ def test_lmdif_matches_the_live_reference_build():
             for trial in range(3):                     # the documented start and two random ones
                 start = np.array(x0, np.float32) if trial == 0 else (np.array(x0, np.float32) + rng.normal(0, 0.3, n)).astype(np.float32)
                 a = P.run_product(klib.load(), klib, name, m, n, start, f, st)
-                b = P.run_reference(R, name, m, n, start, f, st)
+                b = REF("lmdif/%s/%s" % (sname, name), lambda: P.run_reference(R, name, m, n, start, f, st), start)
                 assert a[2:] == b[2:], (sname, name, trial)
                 assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])), (sname, name, trial)
+    REF.save()
 
 
 def test_python_face_and_error_paths():

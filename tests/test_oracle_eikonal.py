@@ -1,6 +1,7 @@
 """Eikonal sources (source_eikonal.f90, source_mt_eikonal.f90, eikonal.f90, heap.f90, geometry.f90):
 oracle restatement against the reference's own modules, bit for bit.  Needs oracle/_ref and the
-CRUST2.0 tables under /root/reference/aux (dev container only); golden vectors cover other boxes."""
+CRUST2.0 tables of the reference tree where they are present; elsewhere the reference's answers to these inputs come from
+tests/golden/ref_calls_eikonal.npz (tests/ref_calls.py)."""
 import ctypes as C
 import os
 
@@ -8,33 +9,47 @@ import numpy as np
 import pytest
 
 from oracle import ko
+from ref_calls import RefCalls
 
 R = ko.LazyRef()
 AUX = "/root/reference/aux/crust2x2"
-pytestmark = pytest.mark.skipif(not ko.ref_available() or not os.path.isdir(AUX), reason="needs oracle/_ref and the reference's aux data")
+REF = RefCalls("eikonal", ko.ref_available() and os.path.isdir(AUX))
 fp = ko._fp
 
 
+@pytest.fixture(scope="module", autouse=True)
+def _save_recording():
+    yield
+    REF.save()
+
+
 def ref_profile(lat, lon):
-    vp, vs, rho, th = (np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(7, np.float32))
-    ok = C.c_int()
-    d = AUX.encode()
-    R.ref_crust_profile(d, C.c_int(len(d)), C.c_double(lat), C.c_double(lon), fp(vp), fp(vs), fp(rho), fp(th), C.byref(ok))
-    assert ok.value == 1
+    def call():
+        vp, vs, rho, th = (np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(8, np.float32), np.zeros(7, np.float32))
+        ok = C.c_int()
+        d = AUX.encode()
+        R.ref_crust_profile(d, C.c_int(len(d)), C.c_double(lat), C.c_double(lon), fp(vp), fp(vs), fp(rho), fp(th), C.byref(ok))
+        return ok.value, vp, vs, rho, th
+    ok, vp, vs, rho, th = REF("crust_profile", call, lat, lon)
+    assert ok == 1
     return ko.crust_profile(vp, vs, rho, th)
 
 
 def ref_eikonal(st, params, edt, lat_rad, lon_rad, limit=0.0):
     params = np.ascontiguousarray(params, np.float32)
     maxc = 200000
-    cent = np.zeros((maxc, 10), np.float32)
-    nc, gs = C.c_int(), (C.c_int * 2)()
-    mo, ri = C.c_float(), C.c_float()
-    cp, cn = np.zeros((2, 3), np.float32), np.zeros((2, 3), np.float32)
-    R.ref_discretize_eikonal(C.c_int(st), C.c_int(len(params)), fp(params), C.c_float(edt), C.c_double(lat_rad),
-                             C.c_double(lon_rad), C.c_float(limit), C.c_int(maxc), C.byref(nc), fp(cent), C.byref(mo),
-                             C.byref(ri), gs, fp(cp), fp(cn))
-    return nc.value, cent[:max(nc.value, 0)].copy(), mo.value, ri.value, (gs[0], gs[1]), cp, cn
+
+    def call():
+        cent = np.zeros((maxc, 10), np.float32)
+        nc, gs = C.c_int(), (C.c_int * 2)()
+        mo, ri = C.c_float(), C.c_float()
+        cp, cn = np.zeros((2, 3), np.float32), np.zeros((2, 3), np.float32)
+        R.ref_discretize_eikonal(C.c_int(st), C.c_int(len(params)), fp(params), C.c_float(edt), C.c_double(lat_rad),
+                                 C.c_double(lon_rad), C.c_float(limit), C.c_int(maxc), C.byref(nc), fp(cent), C.byref(mo),
+                                 C.byref(ri), gs, fp(cp), fp(cn))
+        return nc.value, cent[:max(nc.value, 0)].copy(), mo.value, ri.value, np.array([gs[0], gs[1]], np.int64), cp, cn
+    nc, cent, mo, ri, gs, cp, cn = REF("discretize_eikonal/%d" % st, call, params, edt, lat_rad, lon_rad, limit)
+    return int(nc), cent, float(mo), float(ri), (int(gs[0]), int(gs[1])), cp, cn
 
 
 def test_fast_marching_bitexact():
@@ -55,9 +70,13 @@ def test_fast_marching_bitexact():
         origin = rng.uniform(-5000, 0, 2).astype(np.float32)
         delta = rng.uniform(100, 900, 2).astype(np.float32)
         ip = (origin + rng.uniform(0.3, 0.7, 2) * delta * [nx, ny]).astype(np.float32)
-        t1 = np.zeros((ny, nx), np.float32)
         t2 = np.zeros((ny, nx), np.float32)
-        R.ref_eikonal_fmm(C.c_int(nx), C.c_int(ny), fp(speed), fp(origin), fp(delta), fp(ip), fp(t1))
+
+        def call():
+            t1 = np.zeros((ny, nx), np.float32)
+            R.ref_eikonal_fmm(C.c_int(nx), C.c_int(ny), fp(speed), fp(origin), fp(delta), fp(ip), fp(t1))
+            return (t1,)
+        t1, = REF("eikonal_fmm", call, speed, origin, delta, ip)
         L.ko_eikonal_solver_fmm(fp(speed), C.c_int(nx), C.c_int(ny), fp(origin), fp(delta), fp(ip), fp(t2))
         assert np.array_equal(t1.view(np.uint32), t2.view(np.uint32))
 
