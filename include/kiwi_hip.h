@@ -93,6 +93,20 @@ int kiwi_hip_set_gfdb(kiwi_hip_ctx *ctx, int nx, int nz, int ng, int L,
                       float dt, float dx, float dz, float firstx, float firstz,
                       const float *G, const int *first, const int *nsamp);
 
+/* set_database dbpath nipx nipz (minimizer.f90:91-150 -> gfdb.f90:163-264,1109-1310): the stored database of
+ * kiwi_hip_set_gfdb (same arguments), made nipx times denser in distance and nipz times denser in depth by Gulunay's
+ * f-k interpolation on the device (nx' = nx*nipx, dx' = dx/nipx, likewise in depth; firstx, firstz unchanged; stored
+ * traces stay bit-identical at ix' = ix*nipx, iz' = iz*nipz).  nipx must be a power of two up to 128 and nipz one up
+ * to 32 (other values are refused: the reference dies at their first use).  (1,1) is kiwi_hip_set_gfdb. */
+int kiwi_hip_set_gfdb_interpolated(kiwi_hip_ctx *ctx, int nipx, int nipz, int nx, int nz, int ng, int L,
+                                   float dt, float dx, float dz, float firstx, float firstz,
+                                   const float *G, const int *first, const int *nsamp);
+/* shape of the installed database: maxlen = longest trace */
+int kiwi_hip_get_gfdb_shape(kiwi_hip_ctx *ctx, int *nx, int *nz, int *ng, int *maxlen, float *dx, float *dz);
+/* one installed trace, 0-based indices like G's: first sample index, count (0: not stored) and, when out is not NULL,
+ * its samples (maxn >= n) */
+int kiwi_hip_get_gfdb_trace(kiwi_hip_ctx *ctx, int ix, int iz, int ig, int *first, int *n, float *out, int maxn);
+
 /* set_local_interpolation + set_spacial_undersampling (minimizer_engine.f90:141-163; minimizer.f90:155-207) */
 int kiwi_hip_set_interp(kiwi_hip_ctx *ctx, int bilinear, int xundersample, int zundersample);
 

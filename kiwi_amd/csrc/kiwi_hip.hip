@@ -31,6 +31,8 @@
 #include <mutex>
 #include <thread>
 #include <limits>
+#include <climits>
+#include <cmath>
 
 using namespace kiwi;
 
@@ -97,6 +99,7 @@ struct kiwi_hip_ctx {
     DevBuf<float> G;
     DevBuf<int2> span;
     DevBuf<unsigned char> endz;       // per GF row: the stored trace ends in an exact zero (its repeated end value is 0)
+    int db_lmax = 0;                  // longest stored trace (kiwi_hip_get_gfdb_shape)
 
     // setup
     int bilinear = 0, xus = 1, zus = 1;
@@ -1385,6 +1388,8 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 
 } // namespace
 
+#include "kiwi_gfk.hpp"
+
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
 typedef unsigned int read_u4 __attribute__((ext_vector_type(4)));
@@ -1580,6 +1585,7 @@ int kiwi_hip_set_gfdb(kiwi_hip_ctx *c, int nx, int nz, int ng, int L, float dt, 
     HIPCHECK(hipMemcpy(c->span.p, sp.data(), nrows * sizeof(int2), hipMemcpyHostToDevice));
     HIPCHECK(hipMemcpy(c->endz.p, ez.data(), nrows, hipMemcpyHostToDevice));
     c->gm = GfMeta{ nx, nz, ng, pitch, dt, dx, dz, firstx, firstz };
+    c->db_lmax = lmax;
     c->db_gaps = gaps;
     {
         bool simple = !gaps;
@@ -1591,6 +1597,69 @@ int kiwi_hip_set_gfdb(kiwi_hip_ctx *c, int nx, int nz, int ng, int L, float dt, 
     c->have_db = true;
     c->prepared = false;            // dirtyfy_database, minimizer_engine.f90:1483
     return forward(c, [&](kiwi_hip_ctx *m) { return kiwi_hip_set_gfdb(m, nx, nz, ng, L, dt, dx, dz, firstx, firstz, G, first, nsamp); });
+    GUARD_END(c)
+}
+
+// set_database dbpath nipx nipz (minimizer_engine.f90:114-139, gfdb.f90:223-246,1109-1310): the stored database is installed
+// on this device, densified from its padded rows (kiwi_gfk.hpp), and the dense database installed through
+// kiwi_hip_set_gfdb -- which forwards it to the other devices of a multi-device context
+int kiwi_hip_set_gfdb_interpolated(kiwi_hip_ctx *c, int nipx, int nipz, int nx, int nz, int ng, int L, float dt, float dx,
+                                   float dz, float firstx, float firstz, const float *G, const int *first, const int *nsamp)
+{
+    if (!c) return fail(nullptr, "null context");
+    {
+        const std::string msg = gfk::check_factors(nipx, nipz);
+        if (!msg.empty()) return fail(c, msg);
+    }
+    if (nipx == 1 && nipz == 1) return kiwi_hip_set_gfdb(c, nx, nz, ng, L, dt, dx, dz, firstx, firstz, G, first, nsamp);
+    GUARD_BEGIN_DEV(c)
+    if (nx < 1 || nz < 1 || L < 1) throw std::runtime_error("bad database dimensions");
+    if ((long long)nx * nipx > INT_MAX / 2 || (long long)nz * nipz > INT_MAX / 2) throw std::runtime_error("bad database dimensions");
+    std::vector<kiwi_hip_ctx *> mates;
+    mates.swap(c->mates);                    // the stored database on this device only
+    const int rc = kiwi_hip_set_gfdb(c, nx, nz, ng, L, dt, dx, dz, firstx, firstz, G, first, nsamp);
+    mates.swap(c->mates);
+    if (rc) return rc;
+    gfk::Dense d;
+    try {
+        d = gfk::densify(c, nipx, nipz, L, G, first, nsamp);
+    } catch (...) {
+        c->have_db = false;                  // no half-made database stays behind
+        throw;
+    }
+    // dx' = dx/nipx, dz' = dz/nipz; firstx, firstz unchanged (gfdb.f90:223-246)
+    return kiwi_hip_set_gfdb(c, d.NX, d.NZ, ng, d.L, dt, dx / (float)nipx, dz / (float)nipz, firstx, firstz, d.G.data(),
+                             d.first.data(), d.nsamp.data());
+    GUARD_END(c)
+}
+
+int kiwi_hip_get_gfdb_shape(kiwi_hip_ctx *c, int *nx, int *nz, int *ng, int *maxlen, float *dx, float *dz)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!nx || !nz || !ng || !maxlen || !dx || !dz) return fail(c, "null argument");
+    if (!c->have_db) return fail(c, "no database set");
+    *nx = c->gm.nx; *nz = c->gm.nz; *ng = c->gm.ng; *maxlen = c->db_lmax; *dx = c->gm.dx; *dz = c->gm.dz;
+    return 0;
+}
+
+int kiwi_hip_get_gfdb_trace(kiwi_hip_ctx *c, int ix, int iz, int ig, int *first, int *n, float *out, int maxn)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!first || !n) return fail(c, "null argument");
+    if (!c->have_db) return fail(c, "no database set");
+    if (ix < 0 || ix >= c->gm.nx || iz < 0 || iz >= c->gm.nz || ig < 0 || ig >= c->gm.ng) return fail(c, "trace index out of range");
+    GUARD_BEGIN_DEV(c)
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    const size_t row = ((size_t)ix * c->gm.nz + iz) * c->gm.ng + ig;
+    int2 sp;
+    HIPCHECK(hipMemcpy(&sp, c->span.p + row, sizeof(int2), hipMemcpyDeviceToHost));
+    *first = sp.x;
+    *n = std::max(0, sp.y - sp.x + 1);
+    if (out && *n > 0) {
+        if (maxn < *n) throw std::runtime_error("output buffer too small for the trace");
+        HIPCHECK(hipMemcpy(out, c->G.p + row * (size_t)c->gm.pitch + kRowPad, (size_t)*n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return 0;
     GUARD_END(c)
 }
 

@@ -156,16 +156,37 @@ class Engine:
             pass
 
     # ------------------------------------------------------------------ setup commands
-    def set_database(self, dt, dx, dz, firstx, firstz, data, first, nsamp):
-        """data[nx,nz,ng,L] float32, first/nsamp[nx,nz,ng] int32 (see kiwi_hip_set_gfdb)."""
+    def set_database(self, dt, dx, dz, firstx, firstz, data, first, nsamp, nipx=1, nipz=1):
+        """data[nx,nz,ng,L] float32, first/nsamp[nx,nz,ng] int32 (see kiwi_hip_set_gfdb).  nipx, nipz other than 1: the
+        database is densified by Gulunay's f-k interpolation on the device (kiwi_hip_set_gfdb_interpolated)."""
         data = np.ascontiguousarray(data, np.float32)
         first = np.ascontiguousarray(first, np.int32)
         nsamp = np.ascontiguousarray(nsamp, np.int32)
         nx, nz, ng, L = data.shape
         assert first.shape == (nx, nz, ng) and nsamp.shape == (nx, nz, ng)
-        self._ck(self.L.kiwi_hip_set_gfdb(self.h, nx, nz, ng, L, dt, dx, dz, firstx, firstz, _fp(data), _ip(first),
-                                          _ip(nsamp)), "set_database")
+        if nipx == 1 and nipz == 1:
+            rc = self.L.kiwi_hip_set_gfdb(self.h, nx, nz, ng, L, dt, dx, dz, firstx, firstz, _fp(data), _ip(first),
+                                          _ip(nsamp))
+        else:
+            rc = self.L.kiwi_hip_set_gfdb_interpolated(self.h, int(nipx), int(nipz), nx, nz, ng, L, dt, dx, dz, firstx,
+                                                       firstz, _fp(data), _ip(first), _ip(nsamp))
+        self._ck(rc, "set_database")
         self.dt = dt
+
+    def database_shape(self):
+        """(nx, nz, ng, maxlen, dx, dz) of the installed database (densified, when it was)."""
+        v = [C.c_int() for _ in range(4)] + [C.c_float() for _ in range(2)]
+        self._ck(self.L.kiwi_hip_get_gfdb_shape(self.h, *[C.byref(x) for x in v]), "database_shape")
+        return tuple(x.value for x in v)
+
+    def get_database_trace(self, ix, iz, ig):
+        """(first, samples) of installed trace (ix, iz, ig), 0-based; samples is empty for a trace that is not stored."""
+        f, n = C.c_int(), C.c_int()
+        self._ck(self.L.kiwi_hip_get_gfdb_trace(self.h, ix, iz, ig, C.byref(f), C.byref(n), None, 0), "get_database_trace")
+        out = np.zeros(max(n.value, 1), np.float32)
+        self._ck(self.L.kiwi_hip_get_gfdb_trace(self.h, ix, iz, ig, C.byref(f), C.byref(n), _fp(out), len(out)),
+                 "get_database_trace")
+        return f.value, out[:n.value]
 
     def set_local_interpolation(self, kind):
         self._interp = (kind in ("bilinear", True, 1))

@@ -68,6 +68,32 @@ module kiwi_hip_binding
             integer(c_int), intent(in) :: first(*), nsamp(*)   ! (ng, nz, nx)
         end function
 
+        integer(c_int) function kiwi_hip_set_gfdb_interpolated( ctx, nipx, nipz, nx, nz, ng, L, dt, dx, dz, firstx, firstz, &
+                G, first, nsamp ) bind(C, name='kiwi_hip_set_gfdb_interpolated')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: nipx, nipz, nx, nz, ng, L
+            real(c_float), value :: dt, dx, dz, firstx, firstz
+            real(c_float), intent(in) :: G(*)            ! the stored database, as kiwi_hip_set_gfdb takes it
+            integer(c_int), intent(in) :: first(*), nsamp(*)
+        end function
+
+        integer(c_int) function kiwi_hip_get_gfdb_shape( ctx, nx, nz, ng, maxlen, dx, dz ) bind(C, name='kiwi_hip_get_gfdb_shape')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: nx, nz, ng, maxlen
+            real(c_float), intent(out) :: dx, dz
+        end function
+
+        integer(c_int) function kiwi_hip_get_gfdb_trace( ctx, ix, iz, ig, first, n, out, maxn ) &
+                bind(C, name='kiwi_hip_get_gfdb_trace')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: ix, iz, ig, maxn     ! 0-based
+            integer(c_int), intent(out) :: first, n
+            real(c_float), intent(out) :: out(*)
+        end function
+
         integer(c_int) function kiwi_hip_set_interp( ctx, bilinear, xus, zus ) bind(C, name='kiwi_hip_set_interp')
             import :: c_int, c_ptr
             type(c_ptr), value :: ctx

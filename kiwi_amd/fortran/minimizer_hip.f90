@@ -5,7 +5,9 @@
 ! "<cmd>: ok >" + answer line, "<cmd>: nok" or "<cmd>: nok >" + error line, flushed after each.
 !
 ! Commands (SURVEY.md 8b's subset for the hot path, widened to most of minimizer.f90:1729-1811):
-!   set_database <base>                    <base>.kiwiflat (flat dense GFDB) or the reference's HDF5 <base>.index + chunks
+!   set_database <base> [nipx nipz]        <base>.kiwiflat (flat dense GFDB) or the reference's HDF5 <base>.index + chunks;
+!                                          nipx nipz: densified by Gulunay's f-k interpolation on the device (powers of two
+!                                          up to 128 and 32)
 !   set_effective_dt <dt>
 !   set_local_interpolation nearest_neighbor|bilinear
 !   set_spacial_undersampling <nx> <nz>
@@ -290,12 +292,25 @@ program minimizer_hip
         integer(c_int), allocatable :: first(:), nsamp(:)
         real(c_float), allocatable :: G(:)
         integer :: unit, ios
+        integer(c_int) :: nipx, nipz
         ok_ = .false.
         call split_first( a, base, rest )
+      ! set_database dbpath [ nipx nipz ]: exactly three words means two integers (minimizer.f90:128-146)
+        nipx = 1
+        nipz = 1
+        if (count_words( a ) == 3) then
+            read (rest, *, iostat=ios) nipx, nipz
+            if (ios /= 0) then
+                call fail( 'set_database: failed to parse arguments' ); return
+            end if
+        end if
+        if (nipx < 1 .or. nipz < 1) then
+            call fail( 'set_database: nipx and nipz must be positive' ); return
+        end if
         open( newunit=unit, file=trim(base)//'.kiwiflat', access='stream', form='unformatted', status='old', iostat=ios )
 #ifdef HAVE_GFDB_HDF5
         if (ios /= 0) then        ! the reference's own on-disk format: <base>.index + <base>.<i>.chunk (gfdb_io_hdf.f90)
-            call set_database_hdf5( trim(base), ok_ )
+            call set_database_hdf5( trim(base), nipx, nipz, ok_ )
             return
         end if
 #endif
@@ -313,15 +328,17 @@ program minimizer_hip
             call fail( 'truncated gfdb file '//trim(base)//'.kiwiflat' ); return
         end if
         if (.not. need_ctx()) return
-        ok_ = check( kiwi_hip_set_gfdb( ctx, nx, nz, ng, L, dt, dx, dz, firstx, firstz, G, first, nsamp ) )
+        ok_ = check( kiwi_hip_set_gfdb_interpolated( ctx, nipx, nipz, nx, nz, ng, L, dt, dx, dz, firstx, firstz, G, first, &
+                                                     nsamp ) )
         if (ok_) db_dt = dt
         if (ok_) db_format = 'kiwiflat'
         evaluated = .false.
     end subroutine
 
 #ifdef HAVE_GFDB_HDF5
-    subroutine set_database_hdf5( base, ok_ )
+    subroutine set_database_hdf5( base, nipx, nipz, ok_ )
         character(len=*), intent(in) :: base
+        integer(c_int), intent(in) :: nipx, nipz
         logical, intent(out) :: ok_
         type, bind(C) :: t_index
             real(c_float) :: dt, dx, dz, firstx, firstz
@@ -361,7 +378,8 @@ program minimizer_hip
         allocate( G(int(lmax,8)*ix%nx*ix%nz*ix%ng) )
         if (kiwi_gfdb_read_dense( base//c_null_char, lmax, c_loc(G), first, nsamp, lmax, err, 512_c_int ) /= 0) goto 10
         if (.not. need_ctx()) return
-        ok_ = check( kiwi_hip_set_gfdb( ctx, ix%nx, ix%nz, ix%ng, lmax, ix%dt, ix%dx, ix%dz, ix%firstx, ix%firstz, G, first, nsamp ) )
+        ok_ = check( kiwi_hip_set_gfdb_interpolated( ctx, nipx, nipz, ix%nx, ix%nz, ix%ng, lmax, ix%dt, ix%dx, ix%dz, &
+                                                     ix%firstx, ix%firstz, G, first, nsamp ) )
         if (ok_) db_dt = ix%dt
         if (ok_) db_format = 'hdf5'
         evaluated = .false.

@@ -2,6 +2,7 @@
 
     gf = gfdb_hdf5.read("/path/to/db")            # -> dict(dt, dx, dz, firstx, firstz, data, first, nsamp)
     engine.set_database(gf["dt"], gf["dx"], gf["dz"], gf["firstx"], gf["firstz"], gf["data"], gf["first"], gf["nsamp"])
+    gfdb_hdf5.set_database(engine, "/path/to/db", nipx=2, nipz=2)   # the same call, densified on the device
     python -m kiwi_amd.gfdb_hdf5 /path/to/db out_base     # -> out_base.kiwiflat for kiwi_amd/fortran/minimizer_hip
 
 The C side (kiwi_amd/gfdb/kiwi_gfdb_hdf5.c -> kiwi_amd/libkiwi_gfdb.so) needs the HDF5 C library and is built on
@@ -78,6 +79,14 @@ def read(base):
                                nsamp.ctypes.data_as(ip), C.byref(lmax), buf, 1024), buf)
     return dict(dt=ix.dt, dx=ix.dx, dz=ix.dz, firstx=ix.firstx, firstz=ix.firstz, data=data, first=first, nsamp=nsamp,
                 nchunks=ix.nchunks, nxc=ix.nxc)
+
+
+def set_database(engine, base, nipx=1, nipz=1):
+    """set_database base [nipx nipz] (minimizer.f90:91-150) on an Engine from the database at `base`."""
+    gf = read(base)
+    engine.set_database(gf["dt"], gf["dx"], gf["dz"], gf["firstx"], gf["firstz"], gf["data"], gf["first"], gf["nsamp"],
+                        nipx=nipx, nipz=nipz)
+    return gf
 
 
 def pack_trace(first, data):

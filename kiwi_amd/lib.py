@@ -72,6 +72,10 @@ def load():
         "kiwi_hip_last_error": [vp, C.c_char_p, C.c_int],
         "kiwi_hip_set_gfdb": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                               C.c_float, c_float_p, c_int_p, c_int_p],
+        "kiwi_hip_set_gfdb_interpolated": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, c_float_p, c_int_p, c_int_p],
+        "kiwi_hip_get_gfdb_shape": [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_float_p, c_float_p],
+        "kiwi_hip_get_gfdb_trace": [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, C.c_int],
         "kiwi_hip_set_interp": [vp, C.c_int, C.c_int, C.c_int],
         "kiwi_hip_set_effective_dt": [vp, C.c_float],
         "kiwi_hip_set_source_location": [vp, C.c_float, C.c_float, C.c_double],
