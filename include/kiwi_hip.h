@@ -304,6 +304,32 @@ int kiwi_hip_get_arias_intensities(kiwi_hip_ctx *ctx, int isrc, float *out);
  * ms[0] geometry kernel, ms[1] accumulate kernel(s), ms[2] misfit kernels, ms[3] whole eval;
  * launches[0..2] = number of launches of each in that eval.  Synchronises. */
 int kiwi_hip_get_kernel_ms(kiwi_hip_ctx *ctx, float ms[4], int launches[3]);
+/* Outer misfit of every trial source under ndraw receiver weightings, and the best source of each (make_global_misfits,
+ * seismosizer.py:843-922; the bootstrap over the receivers, gridsearch.py:199-289), on HOST arrays: misfit and norm are the
+ * per-slot results [nsrc][nmis] of kiwi_hip_get_misfits / kiwi_hip_misfits_for_params -- of this context, of a gathered
+ * sharded run, or anything laid out like them; the context supplies device, stream and chunk bound, nothing of its setup.
+ *   slot_receiver[nmis]   receiver (0-based, < nrec) of every slot, ascending: the slots of a receiver are consecutive
+ *   outer_norm            1 l1norm, 2 l2norm
+ *   receiver_weights      [nrec] or NULL = ones; anarchy != 0 divides each by the receiver's norm (clipped at zero)
+ *   draw_weights          [ndraw][nrec]: the weight of receiver r in draw d -- a resampling count under bootstrap, all
+ *                         ones for the plain outer misfit
+ *   best_value, best_index  [ndraw]: the lowest global misfit of each draw and its source (0-based; among equal values
+ *                         the LOWEST index).  A source is excluded from a draw when its weighted norm sum is not
+ *                         positive or its misfit is negative or NaN; a draw with every source excluded answers NaN, 0
+ *   global_of_draw        [nsrc] or NULL: the global misfit of every source under draw `which_draw`; excluded sources
+ *                         read NaN
+ * fp64 throughout, every operation rounded on its own in a fixed order (tests/outer_restatement.py restates it): the
+ * answer does not depend on chunking (KIWI_HIP_CHUNK_MB) or on how a list is cut into shards.  Under l2norm the squared
+ * term is multiplied by the draw weight where the host path multiplies by its root before squaring: a few ulp
+ * (INTEGRATION.md).  nrec is bounded by kiwi_hip_outer_max_receivers(); nsrc by INT_MAX. */
+int kiwi_hip_outer_misfits(kiwi_hip_ctx *ctx, int nsrc, int nmis, int nrec, const int *slot_receiver, const float *misfit,
+                           const float *norm, int outer_norm, const double *receiver_weights, int anarchy, int ndraw,
+                           const double *draw_weights, double *best_value, int *best_index, int which_draw,
+                           double *global_of_draw);
+/* the most receivers kiwi_hip_outer_misfits takes (the weight rows of a draw tile live in LDS) */
+int kiwi_hip_outer_max_receivers(void);
+/* HIP-event durations [ms] of the last kiwi_hip_outer_misfits: ms[0] uploads, ms[1] kernels, ms[2] downloads */
+int kiwi_hip_get_outer_ms(kiwi_hip_ctx *ctx, float ms[3]);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each
  * (layout in kiwi_amd/csrc/kiwi_kernels.hpp); for parity tests */
 int kiwi_hip_get_geometry(kiwi_hip_ctx *ctx, int isrc, int irec, int maxcent, int *ncent, void *records);

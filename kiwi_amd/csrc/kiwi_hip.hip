@@ -202,6 +202,7 @@ struct kiwi_hip_ctx {
     int keep_which = 0;               // kiwi_hip_set_keep_synthetics
     int proc_chunk0 = 0, proc_chunkn = 0, proc_which_held = 0;   // what proc_d currently holds
     size_t chunk_bytes_limit = (size_t)16 << 30;      // workspace per launch; the device has 288 GB
+    float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
 
     // spectral / filtered comparator (hipFFT).  The transform length belongs to the (trial source, slot) pair
     // (fft_size_kernel); the reference-side data that depend on it -- amplitude spectrum, filter weights per bin,
@@ -1389,6 +1390,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 } // namespace
 
 #include "kiwi_gfk.hpp"
+#include "kiwi_outer.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2995,6 +2997,31 @@ int kiwi_hip_get_kernel_ms(kiwi_hip_ctx *c, float ms[4], int launches[3])
     return 0;
     GUARD_END(c)
 }
+
+// make_global_misfits under ndraw receiver weightings and the best source of each (kiwi_outer.hpp), on host arrays: the
+// per-slot misfits of one engine, of a gathered sharded run, or of anything laid out like them
+int kiwi_hip_outer_misfits(kiwi_hip_ctx *c, int nsrc, int nmis, int nrec, const int *slot_receiver, const float *misfit,
+                           const float *norm, int outer_norm, const double *receiver_weights, int anarchy, int ndraw,
+                           const double *draw_weights, double *best_value, int *best_index, int which_draw,
+                           double *global_of_draw)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    outer::run(c, nsrc, nmis, nrec, slot_receiver, misfit, norm, outer_norm, receiver_weights, anarchy, ndraw, draw_weights,
+               best_value, best_index, which_draw, global_of_draw);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_get_outer_ms(kiwi_hip_ctx *c, float ms[3])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 3; i++) ms[i] = c->outer_ms[i];
+    return 0;
+}
+
+int kiwi_hip_outer_max_receivers(void) { return outer::kMaxRec; }
 
 int kiwi_hip_get_geometry(kiwi_hip_ctx *c, int isrc, int irec, int maxcent, int *ncent, void *records)
 {

@@ -502,6 +502,89 @@ class Engine:
             j += k
         return mis, nor, failings
 
+    def outer_max_receivers(self):
+        """The most receivers `outer_misfits` takes (the weight rows of a draw tile live in LDS)."""
+        return int(self.L.kiwi_hip_outer_max_receivers())
+
+    def outer_misfits_slots(self, misfit, norm, slot_receiver, nrec, outer_norm="l2norm", receiver_weights=None, anarchy=False,
+                            draw_weights=None, which_draw=None):
+        """kiwi_hip_outer_misfits on per-slot arrays: misfit, norm [N_s, nmis] float32 as `get_misfits` / `misfits_for_params`
+        return them, `slot_receiver[nmis]` the 0-based receiver of every slot (ascending), `draw_weights[B, nrec]` the weight of
+        every receiver in every draw (None: one draw of ones).  Returns (best_value[B] float64, best_index[B] int32,
+        global_of_draw[N_s] float64 or None): the lowest global misfit of each draw and its source -- among equal values the
+        lowest index; NaN, 0 where every source is excluded -- and the global misfits of all sources under draw `which_draw`."""
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        m = np.ascontiguousarray(misfit, np.float32)
+        n = np.ascontiguousarray(norm, np.float32)
+        sr = np.ascontiguousarray(slot_receiver, np.int32)
+        if m.ndim != 2 or m.shape != n.shape or m.shape[1] != len(sr):
+            raise KiwiHipError("outer_misfits: misfit and norm must be [N_s, nmis] with one slot_receiver entry per slot")
+        nrec = int(nrec)
+        dw = np.ones((1, nrec)) if draw_weights is None else np.ascontiguousarray(draw_weights, np.float64)
+        if dw.ndim != 2 or dw.shape[1] != nrec:
+            raise KiwiHipError("outer_misfits: draw_weights must be [B, %d]" % nrec)
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        nd = len(dw)
+        bv, bi = np.zeros(nd, np.float64), np.zeros(nd, np.int32)
+        g = None if which_draw is None else np.zeros(len(m), np.float64)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        self._ck(self.L.kiwi_hip_outer_misfits(self.h, len(m), m.shape[1], nrec, _ip(sr), _fp(m), _fp(n), code, dp(w),
+                                               1 if anarchy else 0, nd, dp(dw), dp(bv), _ip(bi),
+                                               0 if which_draw is None else int(which_draw), dp(g)), "outer_misfits")
+        return bv, bi, g
+
+    def outer_ms(self):
+        """HIP-event durations [ms] of the last outer_misfits: (uploads, kernels, downloads)."""
+        ms = np.zeros(3, np.float32)
+        self._ck(self.L.kiwi_hip_get_outer_ms(self.h, _fp(ms)), "get_outer_ms")
+        return tuple(float(x) for x in ms)
+
+    def outer_misfits(self, misfits_by_src, norms_by_src, outer_norm="l2norm", receiver_weights=None, anarchy=False,
+                      draw_weights=None, which_draw=None, ncomponents=None):
+        """`make_global_misfits` under B receiver weightings and the best source of each, on the device, from the
+        [N_s, N_r, N_k] arrays `make_misfits_for_sources` returns.  The slot map comes from the receivers' components
+        (`ncomponents`: slots per receiver, for arrays that are not this engine's own); the values go to the device as
+        float32, which is what the engine produced them in.  See `outer_misfits_slots` for the draws and the results."""
+        m = np.asarray(misfits_by_src)
+        n = np.asarray(norms_by_src)
+        if m.ndim != 3 or m.shape != n.shape:
+            raise KiwiHipError("outer_misfits: misfits and norms must be [N_s, N_r, N_k]")
+        nk = [len(c) for c in getattr(self, "components", [])] if ncomponents is None else [int(k) for k in ncomponents]
+        ns, nrec, kmax = m.shape
+        if len(nk) != nrec or max(nk + [0]) > kmax:
+            raise KiwiHipError("outer_misfits: the arrays do not match the receivers' components")
+        slot_receiver = np.repeat(np.arange(nrec, dtype=np.int32), nk)
+        if all(k == kmax for k in nk):
+            mf, nf = m.reshape(ns, nrec * kmax), n.reshape(ns, nrec * kmax)
+        else:
+            cols = np.concatenate([ir * kmax + np.arange(k) for ir, k in enumerate(nk)] + [np.zeros(0, np.int64)]).astype(np.int64)
+            mf, nf = m.reshape(ns, nrec * kmax)[:, cols], n.reshape(ns, nrec * kmax)[:, cols]
+        return self.outer_misfits_slots(mf, nf, slot_receiver, nrec, outer_norm, receiver_weights, anarchy, draw_weights,
+                                        which_draw)
+
+
+def bootstrap_draw_weights(nrec, ndraw, rng, receiver_mask=None, receiver_weights=None):
+    """The resampling counts of `ndraw` bootstrap draws over the enabled receivers, [ndraw, nrec] float64: row d is the
+    `bweights` of the d-th successive `make_global_misfits(..., bootstrap=True, rng=rng)` call.  The generator is consumed
+    exactly as those calls consume it: one `rng.integers(0, ne, ne)` per draw.  (One `rng.integers(0, ne, (ndraw, ne))`
+    yields the same values but can leave the generator's buffered 32-bit half in another state, so whatever the caller drew
+    next would differ.)  The device path and the host path so see the same draws from equally seeded generators, and leave
+    them alike (tests/test_outer_bootstrap.py)."""
+    mask = np.ones(nrec, bool) if receiver_mask is None else np.asarray(receiver_mask, bool)
+    if receiver_weights is not None:
+        w = np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,))
+        mask = np.logical_and(mask, w != 0)
+    enabled = np.arange(nrec)[mask]
+    ne = len(enabled)
+    out = np.zeros((ndraw, nrec), np.float64)
+    for d in range(ndraw):
+        out[d] = np.bincount(enabled[rng.integers(0, ne, ne)], minlength=nrec)
+    return out
+
 
 def make_global_misfits(misfits_by_src, norms_by_src, outer_norm="l2norm", receiver_weights=None, receiver_mask=None,
                         anarchy=False, bootstrap=False, rng=None):

@@ -298,6 +298,32 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: status(*)           ! (nsrc)
         end function
 
+        ! make_global_misfits under ndraw receiver weightings and the best source of each, on host arrays (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_outer_misfits( ctx, nsrc, nmis, nrec, slot_receiver, misfit, norm, outer_norm, &
+                receiver_weights, anarchy, ndraw, draw_weights, best_value, best_index, which_draw, global_of_draw ) &
+                bind(C, name='kiwi_hip_outer_misfits')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: nsrc, nmis, nrec, outer_norm, anarchy, ndraw, which_draw    ! receivers, sources, draws 0-based
+            integer(c_int), intent(in) :: slot_receiver(*)
+            real(c_float), intent(in) :: misfit(*), norm(*)
+            type(c_ptr), value :: receiver_weights        ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            real(c_double), intent(in) :: draw_weights(*)
+            real(c_double), intent(out) :: best_value(*)
+            integer(c_int), intent(out) :: best_index(*)
+            type(c_ptr), value :: global_of_draw          ! c_loc of real(c_double) (nsrc), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_outer_max_receivers() bind(C, name='kiwi_hip_outer_max_receivers')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_get_outer_ms( ctx, ms ) bind(C, name='kiwi_hip_get_outer_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(3)
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

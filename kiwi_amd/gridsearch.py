@@ -4,7 +4,7 @@ counterpart of python/tunguska/source.py:119-164 (`Source.grid`) and gridsearch.
 kiwi_amd/shard.py: the first grid parameter varies slowest."""
 import numpy as np
 
-from .engine import SOURCE_TYPES, make_global_misfits
+from .engine import SOURCE_TYPES, bootstrap_draw_weights, make_global_misfits
 from .lib import KiwiHipError
 
 # wire order of set_source_params (source_bilat.f90:93-106, source_circular.f90:92-102, source_eikonal.f90:97-114,
@@ -99,6 +99,7 @@ class MisfitGrid:
         the inversion.  With a torch.distributed group the grid is sharded over the ranks (kiwi_amd/shard.py)."""
         self.receiver_mask = np.array(engine.enabled, bool)
         self.nreceivers = len(engine.components)
+        self.ncomponents = [len(c) for c in engine.components]
         if len(self.sources):
             if dist is not None:
                 from .shard import sharded_misfits_for_sources
@@ -118,8 +119,26 @@ class MisfitGrid:
         ibest = int(np.nanargmin(g)) if np.any(np.isfinite(g)) else 0
         return ibest, g, g_sr
 
-    def postprocess(self, bootstrap_iterations=1000, rng=None, **outer_misfit_config):
-        """Global misfits, best source, bootstrap distribution of the best source (gridsearch.py:199-289)."""
+    def _postprocess_device(self, engine, bootstrap_iterations, rng, outer_norm="l2norm", receiver_weights=None, anarchy=False):
+        nrec = self.misfits_by_src.shape[1]
+        counts = bootstrap_draw_weights(nrec, bootstrap_iterations, rng, self.receiver_mask, receiver_weights)
+        draws = np.concatenate([np.ones((1, nrec)), counts], 0)
+        _, best, g = engine.outer_misfits(self.misfits_by_src, self.norms_by_src, outer_norm, receiver_weights, anarchy, draws,
+                                          which_draw=0, ncomponents=self.ncomponents)
+        _, g_sr = make_global_misfits(self.misfits_by_src, self.norms_by_src, outer_norm=outer_norm,
+                                      receiver_weights=receiver_weights, receiver_mask=self.receiver_mask, anarchy=anarchy)
+        ibest = int(best[0])
+        self.ibest, self.best_source, self.misfits_by_s = ibest, self.sources[ibest], g
+        self.misfits_by_r, self.variability_by_r = g_sr[ibest], np.std(g_sr, 0)
+        self.bootstrap_sources = [self.sources[int(i)] for i in best[1:]]
+
+    def postprocess(self, bootstrap_iterations=1000, rng=None, engine=None, **outer_misfit_config):
+        """Global misfits, best source, bootstrap distribution of the best source (gridsearch.py:199-289).
+        With `engine` (a kiwi_amd.Engine) the best source and the bootstrap sources come from ONE device call
+        (Engine.outer_misfits: draw 0 = every receiver once, draws 1..B = the resampling counts, drawn from `rng` exactly
+        as the host path draws them) and `misfits_by_s` from that call's draw 0; `misfits_by_r` and `variability_by_r` stay
+        on the host (one pass).  The device's global misfits differ from the host's by a few ulp; without
+        `engine` nothing changes."""
         g, g_sr = make_global_misfits(self.ref_misfits_by_src, self.ref_norms_by_src, receiver_mask=self.receiver_mask,
                                       **outer_misfit_config)
         self.ref_misfit, self.ref_misfits_by_r = g[0], g_sr[0]
@@ -127,12 +146,15 @@ class MisfitGrid:
             self.best_source, self.misfits_by_s, self.misfits_by_r, self.variability_by_r = self.base_params, [], [], []
             self.bootstrap_sources, self.stats = [], {}
             return
-        ibest, g, g_sr = self._best_source(**outer_misfit_config)
-        self.ibest, self.best_source, self.misfits_by_s = ibest, self.sources[ibest], g
-        self.misfits_by_r, self.variability_by_r = g_sr[ibest], np.std(g_sr, 0)
         rng = np.random.default_rng() if rng is None else rng
-        self.bootstrap_sources = [self.sources[self._best_source(bootstrap=True, rng=rng, **outer_misfit_config)[0]]
-                                  for _ in range(bootstrap_iterations)]
+        if engine is not None:
+            self._postprocess_device(engine, bootstrap_iterations, rng, **outer_misfit_config)
+        else:
+            ibest, g, g_sr = self._best_source(**outer_misfit_config)
+            self.ibest, self.best_source, self.misfits_by_s = ibest, self.sources[ibest], g
+            self.misfits_by_r, self.variability_by_r = g_sr[ibest], np.std(g_sr, 0)
+            self.bootstrap_sources = [self.sources[self._best_source(bootstrap=True, rng=rng, **outer_misfit_config)[0]]
+                                      for _ in range(bootstrap_iterations)]
         names = SOURCE_PARAMS[self.sourcetype]
         self.stats = {}
         for param, gvalues in self.param_values:

@@ -118,6 +118,10 @@ def load():
         "kiwi_hip_get_source_centroids": [vp, C.c_int, C.c_int, c_int_p, c_float_p],
         "kiwi_hip_get_reference": [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, C.c_int],
         "kiwi_hip_get_kernel_ms": [vp, c_float_p, c_int_p],
+        "kiwi_hip_outer_misfits": [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_float_p, c_float_p, C.c_int, c_double_p, C.c_int,
+                                   C.c_int, c_double_p, c_double_p, c_int_p, C.c_int, c_double_p],
+        "kiwi_hip_outer_max_receivers": [],
+        "kiwi_hip_get_outer_ms": [vp, c_float_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],

@@ -108,3 +108,57 @@ def sharded_misfits_for_sources(engine, sourcetype, params, dist=None, device_in
     k = (allb.shape[1] - 1) // 2
     failings = [int(i) for i in np.nonzero(allb[:, 2 * k])[0]]
     return allb[:, :k].reshape((-1,) + shape), allb[:, k:2 * k].reshape((-1,) + shape), failings
+
+
+def combine_draw_minima(values, indices, offsets):
+    """The per-draw minima of `world` contiguous shards folded into those of the whole list: values[world, B] the lowest
+    global misfit of each draw within a shard (NaN: the shard had no candidate), indices[world, B] its source WITHIN the
+    shard, offsets[world] the shards' first sources in the whole list.  Lowest value first, then the lowest GLOBAL index
+    (numpy's nanargmin over the whole list; kiwi_outer.hpp applies the same order at every level, so the cut does not show).
+    Returns (value[B], index[B]); a draw without any candidate answers NaN, 0."""
+    v = np.atleast_2d(np.asarray(values, np.float64))
+    gi = np.atleast_2d(np.asarray(indices, np.int64)) + np.asarray(offsets, np.int64)[:, None]
+    bv = np.full(v.shape[1], np.nan)
+    bi = np.zeros(v.shape[1], np.int64)
+    for r in range(v.shape[0]):
+        has = ~np.isnan(v[r])
+        take = has & (np.isnan(bv) | (v[r] < bv) | ((v[r] == bv) & (gi[r] < bi)))
+        bv = np.where(take, v[r], bv)
+        bi = np.where(take, gi[r], bi)
+    return bv, bi
+
+
+def sharded_bootstrap(engine, misfits_by_src, norms_by_src, nsrc_total, outer_norm="l2norm", receiver_weights=None, anarchy=False,
+                      draw_weights=None, dist=None, device_index=None, ncomponents=None):
+    """The best source of every draw over all ranks without gathering the misfits: this rank runs Engine.outer_misfits on
+    its OWN contiguous share (`misfits_by_src`, `norms_by_src`: the [n, N_r, N_k] arrays of shard_range(nsrc_total, world,
+    rank), as make_misfits_for_sources returned them), then B (value, index) pairs per rank are all-gathered and folded by
+    combine_draw_minima -- B pairs instead of N_s x nmis misfits.  `draw_weights[B, N_r]` is taken from rank 0 (broadcast),
+    so the ranks need not seed alike.  Returns (best_value[B], best_index[B]) with indices into the whole list, equal on
+    every rank and bit-identical to the unsharded call."""
+    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+    rank = dist.get_rank() if world > 1 else 0
+    lo, hi = shard_range(nsrc_total, world, rank)
+    if hi - lo != len(misfits_by_src):
+        raise ValueError("this rank's arrays do not match its share of the list")
+    dw = np.ascontiguousarray(draw_weights, np.float64)
+    if world > 1:
+        import torch
+        use_cuda = dist.get_backend() == "nccl"
+        dev = torch.device("cuda", device_index if device_index is not None else torch.cuda.current_device()) \
+            if use_cuda else torch.device("cpu")
+        t = torch.from_numpy(dw).to(dev)
+        dist.broadcast(t, 0)
+        dw = np.ascontiguousarray(t.cpu().numpy())
+    if hi > lo:
+        bv, bi, _ = engine.outer_misfits(misfits_by_src, norms_by_src, outer_norm, receiver_weights, anarchy, dw, ncomponents=ncomponents)
+    else:
+        bv, bi = np.full(len(dw), np.nan), np.zeros(len(dw), np.int32)
+    if world == 1:
+        return combine_draw_minima(bv[None], bi[None], [0])
+    pair = torch.from_numpy(np.stack([bv, bi.astype(np.float64)])).to(dev)       # (an index below 2^31 is exact in fp64)
+    out = torch.empty((world * 2, pair.shape[1]), dtype=torch.float64, device=dev)
+    dist.all_gather_into_tensor(out, pair)
+    out = out.cpu().numpy().reshape(world, 2, -1)
+    offsets = [shard_range(nsrc_total, world, r)[0] for r in range(world)]
+    return combine_draw_minima(out[:, 0], out[:, 1].astype(np.int64), offsets)

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Register / LDS / spill table of the accumulate kernels, per kernel family and arithmetic contract, from the compiler's own
+"""Register / LDS / spill table of the accumulate kernels, per kernel family and arithmetic contract, and of the outer-misfit
+kernels (kiwi_outer.hpp), from the compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
 Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json]"""
 import json
@@ -15,7 +16,34 @@ FAMILIES = {1: "direct", 2: "grouped", 3: "multi", 4: "cell"}
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "") for o in out]
+    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::") for o in out]
+
+
+KEYS = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"),
+        ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"),
+        ("sgpr_spill", r"SGPRs Spill: (\d+)"), ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
+
+
+def collect_outer():
+    """The outer-misfit kernels (kiwi_outer.hpp, namespace outer), compiled into kiwi_hip.o under the exact contract only
+    (`make -C kiwi_amd/csrc asm-hip`)."""
+    r = subprocess.run(["make", "-s", "-C", CSRC, "asm-hip"], capture_output=True, text=True)
+    rows, cur = [], None
+    for line in (r.stderr + r.stdout).split("\n"):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = None
+            if m.group(1).startswith("_ZN5outer"):
+                cur = {"family": "outer", "arith": "exact", "mangled": m.group(1)}
+                rows.append(cur)
+            continue
+        if cur is None:
+            continue
+        for key, pat in KEYS:
+            m = re.search(pat, line)
+            if m:
+                cur[key] = int(m.group(1))
+    return rows
 
 
 def collect():
@@ -40,6 +68,7 @@ def collect():
                     m = re.search(pat, line)
                     if m:
                         cur[key] = int(m.group(1))
+    rows += collect_outer()
     names = demangle([r["mangled"] for r in rows])
     for r, n in zip(rows, names):
         r["kernel"] = n
