@@ -224,6 +224,33 @@ int kiwi_hip_eikonal_cache_stats(long long *hits, long long *misses, int reset);
  * *fallbacks (may be NULL) = how often, since the library was loaded, the optimised march handed a solve to the plain one. */
 int kiwi_hip_fast_marching(const float *speed, int nx, int ny, const float *origin, const float *delta, const float *start,
                            float discard, int plain, float *times, long long *fallbacks);
+/* nsolve independent solves in one call; solve k has an nx[k] x ny[k] grid, x fastest, its speeds at speed + ofs[k], its times
+ * written to times + ofs[k]; origin, delta, start are [nsolve][2]; discard is [nsolve] (NaN: none).
+ * where: 0 = the host's routine (the march of kiwi_hip_fast_marching(plain = 0)) on the discretiser's thread team; needs no GPU
+ *            and accepts ctx == NULL;
+ *        1 = the device of ctx: one solve per wavefront, each the reference's sequential march (same bits on every node),
+ *            on a stream and buffers of the solver's own, cut into several launches where the workspace (16 bytes per node)
+ *            would exceed KIWI_HIP_CHUNK_MB.  A solve whose front outgrows the device heap (4096 entries) is solved again by
+ *            the host's routine.  Grids with (nx + 2) * (ny + 2) > INT_MAX are refused.
+ * *fallbacks (may be NULL): solves of this call handed on -- by the device to the host (where = 1), by the host's optimised
+ * march to the plain one (where = 0). */
+int kiwi_hip_fast_marching_batch(kiwi_hip_ctx *ctx, int where, int nsolve, const int *nx, const int *ny, const long long *ofs,
+                                 const float *speed, const float *origin, const float *delta, const float *start,
+                                 const float *discard, float *times, long long *fallbacks);
+/* Where the eikonal discretisers (kiwi_hip_set_sources_params, kiwi_hip_misfits_for_params, kiwi_hip_minimize_lm) run the
+ * fast-marching solves of a batch: 0 host (default), 1 device -- the solves the cache does not answer go out as one
+ * kiwi_hip_fast_marching_batch(where = 1).  Results do not depend on it.  Forwarded to every device of a multi-device context.
+ * Initial value: KIWI_HIP_EIK_DEVICE=0|1 in the environment, read at kiwi_hip_init. */
+int kiwi_hip_set_eikonal_solver(kiwi_hip_ctx *ctx, int where);
+int kiwi_hip_get_eikonal_solver(kiwi_hip_ctx *ctx, int *where);
+/* upload, kernel and download milliseconds (HIP events, summed over its launches) of the context's last device batch;
+ * any pointer may be NULL; zeros before the first one */
+int kiwi_hip_get_eikonal_solver_ms(kiwi_hip_ctx *ctx, double *upload, double *kernel, double *download);
+/* of the same batch: kernel launches it took (KIWI_HIP_CHUNK_MB) and the largest heap any of its solves reached (entries; the
+ * device heap holds 4096); either pointer may be NULL */
+int kiwi_hip_get_eikonal_solver_stats(kiwi_hip_ctx *ctx, int *launches, int *heap_high_water);
+/* 1 when the host's optimised march and the device march take an nx x ny grid (its padded size fits an int), else 0 */
+int kiwi_hip_fast_marching_grid_ok(long long nx, long long ny);
 
 /* minimize_lm (minimizer_engine.f90:728-874; sminpack/lmdif.f in fp32 with the reference's settings: ftol = xtol =
  * sqrt(spmpar(1)), gtol = 0, maxfev = 500 (n + 1), mode 2 with diag = 1, factor 0.01) over the parameters with

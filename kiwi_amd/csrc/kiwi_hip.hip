@@ -11,10 +11,12 @@
 #include "kiwi_geometry.hpp"
 #include "kiwi_misfit.hpp"
 #include "kiwi_accum_api.hpp"
+#include "kiwi_fmm_device.hpp"
 
 #include <hip/hip_runtime.h>
 #include <hipfft/hipfft.h>
 #include <algorithm>
+#include <array>
 #include <map>
 #include <tuple>
 #include <cstdio>
@@ -84,6 +86,35 @@ struct Receiver {
 };
 
 struct EventPair { hipEvent_t a, b; int kind; };
+
+// One solve of a fast-marching batch as the packed interface and the discretiser hand it over
+struct FmmJob {
+    const float *speed; float *times;
+    int nx, ny;
+    float origin[2], delta[2], start[2], discard;
+};
+
+// The device solver of a context (kiwi_fmm_device.hpp): a stream, buffers and events of its own, so that a batch can run from
+// the producer thread of kiwi_hip_misfits_for_params while the context's stream evaluates the piece before.
+struct FmmDev {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    DevBuf<float> speed_d, times_d;
+    DevBuf<fmmdev::Node> nodes_d;
+    DevBuf<fmmdev::Solve> solves_d;
+    DevBuf<int> status_d;                  // [2 * solves of a launch]: status, then the heap's high-water mark
+    long long dev_bytes = 0;
+    double ms[3] = { 0.0, 0.0, 0.0 };      // upload, kernel, download of the last batch
+    int last_hiwater = 0, last_launches = 0;
+    void release()
+    {
+        speed_d.release(); times_d.release(); nodes_d.release(); solves_d.release(); status_d.release();
+        for (auto &e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+        if (stream) (void)hipStreamDestroy(stream);
+        stream = nullptr;
+    }
+};
 
 } // namespace
 
@@ -203,6 +234,8 @@ struct kiwi_hip_ctx {
     int proc_chunk0 = 0, proc_chunkn = 0, proc_which_held = 0;   // what proc_d currently holds
     size_t chunk_bytes_limit = (size_t)16 << 30;      // workspace per launch; the device has 288 GB
     float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
+    int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
+    mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
 
     // spectral / filtered comparator (hipFFT).  The transform length belongs to the (trial source, slot) pair
     // (fft_size_kernel); the reference-side data that depend on it -- amplitude spectrum, filter weights per bin,
@@ -1453,6 +1486,7 @@ int kiwi_hip_init(int device, kiwi_hip_ctx **out)
             const long v = std::atol(m);
             if (v > 0) c->chunk_bytes_limit = (size_t)v << 20;
         }
+        if (const char *m = std::getenv("KIWI_HIP_EIK_DEVICE")) c->eik_solver = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_RUNS")) {          // 0: no tile sharing across sources; n > 1: longest run
             const int v = std::atoi(m);
             c->share_runs = v != 0;
@@ -1522,6 +1556,7 @@ int kiwi_hip_destroy(kiwi_hip_ctx *c)
     if (c->mate_event) (void)hipEventDestroy(c->mate_event);
     if (c->pairs_pin) (void)hipHostFree(c->pairs_pin);
     if (c->size_event) (void)hipEventDestroy(c->size_event);
+    c->fmm.release();
     (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
@@ -1893,6 +1928,11 @@ int kiwi_hip_set_source_constraints(kiwi_hip_ctx *c, int n, const float *points,
     GUARD_END(c)
 }
 
+static bool eik_staged_env();
+static void eikonal_staged(const kiwi_hip_ctx *c, int where, int sourcetype, const std::vector<int> &idx, const float *params, int np, float edt,
+                           const CrustProfile &prof, const std::vector<HalfSpace> &cons, int nthreads, DiscreteSource *ds,
+                           std::vector<std::string> &errs, double *solve_ms, int *nsolved);
+
 int kiwi_hip_discretize_eikonal(int sourcetype, const float *params, int nparams, float effective_dt,
                                 const float *rupture_profile, int ncon, const float *points, const float *normals,
                                 float *cent, int maxcent, int *ncent, float *moment, float *risetime)
@@ -1903,7 +1943,12 @@ int kiwi_hip_discretize_eikonal(int sourcetype, const float *params, int nparams
         for (int i = 0; i < ncon; i++)
             for (int k = 0; k < 3; k++) { cons[i].point[k] = points[3 * i + k]; cons[i].normal[k] = normals[3 * i + k]; }
         DiscreteSource ds;
-        const std::string err = discretize_eikonal(sourcetype, params, effective_dt, unpack_profile(rupture_profile), cons, ds);
+        std::string err;
+        if (eik_staged_env()) {
+            std::vector<std::string> errs;
+            eikonal_staged(nullptr, 0, sourcetype, std::vector<int>{ 0 }, params, nparams, effective_dt, unpack_profile(rupture_profile), cons, 1, &ds, errs, nullptr, nullptr);
+            err = errs[0];
+        } else err = discretize_eikonal(sourcetype, params, effective_dt, unpack_profile(rupture_profile), cons, ds);
         if (!err.empty()) return err[0] == 'E' ? 5 : 6;      // 5: empty rupture area, 6: nucleation point outside
         *ncent = (int)ds.centroids.size();
         if (moment) *moment = ds.moment;
@@ -2119,12 +2164,249 @@ int kiwi_hip_fast_marching(const float *speed, int nx, int ny, const float *orig
     } catch (...) { return 1; }
 }
 
+// threads of the host discretiser's team for n independent pieces of work (`spare` = CPUs left to the caller's other threads)
+static int disc_team(const kiwi_hip_ctx *c, int spare, int n)
+{
+    int ecap = std::max(1, (effective_cpus() - std::max(0, spare)) / std::max(1, c ? c->cpu_share : 1));
+    if (const char *m = std::getenv("KIWI_HIP_DISC_THREADS")) ecap = std::max(1, std::atoi(m));
+    return std::max(1, std::min({ omp_get_max_threads(), n, ecap }));
+}
+
+// the start cell exactly as fast_marching_plain computes it (eikonal.f90:70-76)
+static void fmm_start_cell(const FmmJob &j, int &ix, int &iy)
+{
+    ix = (int)((j.start[0] - j.origin[0]) / j.delta[0]) + 1; iy = (int)((j.start[1] - j.origin[1]) / j.delta[1]) + 1;
+    ix = std::min(std::max(ix, 1), j.nx);
+    iy = std::min(std::max(iy, 1), j.ny);
+}
+
+// a batch of solves by the host's routine, over `nthreads` threads; returns how many of them the optimised march handed to the plain one
+static long long fmm_host_batch(const std::vector<FmmJob> &jobs, int nthreads)
+{
+    const long long before = eik::fmm_fallbacks().load();
+    const int n = (int)jobs.size();
+    std::exception_ptr err;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (int k = 0; k < n; k++) {
+        try {
+            static thread_local std::vector<float> t;
+            const FmmJob &j = jobs[(size_t)k];
+            eik::fast_marching(j.speed, j.nx, j.ny, j.origin, j.delta, j.start, t, j.discard);
+            std::memcpy(j.times, t.data(), t.size() * sizeof(float));
+        } catch (...) {
+#pragma omp critical
+            err = std::current_exception();
+        }
+    }
+    if (err) std::rethrow_exception(err);
+    return eik::fmm_fallbacks().load() - before;
+}
+
+// a batch of solves on the context's device (kiwi_fmm_device.hpp), on the solver's own stream, in as many launches as the
+// workspace bound asks for; solves that outgrow the device heap are done again by the host's routine.  Returns their number.
+static long long fmm_device_batch(const kiwi_hip_ctx *c, const std::vector<FmmJob> &jobs, int nthreads)
+{
+    FmmDev &d = c->fmm;
+    std::lock_guard<std::mutex> lk(d.mu);
+    const size_t n = jobs.size();
+    for (const FmmJob &j : jobs)
+        if (!eik::grid_fits_int(j.nx, j.ny))
+            throw std::runtime_error("fast-marching grid of " + std::to_string(j.nx) + " x " + std::to_string(j.ny) + " nodes is too large for the device march ((nx + 2) * (ny + 2) exceeds INT_MAX)");
+    HIPCHECK(hipSetDevice(c->device));
+    if (!d.stream) {
+        HIPCHECK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+        for (auto &e : d.ev) HIPCHECK(hipEventCreate(&e));
+    }
+    d.ms[0] = d.ms[1] = d.ms[2] = 0.0;
+    d.last_hiwater = 0; d.last_launches = 0;
+    constexpr size_t kBytesPerNode = 2 * sizeof(float) + sizeof(fmmdev::Node);       // speed, time, node record
+    std::vector<FmmJob> redo;
+    std::vector<fmmdev::Solve> sv;
+    std::vector<int> st;
+    for (size_t k0 = 0; k0 < n;) {
+        size_t k1 = k0, nodes = 0;
+        while (k1 < n) {                                                              // (a launch holds at least one solve)
+            const size_t nn = (size_t)jobs[k1].nx * jobs[k1].ny;
+            if (k1 > k0 && (nodes + nn) * kBytesPerNode > c->chunk_bytes_limit) break;
+            nodes += nn; k1++;
+        }
+        const size_t m = k1 - k0;
+        sv.resize(m);
+        size_t ofs = 0;
+        for (size_t k = 0; k < m; k++) {
+            const FmmJob &j = jobs[k0 + k];
+            fmmdev::Solve &q = sv[k];
+            q.ofs = (long long)ofs; q.nx = j.nx; q.ny = j.ny;
+            fmm_start_cell(j, q.ix, q.iy);
+            q.dx = j.delta[0]; q.dy = j.delta[1]; q.discard = j.discard; q.pad = 0;
+            ofs += (size_t)j.nx * j.ny;
+        }
+        d.speed_d.ensure(nodes, &d.dev_bytes); d.times_d.ensure(nodes, &d.dev_bytes); d.nodes_d.ensure(nodes, &d.dev_bytes);
+        d.solves_d.ensure(m, &d.dev_bytes); d.status_d.ensure(2 * m, &d.dev_bytes);
+        HIPCHECK(hipEventRecord(d.ev[0], d.stream));
+        HIPCHECK(hipMemcpyAsync(d.solves_d.p, sv.data(), m * sizeof(fmmdev::Solve), hipMemcpyHostToDevice, d.stream));
+        for (size_t k = 0; k < m; k++)
+            HIPCHECK(hipMemcpyAsync(d.speed_d.p + sv[k].ofs, jobs[k0 + k].speed, (size_t)sv[k].nx * sv[k].ny * sizeof(float), hipMemcpyHostToDevice, d.stream));
+        HIPCHECK(hipEventRecord(d.ev[1], d.stream));
+        hipLaunchKernelGGL(fmmdev::fmm_batch_kernel, dim3((unsigned)m), dim3(64), 0, d.stream, d.solves_d.p, d.speed_d.p, d.nodes_d.p, d.times_d.p,
+                           d.status_d.p, d.status_d.p + m);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(d.ev[2], d.stream));
+        st.resize(2 * m);
+        HIPCHECK(hipMemcpyAsync(st.data(), d.status_d.p, 2 * m * sizeof(int), hipMemcpyDeviceToHost, d.stream));
+        for (size_t k = 0; k < m; k++)
+            HIPCHECK(hipMemcpyAsync(jobs[k0 + k].times, d.times_d.p + sv[k].ofs, (size_t)sv[k].nx * sv[k].ny * sizeof(float), hipMemcpyDeviceToHost, d.stream));
+        HIPCHECK(hipEventRecord(d.ev[3], d.stream));
+        HIPCHECK(hipStreamSynchronize(d.stream));
+        for (int q = 0; q < 3; q++) { float ms = 0.f; HIPCHECK(hipEventElapsedTime(&ms, d.ev[q], d.ev[q + 1])); d.ms[q] += ms; }
+        for (size_t k = 0; k < m; k++) {
+            if (st[k] != 0) redo.push_back(jobs[k0 + k]);
+            d.last_hiwater = std::max(d.last_hiwater, st[m + k]);
+        }
+        d.last_launches++;
+        k0 = k1;
+    }
+    if (!redo.empty()) fmm_host_batch(redo, std::min(nthreads, (int)redo.size()));
+    return (long long)redo.size();
+}
+
+int kiwi_hip_fast_marching_grid_ok(long long nx, long long ny) { return eik::grid_fits_int(nx, ny) ? 1 : 0; }
+
+int kiwi_hip_fast_marching_batch(kiwi_hip_ctx *c, int where, int nsolve, const int *nx, const int *ny, const long long *ofs,
+                                 const float *speed, const float *origin, const float *delta, const float *start,
+                                 const float *discard, float *times, long long *fallbacks)
+{
+    GUARD_BEGIN
+    if (!nx || !ny || !ofs || !speed || !origin || !delta || !start || !discard || !times) throw std::runtime_error("kiwi_hip_fast_marching_batch: null argument");
+    if (nsolve < 1) throw std::runtime_error("kiwi_hip_fast_marching_batch: need at least one solve");
+    if (where != 0 && where != 1) throw std::runtime_error("kiwi_hip_fast_marching_batch: where must be 0 (host) or 1 (device)");
+    if (where == 1 && !c) throw std::runtime_error("kiwi_hip_fast_marching_batch: the device solver needs a context");
+    std::vector<FmmJob> jobs((size_t)nsolve);
+    for (int k = 0; k < nsolve; k++) {
+        if (nx[k] < 1 || ny[k] < 1) throw std::runtime_error("kiwi_hip_fast_marching_batch: solve " + std::to_string(k + 1) + " has a grid side < 1");
+        if (ofs[k] < 0) throw std::runtime_error("kiwi_hip_fast_marching_batch: negative offset");
+        FmmJob &j = jobs[(size_t)k];
+        j.speed = speed + ofs[k]; j.times = times + ofs[k]; j.nx = nx[k]; j.ny = ny[k];
+        for (int q = 0; q < 2; q++) { j.origin[q] = origin[2 * k + q]; j.delta[q] = delta[2 * k + q]; j.start[q] = start[2 * k + q]; }
+        j.discard = discard[k];
+    }
+    const int nthreads = disc_team(c, 0, nsolve);
+    const long long fb = where == 1 ? fmm_device_batch(c, jobs, nthreads) : fmm_host_batch(jobs, nthreads);
+    if (fallbacks) *fallbacks = fb;
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_set_eikonal_solver(kiwi_hip_ctx *c, int where)
+{
+    if (!c) return fail(c, "null argument");
+    if (where != 0 && where != 1) return fail(c, "kiwi_hip_set_eikonal_solver: 0 (host) or 1 (device)");
+    c->eik_solver = where;
+    return forward(c, [&](kiwi_hip_ctx *m) { return kiwi_hip_set_eikonal_solver(m, where); });
+}
+
+int kiwi_hip_get_eikonal_solver(kiwi_hip_ctx *c, int *where)
+{
+    if (!c || !where) return fail(c, "null argument");
+    *where = c->eik_solver;
+    return 0;
+}
+
+int kiwi_hip_get_eikonal_solver_ms(kiwi_hip_ctx *c, double *upload, double *kernel, double *download)
+{
+    if (!c) return fail(c, "null argument");
+    std::lock_guard<std::mutex> lk(c->fmm.mu);
+    if (upload) *upload = c->fmm.ms[0];
+    if (kernel) *kernel = c->fmm.ms[1];
+    if (download) *download = c->fmm.ms[2];
+    return 0;
+}
+
+int kiwi_hip_get_eikonal_solver_stats(kiwi_hip_ctx *c, int *launches, int *heap_high_water)
+{
+    if (!c) return fail(c, "null argument");
+    std::lock_guard<std::mutex> lk(c->fmm.mu);
+    if (launches) *launches = c->fmm.last_launches;
+    if (heap_high_water) *heap_high_water = c->fmm.last_hiwater;
+    return 0;
+}
+
+// KIWI_HIP_EIK_STAGED=1: the eikonal discretisers take the staged route (prepare, one batch of solves, finish) with the HOST's
+// solver too -- what the device solver's route is tested against on a machine without a GPU.  Read at every call.
+static bool eik_staged_env() { const char *e = std::getenv("KIWI_HIP_EIK_STAGED"); return e && std::atoi(e) != 0; }
+
+// The eikonal discretiser over the ruptures idx[] of a parameter list in three stages (kiwi_host_eikonal.hpp): prepare over the
+// thread team; the solve cache consulted as fast_marching_cached does, solves with identical inputs inside the batch done once
+// (counted as the hits they would be one after the other); the remaining solves as ONE batch -- where = 1: on the device of c,
+// 0: by the host's routine --; results stored under the cache's streak rule; finish over the team.  errs[j]: the reference's
+// error text for idx[j], or "".  solve_ms / nsolved (may be NULL): wall time of the batch of solves and its size.
+static void eikonal_staged(const kiwi_hip_ctx *c, int where, int sourcetype, const std::vector<int> &idx, const float *params, int np, float edt,
+                           const CrustProfile &prof, const std::vector<HalfSpace> &cons, int nthreads, DiscreteSource *ds,
+                           std::vector<std::string> &errs, double *solve_ms, int *nsolved)
+{
+    const int n = (int)idx.size();
+    errs.assign((size_t)n, std::string());
+    std::vector<EikonalStage> st((size_t)n);
+    eik::SolveCache &sc = eik::SolveCache::get();
+    std::vector<eik::CacheProbe> pr((size_t)n);
+    std::vector<char> need((size_t)n, 0);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (int j = 0; j < n; j++) {
+        EikonalStage &q = st[(size_t)j];
+        errs[(size_t)j] = eikonal_prepare(sourcetype, params + (size_t)idx[(size_t)j] * np, edt, prof, cons, q);
+        if (!errs[(size_t)j].empty()) continue;
+        need[(size_t)j] = !(sc.enabled && eik::solve_cache_lookup(q.speed, q.fx, q.fy, q.lo, q.fd, q.start, q.ftimes, q.invalid, pr[(size_t)j]));
+    }
+    std::vector<int> dup_of((size_t)n, -1);
+    if (sc.enabled) {
+        std::map<std::array<unsigned, 7>, std::vector<int>> reps;
+        for (int j = 0; j < n; j++) {
+            if (!need[(size_t)j]) continue;
+            const EikonalStage &q = st[(size_t)j];
+            std::array<unsigned, 7> key{ (unsigned)q.fx, (unsigned)q.fy, (unsigned)pr[(size_t)j].ix, (unsigned)pr[(size_t)j].iy, 0u, 0u, pr[(size_t)j].dbits };
+            std::memcpy(&key[4], &q.fd[0], 4); std::memcpy(&key[5], &q.fd[1], 4);
+            std::vector<int> &list = reps[key];
+            for (int r : list)
+                if (st[(size_t)r].speed.size() == q.speed.size() && std::memcmp(st[(size_t)r].speed.data(), q.speed.data(), q.speed.size() * sizeof(float)) == 0) { dup_of[(size_t)j] = r; break; }
+            if (dup_of[(size_t)j] < 0) list.push_back(j);
+        }
+    }
+    std::vector<FmmJob> jobs;
+    for (int j = 0; j < n; j++) {
+        if (!need[(size_t)j] || dup_of[(size_t)j] >= 0) continue;
+        EikonalStage &q = st[(size_t)j];
+        q.ftimes.resize((size_t)q.fx * q.fy);
+        FmmJob job;
+        job.speed = q.speed.data(); job.times = q.ftimes.data(); job.nx = q.fx; job.ny = q.fy; job.discard = q.invalid;
+        for (int k = 0; k < 2; k++) { job.origin[k] = q.lo[k]; job.delta[k] = q.fd[k]; job.start[k] = q.start[k]; }
+        jobs.push_back(job);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!jobs.empty()) {
+        if (where == 1) fmm_device_batch(c, jobs, nthreads);
+        else fmm_host_batch(jobs, std::min(nthreads, (int)jobs.size()));
+    }
+    if (solve_ms) *solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (nsolved) *nsolved = (int)jobs.size();
+    for (int j = 0; j < n; j++) {
+        if (!need[(size_t)j]) continue;
+        EikonalStage &q = st[(size_t)j];
+        if (dup_of[(size_t)j] >= 0) { q.ftimes = st[(size_t)dup_of[(size_t)j]].ftimes; sc.hits++; sc.miss_streak = 0; }
+        else if (sc.enabled) eik::solve_cache_store(q.speed, q.fx, q.fy, q.fd, q.ftimes, pr[(size_t)j]);
+    }
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (int j = 0; j < n; j++)
+        if (errs[(size_t)j].empty()) errs[(size_t)j] = eikonal_finish(st[(size_t)j], ds[(size_t)idx[(size_t)j]]);
+}
+
 // One batch of trial sources after the host discretiser, before anything touches the device
 struct HostBatch {
     int nsrc = 0, nbad = 0, bad = -1;
     std::string why;
     std::vector<int> ofs, status;
     std::vector<float> cent, mom, rise;
+    double solve_ms = 0.0;         // staged route: wall time of the batch of fast-marching solves, and its size
+    int nsolved = 0;
 };
 
 // psm_set + psm_to_tdsm of every source of the batch (minimizer_engine.f90:500-523), host only: reads the context's
@@ -2173,7 +2455,22 @@ static void discretise_batch(const kiwi_hip_ctx *c, int sourcetype, int nsrc, co
     int nbad = 0, bad = -1;
     std::string why = hb.why;
     std::vector<int> &status = hb.status;
-    if (eikonal) {
+    if (eikonal && (c->eik_solver == 1 || eik_staged_env())) {
+        std::vector<int> idx;
+        for (int s = 0; s < nsrc; s++) if (solve_of[s] == s) idx.push_back(s);
+        std::vector<std::string> errs;
+        eikonal_staged(c, c->eik_solver == 1 ? 1 : 0, sourcetype, idx, params, np, edt, c->rupture_profile, c->constraints,
+                       std::min(nthreads, (int)idx.size()), ds.data(), errs, &hb.solve_ms, &hb.nsolved);
+        for (size_t j = 0; j < idx.size(); j++) {
+            const int s = idx[j];
+            const std::string &err = errs[j];
+            if (!err.empty()) {
+                status[s] = err[0] == 'E' ? 5 : 6;
+                ds[s].centroids.clear(); ds[s].moment = 0.f; ds[s].risetime = 0.f;
+                nbad++; if (bad < 0 || s < bad) { bad = s; why = err; }
+            }
+        }
+    } else if (eikonal) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
         for (int s = 0; s < nsrc; s++) {
             if (solve_of[s] != s) continue;
@@ -2533,6 +2830,38 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
         discretise_batch(c, sourcetype, pieces[(size_t)k].second, params + (size_t)pieces[(size_t)k].first * np, npieces > 1 ? 1 : 0, hb);
         return hb;
     };
+    // Device solver: the latency of a launch of sequential marches does not depend on how many solves it holds, so the pieces
+    // k, k - 1, ... k - g + 1 (contiguous in the list) are discretised as ONE batch -- one launch for all their solves -- and
+    // handed to the evaluation piece by piece as before: the pieces, and with them every result, are the same.
+    // KIWI_HIP_EIK_GROUP: pieces per batch (default 8: up to 1024 solves of the default piece -- one launch fills the device's
+    // 1280 solve slots --, 3.4 MB of host memory per solve in flight).
+    int group = 1;
+    if (c->eik_solver == 1 && source_nparams_eikonal(sourcetype) > 0) {
+        group = 8;
+        if (const char *m = std::getenv("KIWI_HIP_EIK_GROUP")) group = std::max(1, std::atoi(m));
+    }
+    auto work_group = [c, sourcetype, np, params, npieces, &pieces](int k, int g) {      // pieces k - g + 1 .. k, returned in the order k, k - 1, ...
+        const int first = pieces[(size_t)(k - g + 1)].first, end = pieces[(size_t)k].first + pieces[(size_t)k].second;
+        HostBatch all;
+        discretise_batch(c, sourcetype, end - first, params + (size_t)first * np, npieces > 1 ? 1 : 0, all);
+        std::vector<HostBatch> out;
+        for (int q = k; q > k - g; q--) {
+            const int s0 = pieces[(size_t)q].first - first, n = pieces[(size_t)q].second;
+            HostBatch hb;
+            hb.nsrc = n;
+            hb.status.assign(all.status.begin() + s0, all.status.begin() + s0 + n);
+            hb.ofs.resize((size_t)n + 1);
+            for (int s = 0; s <= n; s++) hb.ofs[(size_t)s] = all.ofs[(size_t)(s0 + s)] - all.ofs[(size_t)s0];
+            hb.cent.assign(all.cent.begin() + (size_t)all.ofs[(size_t)s0] * 10, all.cent.begin() + (size_t)all.ofs[(size_t)(s0 + n)] * 10);
+            hb.mom.assign(all.mom.begin() + s0, all.mom.begin() + s0 + n);
+            hb.rise.assign(all.rise.begin() + s0, all.rise.begin() + s0 + n);
+            hb.nbad = 0; hb.bad = -1; hb.why = "source discretisation failed";
+            for (int s = 0; s < n; s++) if (hb.status[(size_t)s]) { hb.nbad++; if (hb.bad < 0) { hb.bad = s; hb.why = status_message(hb.status[(size_t)s]); } }
+            if (q == k) { hb.solve_ms = all.solve_ms; hb.nsolved = all.nsolved; }
+            out.push_back(std::move(hb));
+        }
+        return out;
+    };
     // last piece first: the context is left with the HEAD of the list (sources 0 .. piece - 1), its source 0 the list's.
     // The discretiser runs AHEAD of the device by up to kAhead pieces (round 6; until then it started a piece when the device
     // started the one before, and idled once it was done: with the eikonal types' solves at 0.6 of a piece's device time the
@@ -2547,13 +2876,18 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
     constexpr size_t kAhead = 3;
     std::future<void> producer = std::async(std::launch::async, [&] {
         try {
-            for (int k = npieces - 1; k >= 0; k--) {
-                HostBatch hb = work(k);
-                std::unique_lock<std::mutex> lk(ahead.mu);
-                ahead.cv.wait(lk, [&] { return ahead.q.size() < kAhead || ahead.stop; });
-                if (ahead.stop) return;
-                ahead.q.push_back(std::move(hb));
-                ahead.cv.notify_all();
+            for (int k = npieces - 1; k >= 0;) {
+                const int g = std::min(group, k + 1);
+                std::vector<HostBatch> hbs;
+                if (g > 1) hbs = work_group(k, g); else hbs.push_back(work(k));
+                for (HostBatch &hb : hbs) {
+                    std::unique_lock<std::mutex> lk(ahead.mu);
+                    ahead.cv.wait(lk, [&] { return ahead.q.size() < kAhead || ahead.stop; });
+                    if (ahead.stop) return;
+                    ahead.q.push_back(std::move(hb));
+                    ahead.cv.notify_all();
+                }
+                k -= g;
             }
         } catch (...) {
             std::lock_guard<std::mutex> lk(ahead.mu);
@@ -2593,8 +2927,12 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
         eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
-        if (trace) std::fprintf(stderr, "kiwi_hip piece [%d, %d): waited %.1f ms for the discretiser, upload %.1f ms, evaluation + download %.1f ms\n",
-                                s0, s0 + n, t_got - t_wait, t_up - t_got, now() - t_up);
+        if (trace) {
+            std::fprintf(stderr, "kiwi_hip piece [%d, %d): waited %.1f ms for the discretiser, upload %.1f ms, evaluation + download %.1f ms",
+                         s0, s0 + n, t_got - t_wait, t_up - t_got, now() - t_up);
+            if (hb.nsolved > 0) std::fprintf(stderr, ", its batch of %d fast-marching solves took %.1f ms on the %s", hb.nsolved, hb.solve_ms, c->eik_solver == 1 ? "device" : "host");
+            std::fprintf(stderr, "\n");
+        }
     }
     return 0;
     GUARD_END(c)
@@ -3062,7 +3400,7 @@ int kiwi_hip_build_flags(char *buf, int buflen)
 
 int kiwi_hip_get_device_bytes(kiwi_hip_ctx *c, long long *bytes)
 {
-    *bytes = c->dev_bytes;
+    *bytes = c->dev_bytes + c->fmm.dev_bytes;          // (with the buffers of the device march, kiwi_hip_fast_marching_batch)
     return 0;
 }
 

@@ -183,39 +183,58 @@ struct SolveCache {
     std::atomic<unsigned> probe{ 0 };
 };
 
-inline void fast_marching_cached(const std::vector<float> &speed, int nx, int ny, const float origin[2], const float delta[2],
-                                 const float start[2], std::vector<float> &times, float discard)
+// The cache's two halves around a solve, so that the solve itself can happen elsewhere (a device batch, kiwi_hip.hip):
+// solve_cache_lookup answers a hit (times filled, counted) or remembers what it worked out; solve_cache_store counts the miss and
+// keeps the result under the streak rule.  fast_marching_cached is lookup + fast_marching + store.
+struct CacheProbe { int ix = 0, iy = 0; unsigned dbits = 0; unsigned long long h = 0; bool hashed = false; };
+
+inline bool solve_cache_lookup(const std::vector<float> &speed, int nx, int ny, const float origin[2], const float delta[2],
+                               const float start[2], std::vector<float> &times, float discard, CacheProbe &pr)
 {
     SolveCache &sc = SolveCache::get();
-    if (!sc.enabled) { fast_marching(speed.data(), nx, ny, origin, delta, start, times, discard); return; }
     // the start cell exactly as fast_marching computes it: all it takes from `origin` and `start`
     int ix = (int)((start[0] - origin[0]) / delta[0]) + 1, iy = (int)((start[1] - origin[1]) / delta[1]) + 1;
     ix = std::min(std::max(ix, 1), nx);
     iy = std::min(std::max(iy, 1), ny);
     unsigned dbits;
     std::memcpy(&dbits, &discard, 4);
-    unsigned long long h = 0;
-    bool hashed = false;
+    pr.ix = ix; pr.iy = iy; pr.dbits = dbits; pr.h = 0; pr.hashed = false;
     if (sc.candidates(nx, ny, ix, iy, delta[0], delta[1], dbits)) {
-        h = SolveCache::hash_of(speed, nx, ny, ix, iy, delta[0], delta[1]);
-        hashed = true;
-        if (auto e = sc.find(h, speed, nx, ny, ix, iy, delta[0], delta[1], dbits)) {
+        pr.h = SolveCache::hash_of(speed, nx, ny, ix, iy, delta[0], delta[1]);
+        pr.hashed = true;
+        if (auto e = sc.find(pr.h, speed, nx, ny, ix, iy, delta[0], delta[1], dbits)) {
             times = e->times;
             sc.hits++;
             sc.miss_streak = 0;
-            return;
+            return true;
         }
     }
-    fast_marching(speed.data(), nx, ny, origin, delta, start, times, discard);
+    return false;
+}
+
+inline void solve_cache_store(const std::vector<float> &speed, int nx, int ny, const float delta[2], const std::vector<float> &times, CacheProbe &pr)
+{
+    SolveCache &sc = SolveCache::get();
     sc.misses++;
     if (sc.miss_streak.fetch_add(1) >= SolveCache::kStreak && sc.probe.fetch_add(1) % SolveCache::kProbe != 0) return;
-    if (!hashed) h = SolveCache::hash_of(speed, nx, ny, ix, iy, delta[0], delta[1]);
+    if (!pr.hashed) pr.h = SolveCache::hash_of(speed, nx, ny, pr.ix, pr.iy, delta[0], delta[1]);
     auto e = sc.take_victim();
     if (!e) e = std::make_shared<SolveCache::Entry>();
-    e->hash = h; e->nx = nx; e->ny = ny; e->ix = ix; e->iy = iy; e->dx = delta[0]; e->dy = delta[1]; e->discard = dbits;
+    e->hash = pr.h; e->nx = nx; e->ny = ny; e->ix = pr.ix; e->iy = pr.iy; e->dx = delta[0]; e->dy = delta[1]; e->discard = pr.dbits;
     e->speed.assign(speed.begin(), speed.end());
     e->times.assign(times.begin(), times.end());
     sc.put(std::move(e));
+}
+
+inline void fast_marching_cached(const std::vector<float> &speed, int nx, int ny, const float origin[2], const float delta[2],
+                                 const float start[2], std::vector<float> &times, float discard)
+{
+    SolveCache &sc = SolveCache::get();
+    if (!sc.enabled) { fast_marching(speed.data(), nx, ny, origin, delta, start, times, discard); return; }
+    CacheProbe pr;
+    if (solve_cache_lookup(speed, nx, ny, origin, delta, start, times, discard, pr)) return;
+    fast_marching(speed.data(), nx, ny, origin, delta, start, times, discard);
+    solve_cache_store(speed, nx, ny, delta, times, pr);
 }
 
 // ---- the two passes over the fine grid, four points at a time (round 6) -------------------------------------------------------
@@ -407,24 +426,49 @@ inline void coarse_durations(const std::vector<int> &cellof, const std::vector<f
 
 inline int source_nparams_eikonal(int type) { return type == 4 ? 15 : (type == 5 ? 20 : -1); }
 
+// The eikonal discretiser in three stages around its fast-marching solve -- prepare (everything up to the speed grid and
+// `invalid`, or the early error texts), solve, finish (coarse cells, durations, centroid table) --, with what the stages hand on
+// kept in a structure, so that the solves of a batch can happen elsewhere between prepare and finish (a device batch,
+// kiwi_hip.hip).  discretize_eikonal below is their composition: the host path is the same statements.
+struct EikonalStage {
+    int type = 0;
+    const float *P = nullptr;
+    float doi = 0.f;
+    const CrustProfile *prof = nullptr;
+    const std::vector<HalfSpace> *cons = nullptr;
+    bool mt = false, plain = false;
+    float Rrup[3][3], Rslip[3][3];
+    eik::V3 shift{}, center{};
+    float lo[2], hi[2], ext[2], fd[2], start[2];
+    int fx = 0, fy = 0;
+    eik::FineGrid fg;
+    float minspeed = 0.f, invalid = 0.f;
+    std::vector<float> speed, ftimes;
+    std::vector<eik::V3> fpt;
+};
+
 // returns "" on success, otherwise the reference's error text
-inline std::string discretize_eikonal(int type, const float *P, float doi, const CrustProfile &prof,
-                                      const std::vector<HalfSpace> &cons, DiscreteSource &out)
+inline std::string eikonal_prepare(int type, const float *P, float doi, const CrustProfile &prof,
+                                   const std::vector<HalfSpace> &cons, EikonalStage &st)
 {
     using namespace eik;
+    st.type = type; st.P = P; st.doi = doi; st.prof = &prof; st.cons = &cons;
     const bool mt = (type == 5);
+    st.mt = mt;
     const int o = mt ? 0 : 1;                                  // `eikonal` has slip-rake at position 8
     const float bsx = P[7 + o], bsy = P[8 + o], brad = P[9 + o], nux = P[10 + o], nuy = P[11 + o], relv = P[12 + o];
-    float Rrup[3][3], Rslip[3][3];
+    float (&Rrup)[3][3] = st.Rrup, (&Rslip)[3][3] = st.Rslip;
     init_euler(d2r(P[6]), d2r(P[5]), 0.f, Rrup);
     if (!mt) init_euler(d2r(P[6]), d2r(P[5]), -d2r(P[7]), Rslip);
-    const V3 shift = { P[1], P[2], P[3] };
+    st.shift = { P[1], P[2], P[3] };
+    const V3 &shift = st.shift;
     auto rc_to_ned = [&](const V3 &rc) { V3 p = mul(Rrup, rc); for (int k = 0; k < 3; k++) p[k] = p[k] + shift[k]; return p; };
     auto ned_to_rc = [&](const V3 &p) { return mulT(Rrup, V3{ p[0] - shift[0], p[1] - shift[1], p[2] - shift[2] }); };
     auto allowed = [&](const V3 &p) { for (auto &h : cons) if (!inside(p, h)) return false; return true; };
 
     // bounding circle as a 180-gon, clipped by every constraint (psm_borderline_*)
-    const V3 center = rc_to_ned({ bsx, bsy, 0.f });
+    st.center = rc_to_ned({ bsx, bsy, 0.f });
+    const V3 &center = st.center;
     float tr[3][3];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) tr[i][j] = -Rrup[i][j] * brad;
     const int ninit = (brad == 0.f) ? 1 : 180;
@@ -437,7 +481,8 @@ inline std::string discretize_eikonal(int type, const float *P, float doi, const
     if (cons.empty()) poly.clear();
     for (auto &h : cons) poly = clip(poly, h);
     if (poly.empty()) return "Empty rupture area";
-    float lo[2] = { std::numeric_limits<float>::max(), std::numeric_limits<float>::max() }, hi[2] = { -lo[0], -lo[1] };
+    float (&lo)[2] = st.lo, (&hi)[2] = st.hi;
+    lo[0] = std::numeric_limits<float>::max(); lo[1] = std::numeric_limits<float>::max(); hi[0] = -lo[0]; hi[1] = -lo[1];
     for (auto &p : poly) {
         const V3 rc = ned_to_rc(p);
         for (int k = 0; k < 2; k++) { lo[k] = std::min(lo[k], rc[k]); hi[k] = std::max(hi[k], rc[k]); }
@@ -445,21 +490,24 @@ inline std::string discretize_eikonal(int type, const float *P, float doi, const
 
     // fine grid of rupture speeds (psm_make_*_grid)
     const float dgrid = std::min(100.f * doi / 2.f, 4000.f);
-    const float ext[2] = { hi[0] - lo[0], hi[1] - lo[1] };
+    float (&ext)[2] = st.ext;
+    ext[0] = hi[0] - lo[0]; ext[1] = hi[1] - lo[1];
     int nf[2] = { (int)std::ceil(ext[0] / dgrid), (int)std::ceil(ext[1] / dgrid) };
     if (nf[0] == 0) nf[0] = 1;
     if (nf[1] == 0) nf[1] = 1;
-    const float fd[2] = { ext[0] / (float)nf[0], ext[1] / (float)nf[1] };
+    float (&fd)[2] = st.fd;
+    fd[0] = ext[0] / (float)nf[0]; fd[1] = ext[1] / (float)nf[1];
     {
         const float nukl = std::sqrt(nux * nux + nuy * nuy);
         if (!allowed(rc_to_ned({ nux, nuy, 0.f })) || nukl > brad)
             return "position of nucleation point is outside of rupture region";
     }
     const int fx = nf[0], fy = nf[1];
-    static thread_local std::vector<float> speed, ftimes;       // per-thread work arrays, see fast_marching
-    static thread_local std::vector<V3> fpt;
+    st.fx = fx; st.fy = fy;
+    std::vector<float> &speed = st.speed;                       // (the stage's arrays: per thread in discretize_eikonal, see fast_marching)
+    std::vector<V3> &fpt = st.fpt;
     const bool plain = fmm_mode() == 1;                         // KIWI_HIP_EIK_PLAIN=1: the scalar statements (tests compare the two)
-    FineGrid fg;
+    FineGrid &fg = st.fg;
     for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) fg.R[i][j] = Rrup[i][j]; fg.shift[i] = shift[i]; fg.center[i] = center[i]; }
     fg.brad = brad; fg.cons = cons.data(); fg.ncons = (int)cons.size();
     fg.lo[0] = lo[0]; fg.lo[1] = lo[1]; fg.fd[0] = fd[0]; fg.fd[1] = fd[1]; fg.fx = fx; fg.fy = fy;
@@ -482,8 +530,32 @@ inline std::string discretize_eikonal(int type, const float *P, float doi, const
     } else minspeed = speed_grid_simd(fg, prof, relv, speed);
     const float invalid = minspeed * 0.5f;
     for (auto &v : speed) if (v == 0.f) v = invalid;
-    const float start[2] = { nux, nuy };
-    fast_marching_cached(speed, fx, fy, lo, fd, start, ftimes, invalid);      // (exact: hit = same inputs, compared in full)
+    st.start[0] = nux; st.start[1] = nuy;
+    st.minspeed = minspeed; st.invalid = invalid; st.plain = plain;
+    return "";
+}
+
+// the solve of a prepared stage on the host (through the solve cache)
+inline void eikonal_solve(EikonalStage &st)
+{
+    eik::fast_marching_cached(st.speed, st.fx, st.fy, st.lo, st.fd, st.start, st.ftimes, st.invalid);      // (exact: hit = same inputs, compared in full)
+}
+
+// a prepared stage whose arrival times are in st.ftimes
+inline std::string eikonal_finish(EikonalStage &st, DiscreteSource &out)
+{
+    using namespace eik;
+    const bool mt = st.mt, plain = st.plain;
+    const float *P = st.P;
+    const float doi = st.doi;
+    const float (&Rrup)[3][3] = st.Rrup, (&Rslip)[3][3] = st.Rslip;
+    const V3 &shift = st.shift;
+    auto ned_to_rc = [&](const V3 &p) { return mulT(Rrup, V3{ p[0] - shift[0], p[1] - shift[1], p[2] - shift[2] }); };
+    const float (&lo)[2] = st.lo, (&hi)[2] = st.hi, (&ext)[2] = st.ext;
+    std::vector<float> &speed = st.speed, &ftimes = st.ftimes;
+    std::vector<V3> &fpt = st.fpt;
+    const FineGrid &fg = st.fg;
+    const float minspeed = st.minspeed, invalid = st.invalid;
     if (plain) for (size_t k = 0; k < speed.size(); k++) if (speed[k] == invalid) ftimes[k] = -1.f;
 
     // coarse grid (psm_to_tdsm_size_*, psm_downsample_grid)
@@ -573,6 +645,17 @@ inline std::string discretize_eikonal(int type, const float *P, float doi, const
     out.moment = P[4];
     out.risetime = mt ? P[19] : P[14];
     return "";
+}
+
+
+inline std::string discretize_eikonal(int type, const float *P, float doi, const CrustProfile &prof,
+                                      const std::vector<HalfSpace> &cons, DiscreteSource &out)
+{
+    static thread_local EikonalStage st;                        // per-thread work arrays, see fast_marching
+    const std::string err = eikonal_prepare(type, P, doi, prof, cons, st);
+    if (!err.empty()) return err;
+    eikonal_solve(st);
+    return eikonal_finish(st, out);
 }
 
 } // namespace kiwi

@@ -28,6 +28,7 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -361,11 +362,14 @@ struct Work { std::vector<float> T, S, hk; std::vector<int> BP, hi; };
 inline std::atomic<long long> &fmm_fallbacks() { static std::atomic<long long> n{ 0 }; return n; }
 inline int &fmm_mode() { static int mode = [] { const char *e = std::getenv("KIWI_HIP_EIK_PLAIN"); return e ? std::atoi(e) : 0; }(); return mode; }
 
+// the padded grid is indexed with int, by the march below and by the device march (kiwi_fmm_device.hpp)
+inline bool grid_fits_int(long long nx, long long ny) { return nx >= 1 && ny >= 1 && nx <= INT_MAX && ny <= INT_MAX && (nx + 2) * (ny + 2) <= (long long)INT_MAX; }
+
 inline void fast_marching(const float *speed, int nx, int ny, const float origin[2], const float delta[2],
                           const float start[2], std::vector<float> &times, float discard = std::numeric_limits<float>::quiet_NaN())
 {
     using namespace fm;
-    if (fmm_mode() == 1 || (long long)nx * ny > (1ll << 30)) { fast_marching_plain(speed, nx, ny, origin, delta, start, times, discard); return; }
+    if (fmm_mode() == 1 || (long long)nx * ny > (1ll << 30) || !grid_fits_int(nx, ny)) { fast_marching_plain(speed, nx, ny, origin, delta, start, times, discard); return; }
     const float dx = delta[0], dy = delta[1];
     if (nx == 1 && ny == 1) { times.assign(1, 0.f); return; }          // eikonal.f90:85
     static thread_local Work w;

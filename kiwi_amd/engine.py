@@ -90,6 +90,49 @@ def discretize_eikonal(sourcetype, params, effective_dt, rupture_profile, con_po
     return cent, mo.value, ri.value
 
 
+def fast_marching_grid_ok(nx, ny):
+    """Does the host's optimised march / the device march take an nx x ny grid (padded size within an int)?"""
+    return bool(_lib.load().kiwi_hip_fast_marching_grid_ok(int(nx), int(ny)))
+
+
+def fast_marching_batch(speeds, origins, deltas, starts, discards=None, engine=None):
+    """Independent fast-marching solves in one call (kiwi_hip_fast_marching_batch): speeds is a list of 2-D float32 arrays
+    [ny, nx] of possibly different shapes, origins / deltas / starts one (x, y) pair per solve, discards one speed per solve
+    (None, or NaN entries: none).  engine=None: the host's routine, no GPU needed; an Engine: its device.  Returns
+    (list of time arrays, number of solves handed on -- by the device to the host, or by the host's march to the plain one)."""
+    L = _lib.load()
+    n = len(speeds)
+    arrs = [np.ascontiguousarray(a, np.float32) for a in speeds]
+    for a in arrs:
+        if a.ndim != 2:
+            raise ValueError("every speed grid is a 2-D array [ny, nx]")
+    nx = np.array([a.shape[1] for a in arrs], np.int32)
+    ny = np.array([a.shape[0] for a in arrs], np.int32)
+    sizes = np.array([a.size for a in arrs], np.int64)
+    ofs = np.zeros(max(n, 1), np.int64)
+    ofs[1:n] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    packed = np.concatenate([a.ravel() for a in arrs]) if n and total else np.zeros(1, np.float32)
+    times = np.zeros(max(total, 1), np.float32)
+    org = np.ascontiguousarray(origins, np.float32).reshape(-1, 2)
+    dlt = np.ascontiguousarray(deltas, np.float32).reshape(-1, 2)
+    sta = np.ascontiguousarray(starts, np.float32).reshape(-1, 2)
+    dis = np.full(n, np.nan, np.float32) if discards is None else np.ascontiguousarray(discards, np.float32).reshape(-1)
+    if not (len(org) == len(dlt) == len(sta) == len(dis) == n):
+        raise ValueError("origins, deltas, starts and discards need one entry per solve")
+    fb = C.c_longlong(0)
+    h = engine.h if engine is not None else None
+    rc = L.kiwi_hip_fast_marching_batch(h, 1 if engine is not None else 0, n, _ip(nx), _ip(ny),
+                                        ofs.ctypes.data_as(C.POINTER(C.c_longlong)), _fp(packed), _fp(org), _fp(dlt), _fp(sta),
+                                        _fp(dis), _fp(times), C.byref(fb))
+    if rc != 0:
+        buf = C.create_string_buffer(1024)
+        L.kiwi_hip_last_error(h, buf, 1024)
+        raise KiwiHipError("fast_marching_batch: nok > %s" % buf.value.decode())
+    out = [times[int(ofs[k]):int(ofs[k]) + int(sizes[k])].reshape(arrs[k].shape).copy() for k in range(n)]
+    return out, fb.value
+
+
 def _pieces(n, piece, st):
     """The pieces [first, first + count) kiwi_hip_misfits_for_params cuts a list of n sources into (list order; it works
     from the last to the first): `piece` sources each, and for the eikonal types the last one as a ramp of half, a quarter,
@@ -104,10 +147,11 @@ def _pieces(n, piece, st):
 
 
 class Engine:
-    def __init__(self, device=0, ndev=None):
+    def __init__(self, device=0, ndev=None, eikonal_solver=None):
         """device: the GPU of a one-device engine; ndev: instead, ONE engine over that many devices of this process
         (kiwi_hip_init_multi; 0 = all visible): setters are repeated on every device, misfits_for_params /
-        make_misfits_for_sources shard their trial list over them."""
+        make_misfits_for_sources shard their trial list over them.  eikonal_solver: 'host' or 'device' (set_eikonal_solver);
+        None leaves the library's choice (host, or KIWI_HIP_EIK_DEVICE)."""
         self.L = _lib.load()
         self.h = C.c_void_p()
         rc = self.L.kiwi_hip_init(device, C.byref(self.h)) if ndev is None else self.L.kiwi_hip_init_multi(ndev, C.byref(self.h))
@@ -117,6 +161,34 @@ class Engine:
             self.h = None
             raise KiwiHipError("kiwi_hip_init: " + buf.value.decode())
         self.nsrc = 0
+        if eikonal_solver is not None:
+            self.set_eikonal_solver(eikonal_solver)
+
+    def set_eikonal_solver(self, where):
+        """Where the eikonal discretisers run their fast-marching solves: 'host' (default) or 'device' -- the solves of a
+        batch that the solve cache does not answer go to the GPU as one launch, one solve per wavefront; same results."""
+        w = {"host": 0, "device": 1, 0: 0, 1: 1}.get(where)
+        if w is None:
+            raise ValueError("eikonal_solver: 'host' or 'device'")
+        self._ck(self.L.kiwi_hip_set_eikonal_solver(self.h, w), "set_eikonal_solver")
+
+    @property
+    def eikonal_solver(self):
+        w = C.c_int(0)
+        self._ck(self.L.kiwi_hip_get_eikonal_solver(self.h, C.byref(w)), "get_eikonal_solver")
+        return "device" if w.value == 1 else "host"
+
+    def eikonal_solver_ms(self):
+        """(upload, kernel, download) milliseconds of this context's last device batch of fast-marching solves (HIP events)."""
+        u, k, d = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._ck(self.L.kiwi_hip_get_eikonal_solver_ms(self.h, C.byref(u), C.byref(k), C.byref(d)), "get_eikonal_solver_ms")
+        return u.value, k.value, d.value
+
+    def eikonal_solver_stats(self):
+        """(kernel launches, largest heap of any solve) of the same batch; the device heap holds 4096 entries."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._ck(self.L.kiwi_hip_get_eikonal_solver_stats(self.h, C.byref(a), C.byref(b)), "get_eikonal_solver_stats")
+        return a.value, b.value
 
     def ndevices(self):
         n = C.c_int(0)

@@ -345,6 +345,52 @@ module kiwi_hip_binding
             integer(c_long_long), intent(out) :: fallbacks
         end function
 
+      ! nsolve solves in one call: where = 0 the host's routine (ctx may be c_null_ptr), 1 the device of ctx
+        integer(c_int) function kiwi_hip_fast_marching_batch( ctx, where, nsolve, nx, ny, ofs, speed, origin, delta, start, &
+                                                              discard, times, fallbacks ) &
+                                                              bind(C, name='kiwi_hip_fast_marching_batch')
+            import :: c_int, c_ptr, c_float, c_long_long
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: where, nsolve
+            integer(c_int), intent(in) :: nx(*), ny(*)
+            integer(c_long_long), intent(in) :: ofs(*)            ! 0-based offsets of the solves in speed and times
+            real(c_float), intent(in) :: speed(*), origin(2,*), delta(2,*), start(2,*), discard(*)
+            real(c_float), intent(out) :: times(*)
+            integer(c_long_long), intent(out) :: fallbacks
+        end function
+
+      ! where the eikonal discretisers solve: 0 host (default), 1 device (env KIWI_HIP_EIK_DEVICE at kiwi_hip_init)
+        integer(c_int) function kiwi_hip_set_eikonal_solver( ctx, where ) bind(C, name='kiwi_hip_set_eikonal_solver')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: where
+        end function
+
+        integer(c_int) function kiwi_hip_get_eikonal_solver( ctx, where ) bind(C, name='kiwi_hip_get_eikonal_solver')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: where
+        end function
+
+        integer(c_int) function kiwi_hip_get_eikonal_solver_ms( ctx, upload, kernel, download ) &
+                                                                bind(C, name='kiwi_hip_get_eikonal_solver_ms')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            real(c_double), intent(out) :: upload, kernel, download
+        end function
+
+        integer(c_int) function kiwi_hip_get_eikonal_solver_stats( ctx, launches, heap_high_water ) &
+                                                                   bind(C, name='kiwi_hip_get_eikonal_solver_stats')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: launches, heap_high_water
+        end function
+
+        integer(c_int) function kiwi_hip_fast_marching_grid_ok( nx, ny ) bind(C, name='kiwi_hip_fast_marching_grid_ok')
+            import :: c_int, c_long_long
+            integer(c_long_long), value :: nx, ny
+        end function
+
         integer(c_int) function kiwi_hip_eval( ctx, isrc0, nsrc ) bind(C, name='kiwi_hip_eval')
             import :: c_int, c_ptr
             type(c_ptr), value :: ctx

@@ -108,6 +108,13 @@ def load():
         "kiwi_hip_eikonal_cache_stats": [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_int],
         "kiwi_hip_fast_marching": [c_float_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, C.c_float, C.c_int, c_float_p,
                                    C.POINTER(C.c_longlong)],
+        "kiwi_hip_fast_marching_batch": [vp, C.c_int, C.c_int, c_int_p, c_int_p, C.POINTER(C.c_longlong), c_float_p, c_float_p,
+                                         c_float_p, c_float_p, c_float_p, c_float_p, C.POINTER(C.c_longlong)],
+        "kiwi_hip_set_eikonal_solver": [vp, C.c_int],
+        "kiwi_hip_get_eikonal_solver": [vp, c_int_p],
+        "kiwi_hip_get_eikonal_solver_ms": [vp, c_double_p, c_double_p, c_double_p],
+        "kiwi_hip_get_eikonal_solver_stats": [vp, c_int_p, c_int_p],
+        "kiwi_hip_fast_marching_grid_ok": [C.c_longlong, C.c_longlong],
         "kiwi_hip_eval": [vp, C.c_int, C.c_int],
         "kiwi_hip_sync": [vp],
         "kiwi_hip_set_keep_synthetics": [vp, C.c_int],
