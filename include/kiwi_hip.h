@@ -357,6 +357,43 @@ int kiwi_hip_outer_misfits(kiwi_hip_ctx *ctx, int nsrc, int nmis, int nrec, cons
 int kiwi_hip_outer_max_receivers(void);
 /* HIP-event durations [ms] of the last kiwi_hip_outer_misfits: ms[0] uploads, ms[1] kernels, ms[2] downloads */
 int kiwi_hip_get_outer_ms(kiwi_hip_ctx *ctx, float ms[3]);
+/* Least-squares coefficients of K basis sources per group under the time-domain l2norm, on the device (kiwi_amd/csrc/kiwi_linfit.hpp).
+ * Sources [isrc0, isrc0 + ngroup K) of the uploaded batch are ngroup groups of K consecutive basis sources, 1 <= K <=
+ * kiwi_hip_linear_fit_max_basis().  With s_i = what the l2norm comparator compares of basis source i (syn_factor x the moment-
+ * scaled, rise-time-folded, tapered synthetic; the frequency-filtered trace where the receiver has a misfit filter) and d the
+ * reference side of the same comparison, per (group, enabled receiver r), summed over the receiver's slots, in fp64:
+ *     G_r[i][j] = dt sum_t s_i[t] s_j[t] (i <= j)     b_r[i] = dt sum_t s_i[t] d[t]     R_r = dt sum_t d[t]^2
+ * NN = K (K + 1) / 2 + K + 1 numbers laid out as: G upper triangle by rows, b, R.  The receivers are folded with w_r =
+ * receiver_weight[r] (NULL: ones; 0 excludes; disabled receivers never count), divided by sqrt(R_r) if anarchy != 0 (a receiver
+ * with R_r = 0 then has weight 0): G = sum w_r^2 G_r, likewise b and R.  G is scaled to unit diagonal and solved by Cholesky:
+ *   coef       [ngroup][K]  the minimiser x of | d - sum_i x_i s_i |
+ *   misfit     [ngroup]     sqrt(max(R - 2 x.b + x.G.x, 0) / R): the global misfit (l2norm inner and outer norm) of sum_i x_i s_i
+ *   status     [ngroup]     0 solved; 1 no solution: a diagonal element that is not positive, a pivot <= K 2^-52, or R not positive;
+ *                           2 a basis source of the group failed to discretise (kiwi_hip_get_source_status)
+ *   pivot_min  [ngroup] or NULL: the smallest Cholesky pivot of the scaled matrix reached (1 for an orthogonal basis, towards 0
+ *                           for a dependent one; rank deficiency shows as a pivot of round-off size, which the breakdown test
+ *                           need not catch: judge by this number)
+ *   normal     [ngroup][NN] or NULL: the weighted sums G, b, R (unscaled)
+ *   normal_by_receiver [ngroup][nrec][NN] or NULL: G_r, b_r, R_r, unweighted; zeros for disabled receivers
+ * Groups with status != 0 answer NaN coefficients and misfit; their sums (and, for status 1, the pivot reached) are still returned.
+ * Every sum has a fixed order (no atomics; tests/linfit_restatement.py restates it): the answer does not depend on K's
+ * neighbours, on chunking (KIWI_HIP_CHUNK_MB), on isrc0 or on how a list is cut into pieces.  The evaluation is kiwi_hip_eval's:
+ * misfits, norm factors and global misfits of the basis sources are left as an evaluation with kept synthetics leaves them.
+ * Refused (non-zero, kiwi_hip_last_error names the reason): a misfit method other than l2norm, floating shift ranges, an enabled
+ * receiver without a misfit taper or without references, K out of range, a range that is not inside the batch. */
+int kiwi_hip_linear_fit(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, double *coef,
+                        double *misfit, int *status, double *pivot_min, double *normal, double *normal_by_receiver);
+/* The same for a parameter list params[ngroup * K][nparams] of any length: discretised and uploaded piece by piece as
+ * kiwi_hip_misfits_for_params does (piece: sources per piece, rounded down to a multiple of K; <= 0: that call's default); a
+ * context over several devices cuts the GROUP list into one contiguous range per device.  Afterwards the context holds the head
+ * of the list. */
+int kiwi_hip_linear_fit_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                               const double *receiver_weight, int anarchy, double *coef, double *misfit, int *status,
+                               double *pivot_min, double *normal, double *normal_by_receiver);
+/* the most basis sources per group (the accumulators of a thread are registers); answers without a device */
+int kiwi_hip_linear_fit_max_basis(void);
+/* HIP-event durations [ms] of the last linear fit on this context: ms[0] evaluation, ms[1] fit kernels, ms[2] downloads */
+int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *ctx, float ms[3]);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each
  * (layout in kiwi_amd/csrc/kiwi_kernels.hpp); for parity tests */
 int kiwi_hip_get_geometry(kiwi_hip_ctx *ctx, int isrc, int irec, int maxcent, int *ncent, void *records);

@@ -234,6 +234,7 @@ struct kiwi_hip_ctx {
     int proc_chunk0 = 0, proc_chunkn = 0, proc_which_held = 0;   // what proc_d currently holds
     size_t chunk_bytes_limit = (size_t)16 << 30;      // workspace per launch; the device has 288 GB
     float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
+    float linfit_ms[3] = { 0.f, 0.f, 0.f };           // evaluation, fit kernels, download of the last kiwi_hip_linear_fit (kiwi_linfit.hpp)
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
 
@@ -1424,6 +1425,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 
 #include "kiwi_gfk.hpp"
 #include "kiwi_outer.hpp"
+#include "kiwi_linfit.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2764,38 +2766,49 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
 // list is cut into pieces; while the device evaluates one piece, a second host thread discretises the next.  Per piece
 // the calls are exactly kiwi_hip_set_sources_params + kiwi_hip_eval + kiwi_hip_get_misfits + kiwi_hip_get_source_status,
 // so results do not depend on `piece` (a source's evaluation does not depend on its batch: tests).
-int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
-                                float *misfit, float *norm, float *global, int *status)
+// (kiwi_hip_linear_fit_params goes through the same pieces with `fit` set: the list is then groups of fit->K consecutive basis
+// sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
+struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; };
+
+static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
+                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
     if (np < 0) throw std::runtime_error("source type not supported by the host discretiser");
     if (nsrc < 1) throw std::runtime_error("need at least one source");
     HIPCHECK(hipSetDevice(c->device));
+    if (fit) linfit::check_setup(c, fit->K, fit->out);
+    const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
+    const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
                                                 "(the device comparator evaluates norms over the taper span, comparator.f90:782-792)");
     const size_t nmis = (size_t)c->nmis;
-    if (!c->mates.empty() && nsrc >= 2) {
+    if (!c->mates.empty() && nsrc / unit >= 2) {
         // ---- multi-device context: contiguous shards in list order (Source.grid order), shard 0 here -- this context keeps the
         // HEAD of the list as in the one-device case --, the others each in a thread of their own on their device
-        const int ndev = std::min(nsrc, 1 + (int)c->mates.size());
+        const int ndev = std::min(nsrc / unit, 1 + (int)c->mates.size());
         // (futures: their destructors join -- a std::thread that is still joinable when an exception unwinds this frame, e.g.
         // from the next emplace_back, would end the process in std::terminate)
         std::vector<std::future<int>> th;
         std::vector<int> rc((size_t)ndev, 0);
-        auto bound = [&](int i) { return (int)((long long)nsrc * i / ndev); };
+        auto bound = [&](int i) { return unit * (int)((long long)(nsrc / unit) * i / ndev); };
+        auto sub_fit = [&](int s0) { LinFitCall f = *fit; f.out = fit->out.at(s0 / unit, unit, nrec_all); return f; };
         for (int i = 1; i < ndev; i++) {
             kiwi_hip_ctx *m = c->mates[(size_t)i - 1];
             const int s0 = bound(i), n = bound(i + 1) - s0;
+            const bool fitting = fit != nullptr;
+            const LinFitCall mine = fitting ? sub_fit(s0) : LinFitCall{};
             th.push_back(std::async(std::launch::async, [=] {
-                return kiwi_hip_misfits_for_params(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
-                                                   norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr);
+                return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
+                                       norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
+                                       fitting ? &mine : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = kiwi_hip_misfits_for_params(c, sourcetype, bound(1), params, piece, misfit, norm, global, status);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -2809,16 +2822,17 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
     // (default piece: 128 eikonal solves keep the discretiser team busy for one device evaluation; for the closed-form source types the
     // host is a few per cent of a piece and larger launches fill the device better -- cfg3, 4096 trials: 31.1 k evals/s at 1024, 32.5 k at 2048)
     if (piece <= 0) piece = source_nparams_eikonal(sourcetype) > 0 ? 128 : 2048;
+    if (unit > 1) piece = std::max(unit, piece - piece % unit);
     // pieces [first, first + count) in list order.  Eikonal types: the LAST piece of the list -- the first one worked on, the one
     // whose discretisation nothing hides -- is cut into a ramp of an eighth, an eighth, a quarter and half a piece, so that the
     // device starts after an eighth of a piece's fast-marching solves (one per discretiser thread at the default 128 on 16 CPUs)
     // instead of a whole one (512 cfg4-nukl trials: 137 ms of the call's 1066 were that wait).
     std::vector<std::pair<int, int>> pieces;
     for (int s0 = 0; s0 < nsrc; s0 += piece) pieces.emplace_back(s0, std::min(piece, nsrc - s0));
-    if (source_nparams_eikonal(sourcetype) > 0 && pieces.size() >= 2 && pieces.back().second >= 8) {
+    if (source_nparams_eikonal(sourcetype) > 0 && pieces.size() >= 2 && pieces.back().second / unit >= 8) {
         const std::pair<int, int> last = pieces.back();
         pieces.pop_back();
-        const int e = last.second / 8, q = last.second / 4, h = last.second - 2 * e - q;
+        const int e = last.second / unit / 8 * unit, q = last.second / unit / 4 * unit, h = last.second - 2 * e - q;
         pieces.emplace_back(last.first, h);
         pieces.emplace_back(last.first + h, q);
         pieces.emplace_back(last.first + h + q, e);
@@ -2920,11 +2934,13 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
             if (misfit) std::memset(misfit + (size_t)s0 * nmis, 0, (size_t)n * nmis * sizeof(float));
             if (norm) std::memset(norm + (size_t)s0 * nmis, 0, (size_t)n * nmis * sizeof(float));
             if (global) std::memset(global + s0, 0, (size_t)n * sizeof(float));
+            if (fit) linfit::fill_failed(n / unit, unit, nrec_all, fit->out.at(s0 / unit, unit, nrec_all));
             continue;
         }
         upload_batch(c, hb);
         const double t_up = now();
-        eval_impl(c, 0, n, c->keep_which);
+        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all));
+        else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
         if (trace) {
@@ -2936,6 +2952,48 @@ int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const
     }
     return 0;
     GUARD_END(c)
+}
+
+int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
+                                float *misfit, float *norm, float *global, int *status)
+{
+    return for_params_impl(c, sourcetype, nsrc, params, piece, misfit, norm, global, status, nullptr);
+}
+
+// Least-squares coefficients of K basis sources per group under l2norm (kiwi_linfit.hpp), for groups of the uploaded batch ...
+int kiwi_hip_linear_fit(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, double *coef,
+                        double *misfit, int *status, double *pivot_min, double *normal, double *normal_by_receiver)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = 0.f;
+    linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver });
+    return 0;
+    GUARD_END(c)
+}
+
+// ... and for a parameter list of any length, discretised and uploaded piece by piece like kiwi_hip_misfits_for_params
+int kiwi_hip_linear_fit_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                               const double *receiver_weight, int anarchy, double *coef, double *misfit, int *status, double *pivot_min,
+                               double *normal, double *normal_by_receiver)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = 0.f;
+    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+}
+
+int kiwi_hip_linear_fit_max_basis(void) { return linfit::kMaxBasis; }
+
+int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *c, float ms[3])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 3; i++) ms[i] = c->linfit_ms[i];
+    return 0;
 }
 
 int kiwi_hip_get_synthetics(kiwi_hip_ctx *c, int isrc, int irec, int icomp, int which, int *first, int *n,

@@ -1,0 +1,384 @@
+// kiwi_linfit.hpp -- least-squares coefficients of K basis sources per group under the time-domain l2norm: the inner products
+// between SYNTHETICS (the comparator only ever pairs a synthetic with a reference), the normal equations of every group and
+// their solution.  For `moment_tensor` and `mt_eikonal` the six tensor components enter the centroid table, and so the
+// synthetics, linearly (kiwi_host.hpp discretize_moment_tensor, kiwi_host_eikonal.hpp): with six unit tensors as basis the
+// coefficients ARE the best moment tensor of a trial location (kiwi_amd/mtfit.py).  Included by kiwi_hip.hip after the
+// evaluation, so it is compiled with that object's -ffp-contract=off: every fp64 product, sum, quotient and root below is
+// rounded on its own, and tests/linfit_restatement.py restates each step in the same order (the GPU tests ask for bit identity).
+//
+// Sources [isrc0, isrc0 + ngroup K) of the uploaded batch are ngroup groups of K consecutive basis sources.  Per chunk of whole
+// groups (bounded like an evaluation's chunks, KIWI_HIP_CHUNK_MB):
+//   evaluate  run_chunk with the processed synthetics kept (tapered; filtered where a receiver has a misfit filter): misfits,
+//             norm factors and global misfits of the basis sources are left exactly as kiwi_hip_eval leaves them
+//   gram      one workgroup of 256 threads per (group, receiver).  With s_i[t] = syn_factor x kept trace of basis source i (the
+//             fp32 product the comparator forms) and d[t] the reference side of the same comparison, every thread keeps
+//             NN = K (K + 1) / 2 + K + 1 fp64 accumulators, in this order: G[i][j] (i <= j, upper triangle by rows), b[i], R:
+//                 G[i][j] += s_i[t] s_j[t]      b[i] += s_i[t] d[t]      R += d[t] d[t]
+//             (a product of two fp32 values is exact in fp64; only the order of the additions matters).  A thread takes the
+//             samples t = tid, tid + 256, ... of the receiver's first slot in ascending order, then those of the next slot, and
+//             so on, into the SAME accumulators.  Tree: within a wavefront v[lane] = v[lane] + v[lane + off] for off = 32, 16,
+//             8, 4, 2, 1; then (w0 + w1) + (w2 + w3) over the four wavefronts; the total times (double) dt.  The K traces of a
+//             sample are read once and feed all pairs from registers: each sample of each kept trace is read from memory once.
+//             The order is the same for every K, chunk size, isrc0 and group position.  No atomics.
+//   solve     one thread per group.  Receivers r ascending: w = receiver_weight[r] (0 for a disabled receiver); a receiver with
+//             w == 0 is skipped; anarchy: w = R_r > 0 ? w / sqrt(R_r) : 0; N[p] = N[p] + (w w) N_r[p].  D_i = G_ii; scaling
+//             s_i = 1 / sqrt(D_i); A_ij = (G_ij s_i) s_j, A_ii = 1.  Cholesky A = L L^T by columns j ascending:
+//                 d = 1; d = d - L_jk L_jk (k < j ascending); pivot d; L_jj = sqrt(d);
+//                 v = A_ij; v = v - L_ik L_jk (k < j ascending); L_ij = v / L_jj   (i > j)
+//             y_i = (b_i s_i - sum_{k < i} L_ik y_k) / L_ii; z_i = (y_i - sum_{k > i} L_ki z_k) / L_ii (i descending, k
+//             ascending); coef_i = z_i s_i.  misfit = sqrt(max((R - 2 x.b) + x.G.x, 0) / R) with x.b and the rows of G x summed
+//             from zero in ascending index order and x.G.x = sum_i x_i (G x)_i.  pivot_min: the smallest pivot up to and
+//             including the one that broke down; 0 for a diagonal that is not positive.
+// Status of a group: 0 solved; 1 no solution (a diagonal element not positive, a pivot <= K 2^-52, or R not positive); 2 a
+// basis source of the group failed to discretise (set on the host).  Groups with status != 0 answer NaN coefficients and misfit.
+
+namespace linfit {
+
+constexpr int kMaxBasis = 8;
+constexpr int kThreads = 256;
+
+__host__ __device__ constexpr int nn_of(int K) { return K * (K + 1) / 2 + K + 1; }
+__host__ __device__ constexpr int tri(int K, int i, int j) { return i * K - i * (i - 1) / 2 + (j - i); }     // i <= j
+
+// nbr: [group of the chunk][receiver][NN]; blockIdx.x = receiver (all of them: a disabled one is left at the zeros of the
+// memset before the launch), blockIdx.y = group.  pairs: the chunk's (source, slot) records where transforms ran, else null
+template <int K>
+__global__ __launch_bounds__(kThreads) void linfit_gram_kernel(const float *__restrict__ proc, size_t syn_stride,
+                                                               const RecvDev *__restrict__ recv, const CompDev *__restrict__ comps,
+                                                               const float *__restrict__ reft, const float *__restrict__ reffilt,
+                                                               const FftPair *__restrict__ pairs, int nmis, int nrec, float syn_factor,
+                                                               float dt, double *__restrict__ nbr)
+{
+    constexpr int NG = K * (K + 1) / 2, NN = NG + K + 1;
+    __shared__ double part[kThreads / 64][NN];
+    const int r = (int)blockIdx.x, g = (int)blockIdx.y, tid = (int)threadIdx.x;
+    const RecvDev rd = recv[r];
+    if (!rd.enabled) return;
+    const bool unit = (syn_factor == 1.f);
+    const float *__restrict__ src0 = proc + (size_t)g * K * syn_stride;
+    double acc[NN];
+#pragma unroll
+    for (int p = 0; p < NN; p++) acc[p] = 0.0;
+    for (int k = 0; k < rd.ncomp; k++) {
+        const int slot = rd.slot0 + k;
+        const CompDev cd = comps[slot];
+        const float *__restrict__ sy = src0 + cd.synofs + cd.halo;
+        const float *__restrict__ dp = (cd.has_filter && pairs) ? reffilt + pairs[(size_t)g * K * nmis + slot].filtofs : reft + cd.refofs;
+        for (int i = tid; i < cd.wlen; i += kThreads) {
+            double s[K];
+#pragma unroll
+            for (int a = 0; a < K; a++) {
+                const float v = sy[(size_t)a * syn_stride + i];
+                s[a] = (double)(unit ? v : syn_factor * v);
+            }
+            const double dv = (double)dp[i];
+            int p = 0;
+#pragma unroll
+            for (int a = 0; a < K; a++)
+#pragma unroll
+                for (int b = a; b < K; b++, p++) acc[p] = acc[p] + s[a] * s[b];
+#pragma unroll
+            for (int a = 0; a < K; a++) acc[NG + a] = acc[NG + a] + s[a] * dv;
+            acc[NN - 1] = acc[NN - 1] + dv * dv;
+        }
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int p = 0; p < NN; p++) {
+        double v = acc[p];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+        if (lane == 0) part[wave][p] = v;
+    }
+    __syncthreads();
+    if (tid < NN) {
+        const double t = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+        nbr[((size_t)g * nrec + r) * NN + tid] = (double)dt * t;
+    }
+}
+
+// w: [nrec] receiver weights with zeros for disabled receivers.  normal: [ng][NN] or null
+template <int K>
+__global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restrict__ nbr, const double *__restrict__ w, int nrec,
+                                                          int anarchy, int ng, double *__restrict__ coef, double *__restrict__ misfit,
+                                                          int *__restrict__ status, double *__restrict__ pivot_min,
+                                                          double *__restrict__ normal)
+{
+    constexpr int NG = K * (K + 1) / 2, NN = NG + K + 1;
+    const int g = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (g >= ng) return;
+    double N[NN];
+#pragma unroll
+    for (int p = 0; p < NN; p++) N[p] = 0.0;
+    for (int r = 0; r < nrec; r++) {
+        double wr = w[r];
+        if (wr == 0.0) continue;
+        const double *__restrict__ q = nbr + ((size_t)g * nrec + r) * NN;
+        if (anarchy) {
+            const double Rr = q[NN - 1];
+            wr = Rr > 0.0 ? wr / sqrt(Rr) : 0.0;
+            if (wr == 0.0) continue;
+        }
+        const double w2 = wr * wr;
+#pragma unroll
+        for (int p = 0; p < NN; p++) N[p] = N[p] + w2 * q[p];
+    }
+    if (normal)
+#pragma unroll
+        for (int p = 0; p < NN; p++) normal[(size_t)g * NN + p] = N[p];
+    const double R = N[NN - 1];
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    int st = 0;
+    double pmin = 0.0;
+    double x[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) x[i] = nan;
+    bool diag_ok = true;
+#pragma unroll
+    for (int i = 0; i < K; i++) if (!(N[tri(K, i, i)] > 0.0)) diag_ok = false;
+    if (!diag_ok) {
+        st = 1;
+    } else {
+        double s[K], L[K][K];
+#pragma unroll
+        for (int i = 0; i < K; i++) s[i] = 1.0 / sqrt(N[tri(K, i, i)]);
+        const double tol = (double)K * 2.220446049250313e-16;       // K 2^-52
+        bool ok = true;
+        pmin = 1.0;
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            double d = 1.0;
+#pragma unroll
+            for (int k = 0; k < j; k++) d = d - L[j][k] * L[j][k];
+            if (ok) {
+                if (d < pmin) pmin = d;
+                if (!(d > tol)) ok = false;
+            }
+            const double ljj = sqrt(d);
+            L[j][j] = ljj;
+#pragma unroll
+            for (int i = j + 1; i < K; i++) {
+                double v = (N[tri(K, j, i)] * s[i]) * s[j];
+#pragma unroll
+                for (int k = 0; k < j; k++) v = v - L[i][k] * L[j][k];
+                L[i][j] = v / ljj;
+            }
+        }
+        if (!ok) {
+            st = 1;
+        } else {
+            double y[K];
+#pragma unroll
+            for (int i = 0; i < K; i++) {
+                double v = N[NG + i] * s[i];
+#pragma unroll
+                for (int k = 0; k < i; k++) v = v - L[i][k] * y[k];
+                y[i] = v / L[i][i];
+            }
+#pragma unroll
+            for (int i = K - 1; i >= 0; i--) {
+                double v = y[i];
+#pragma unroll
+                for (int k = i + 1; k < K; k++) v = v - L[k][i] * y[k];
+                y[i] = v / L[i][i];                                   // (y becomes z in place: z_k, k > i, are final)
+            }
+#pragma unroll
+            for (int i = 0; i < K; i++) x[i] = y[i] * s[i];
+        }
+    }
+    if (!(R > 0.0)) st = 1;
+    double mf = nan;
+    if (st == 0) {
+        double xb = 0.0, xgx = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; i++) xb = xb + x[i] * N[NG + i];
+#pragma unroll
+        for (int i = 0; i < K; i++) {
+            double row = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; j++) row = row + N[i <= j ? tri(K, i, j) : tri(K, j, i)] * x[j];
+            xgx = xgx + x[i] * row;
+        }
+        double val = (R - 2.0 * xb) + xgx;
+        val = val > 0.0 ? val : 0.0;
+        mf = sqrt(val / R);
+    }
+#pragma unroll
+    for (int i = 0; i < K; i++) coef[(size_t)g * K + i] = st == 0 ? x[i] : nan;
+    misfit[g] = mf;
+    status[g] = st;
+    pivot_min[g] = pmin;
+}
+
+template <int K>
+static void launch(kiwi_hip_ctx *c, int ng, const FftPair *pairs, const double *w_d, int anarchy, double *nbr, double *coef,
+                   double *misfit, int *status, double *pivot, double *normal)
+{
+    const int nrec = (int)c->recv.size();
+    hipLaunchKernelGGL(linfit_gram_kernel<K>, dim3((unsigned)nrec, (unsigned)ng), dim3(kThreads), 0, c->stream, c->proc_d.p, c->syn_stride,
+                       c->recv_d.p, c->comps_d.p, c->reft_d.p, c->reffilt_d.p, pairs, c->nmis, nrec, c->syn_factor, c->gm.dt, nbr);
+    HIPCHECK(hipGetLastError());
+    hipLaunchKernelGGL(linfit_solve_kernel<K>, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, c->stream, nbr, w_d, nrec, anarchy, ng, coef,
+                       misfit, status, pivot, normal);
+    HIPCHECK(hipGetLastError());
+}
+
+static void launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, double *nbr, double *coef,
+                       double *misfit, int *status, double *pivot, double *normal)
+{
+    switch (K) {
+    case 1: launch<1>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 2: launch<2>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 3: launch<3>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 4: launch<4>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 5: launch<5>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 6: launch<6>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    case 7: launch<7>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    default: launch<8>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
+    }
+}
+
+// host arrays of the caller, each for the groups of ONE call of run(); any of pivot_min, normal, by_receiver may be null
+struct Out {
+    double *coef, *misfit;
+    int *status;
+    double *pivot_min, *normal, *by_receiver;
+    Out at(int g, int K, int nrec) const
+    {
+        const size_t nn = (size_t)nn_of(K);
+        return Out{ coef + (size_t)g * K, misfit + g, status + g, pivot_min ? pivot_min + g : nullptr,
+                    normal ? normal + (size_t)g * nn : nullptr, by_receiver ? by_receiver + (size_t)g * nrec * nn : nullptr };
+    }
+};
+
+// what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.
+static void check_setup(kiwi_hip_ctx *c, int K, const Out &out)
+{
+    if (K < 1 || K > kMaxBasis)
+        throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(kMaxBasis) + " are supported");
+    if (!out.coef || !out.misfit || !out.status) throw std::runtime_error("linear_fit: null coef, misfit or status array");
+    if (c->method == KIWI_FLOATING_L2NORM || c->method == KIWI_FLOATING_L1NORM)
+        throw std::runtime_error("linear_fit: floating shift ranges make the misfit a minimum over shifts, which is not quadratic in the coefficients; set l2norm");
+    if (c->method != KIWI_L2NORM)
+        throw std::runtime_error("linear_fit: the misfit method must be l2norm (the only inner norm that is quadratic in the coefficients)");
+    prepare(c);
+    if (c->synth_only) throw std::runtime_error("linear_fit: every enabled receiver component needs a reference seismogram");
+    if (c->any_untapered)
+        throw std::runtime_error("linear_fit: an enabled receiver has no misfit taper (its comparison span follows the source, so the basis traces have no common span)");
+}
+
+// the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->linfit_ms
+static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Out &out)
+{
+    check_setup(c, K, out);
+    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
+        throw std::runtime_error("linear_fit: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
+                                 " are not inside the uploaded batch of " + std::to_string(c->nsrc));
+    if (ngroup == 0) return;
+    const int nrec = (int)c->recv.size(), NN = nn_of(K);
+    // With a misfit filter the kept traces come from the library transforms; the filtered references are made by the transform
+    // their trial sources go through (make_variants), so for the duration of the call that is the library's for every length --
+    // the way kiwi_hip_get_amp_spectrum forces it --, and the reference variants are made afresh before and after.
+    struct Restore {
+        kiwi_hip_ctx *c; bool fused, touched;
+        static void drop_variants(kiwi_hip_ctx *c) { c->variants.clear(); c->refamp_h.clear(); c->filtw_h.clear(); c->reffilt_h.clear(); }
+        ~Restore() { if (touched) { c->fused_fft = fused; drop_variants(c); } }
+    } restore{ c, c->fused_fft, false };
+    if (c->fft_needed && c->fused_fft) { c->fused_fft = false; Restore::drop_variants(c); restore.touched = true; }
+    c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
+    c->global_d.ensure((size_t)c->nsrc, &c->dev_bytes);
+    if (c->fft_needed && !c->fft_ready) prepare_fft(c, c->reft_h);
+    const int proc_which = c->any_filter ? 3 : 2;
+    c->fuse_now = can_fuse(c, proc_which, isrc0, ngroup * K);
+    if (c->fft_needed && c->fft_cap < K) throw std::runtime_error("linear_fit: the transform workspace (KIWI_HIP_CHUNK_MB) does not hold one group");
+
+    std::vector<double> w((size_t)nrec, 0.0);
+    for (int r = 0; r < nrec; r++)
+        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d;
+    DevBuf<int> st_d;
+    w_d.alloc((size_t)nrec, &c->dev_bytes);
+    HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; i++) ev[i] = c->get_event();
+    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 4; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    std::vector<double> piv_h;
+    int g0 = 0;
+    while (g0 < ngroup) {
+        // whole groups, bounded by workspace bytes the way eval_impl bounds its chunks
+        size_t bytes = 0;
+        int ng = 0;
+        while (g0 + ng < ngroup) {
+            size_t add = 0;
+            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
+                const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
+                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float) * 2;
+            }
+            add += (size_t)nrec * NN * sizeof(double);
+            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
+            if (c->fft_needed && (ng + 1) * K > c->fft_cap) break;
+            bytes += add; ng++;
+        }
+        const int s0 = isrc0 + g0 * K;
+        HIPCHECK(hipEventRecord(ev[0], c->stream));
+        run_chunk(c, s0, ng * K, proc_which);
+        HIPCHECK(hipEventRecord(ev[1], c->stream));
+        nbr_d.ensure((size_t)ng * nrec * NN, &c->dev_bytes);
+        coef_d.ensure((size_t)ng * K, &c->dev_bytes); mis_d.ensure((size_t)ng, &c->dev_bytes); piv_d.ensure((size_t)ng, &c->dev_bytes);
+        st_d.ensure((size_t)ng, &c->dev_bytes);
+        if (out.normal) normal_d.ensure((size_t)ng * NN, &c->dev_bytes);
+        HIPCHECK(hipMemsetAsync(nbr_d.p, 0, (size_t)ng * nrec * NN * sizeof(double), c->stream));
+        launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, coef_d.p, mis_d.p,
+                   st_d.p, piv_d.p, out.normal ? normal_d.p : (double *)nullptr);
+        HIPCHECK(hipEventRecord(ev[2], c->stream));
+        piv_h.resize((size_t)ng);
+        HIPCHECK(hipMemcpyAsync(out.coef + (size_t)g0 * K, coef_d.p, (size_t)ng * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(out.misfit + g0, mis_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(out.status + g0, st_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(out.pivot_min ? out.pivot_min + g0 : piv_h.data(), piv_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (out.normal)
+            HIPCHECK(hipMemcpyAsync(out.normal + (size_t)g0 * NN, normal_d.p, (size_t)ng * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (out.by_receiver)
+            HIPCHECK(hipMemcpyAsync(out.by_receiver + (size_t)g0 * nrec * NN, nbr_d.p, (size_t)ng * nrec * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipEventRecord(ev[3], c->stream));
+        HIPCHECK(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < 3; i++) {
+            float t = 0.f;
+            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+            c->linfit_ms[i] += t;
+        }
+        g0 += ng;
+    }
+    // what an evaluation of the range leaves behind (eval_impl)
+    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = proc_which;
+    c->evaluated.resize((size_t)c->nsrc, 0);
+    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
+    // a basis source that failed to discretise: no fit for its group
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int g = 0; g < ngroup; g++) {
+        bool bad = false;
+        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
+        if (!bad) continue;
+        out.status[g] = 2;
+        out.misfit[g] = nan;
+        for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
+    }
+}
+
+// groups whose basis sources could not be discretised at all (nothing was uploaded for them): status 2, NaN, zero sums
+static void fill_failed(int ngroup, int K, int nrec, const Out &out)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const size_t nn = (size_t)nn_of(K);
+    for (int g = 0; g < ngroup; g++) {
+        out.status[g] = 2; out.misfit[g] = nan;
+        for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
+        if (out.pivot_min) out.pivot_min[g] = 0.0;
+    }
+    if (out.normal) std::memset(out.normal, 0, (size_t)ngroup * nn * sizeof(double));
+    if (out.by_receiver) std::memset(out.by_receiver, 0, (size_t)ngroup * nrec * nn * sizeof(double));
+}
+
+} // namespace linfit

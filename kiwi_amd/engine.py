@@ -4,6 +4,7 @@ Method names follow the reference's stdin commands / minimizer_engine procedures
 (minimizer.f90:1729-1811) so that the calling code reads like python/tunguska/seismosizer.py;
 ``make_misfits_for_sources`` and ``make_global_misfits`` restate the two Python functions that sit
 directly on the path (seismosizer.py:682-722, 843-922)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,8 @@ SOURCE_TYPES = {"bilateral": 1, "circular": 2, "point_lp": 3, "eikonal": 4, "mt_
                 "moment_tensor": 6}          # source_all.f90:88-98
 NORMS = {"l2norm": 1, "l1norm": 2, "ampspec_l2norm": 3, "ampspec_l1norm": 4, "scalar_product": 5,
          "peak": 6, "floating_l2norm": 7, "floating_l1norm": 8}      # comparator.f90:137-146
+
+LinearFit = collections.namedtuple("LinearFit", "coef misfit status pivot_min normal by_receiver")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
                    ("f", np.float32, 6), ("cl", np.float32), ("sl", np.float32), ("flags", np.int32),
@@ -637,6 +640,78 @@ class Engine:
             mf, nf = m.reshape(ns, nrec * kmax)[:, cols], n.reshape(ns, nrec * kmax)[:, cols]
         return self.outer_misfits_slots(mf, nf, slot_receiver, nrec, outer_norm, receiver_weights, anarchy, draw_weights,
                                         which_draw)
+
+    # ------------------------------------------------------------------ linear fit (kiwi_hip_linear_fit)
+    def linear_fit_max_basis(self):
+        """The most basis sources per group `linear_fit` takes."""
+        return int(self.L.kiwi_hip_linear_fit_max_basis())
+
+    def _linear_fit_arrays(self, ngroup, K, receiver_weights, normal, by_receiver):
+        K, ngroup = int(K), int(ngroup)
+        if not 1 <= K <= self.linear_fit_max_basis():
+            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        nrec, nn = len(self.components), K * (K + 1) // 2 + K + 1
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        out = LinearFit(np.zeros((ngroup, K)), np.zeros(ngroup), np.zeros(ngroup, np.int32), np.zeros(ngroup),
+                        np.zeros((ngroup, nn)) if normal else None, np.zeros((ngroup, nrec, nn)) if by_receiver else None)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        return w, out, dp
+
+    def linear_fit(self, isrc0, ngroup, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False):
+        """Least-squares coefficients of K basis sources per group under l2norm (kiwi_hip_linear_fit): sources
+        [isrc0, isrc0 + ngroup K) of the uploaded batch are `ngroup` groups of K consecutive basis sources.  Returns a
+        `LinearFit`: coef[ngroup, K], misfit[ngroup] (the global misfit of the fitted combination), status[ngroup] (0 solved,
+        1 no solution, 2 a basis source failed to discretise), pivot_min[ngroup] (smallest Cholesky pivot of the unit-diagonal
+        normal matrix: judge near-dependence by it), and on request normal[ngroup, NN] (G upper triangle by rows, b, R --
+        weighted sums) and by_receiver[ngroup, nrec, NN] (unweighted, zeros for disabled receivers)."""
+        w, out, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, normal, by_receiver)
+        self._ck(self.L.kiwi_hip_linear_fit(self.h, int(isrc0), int(ngroup), int(K), dp(w), 1 if anarchy else 0, dp(out.coef),
+                                            dp(out.misfit), _ip(out.status), dp(out.pivot_min), dp(out.normal), dp(out.by_receiver)),
+                 "linear_fit")
+        return out
+
+    def linear_fit_params(self, sourcetype, params, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False, piece=0):
+        """`linear_fit` for a parameter list of any length (kiwi_hip_linear_fit_params): params[ngroup * K, nparams], every K
+        consecutive rows a group; discretised and uploaded in pieces of `piece` sources (rounded down to a multiple of K;
+        0: the default of misfits_for_params), the host discretiser of one piece running while the device works on another.
+        Piece size does not change a bit.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        w, out, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, normal, by_receiver)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_params(self.h, st, ngroup, K, _fp(p), int(piece), dp(w), 1 if anarchy else 0,
+                                                       dp(out.coef), dp(out.misfit), _ip(out.status), dp(out.pivot_min),
+                                                       dp(out.normal), dp(out.by_receiver)), "linear_fit")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        # the context holds the first piece (list order) that uploaded anything; a group's status does not say whether ALL of
+        # its piece failed to discretise, so the context is asked: the longest range of source statuses it answers
+        before = self.nsrc
+        buf = np.zeros(max(before, len(p), 1), np.int32)
+        lo, hi = 0, len(buf)
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if self.L.kiwi_hip_get_source_status(self.h, 0, mid, _ip(buf)) == 0:
+                lo = mid
+            else:
+                hi = mid - 1
+        self.nsrc = lo
+        return out
+
+    def linear_fit_ms(self):
+        """HIP-event durations [ms] of the last linear fit: (evaluation, fit kernels, downloads)."""
+        ms = np.zeros(3, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_ms(self.h, _fp(ms)), "get_linear_fit_ms")
+        return tuple(float(x) for x in ms)
 
 
 def bootstrap_draw_weights(nrec, ndraw, rng, receiver_mask=None, receiver_weights=None):

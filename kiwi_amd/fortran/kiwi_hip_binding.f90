@@ -324,6 +324,44 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(3)
         end function
 
+        ! least-squares coefficients of K basis sources per group under l2norm, groups of the uploaded batch (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_linear_fit( ctx, isrc0, ngroup, k, receiver_weight, anarchy, coef, misfit, status, &
+                pivot_min, normal, normal_by_receiver ) bind(C, name='kiwi_hip_linear_fit')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, anarchy      ! isrc0 0-based
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            real(c_double), intent(out) :: coef(*)        ! (k, ngroup)
+            real(c_double), intent(out) :: misfit(*)      ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: pivot_min               ! c_loc of real(c_double) (ngroup), or c_null_ptr
+            type(c_ptr), value :: normal                  ! c_loc of real(c_double) (nn, ngroup), nn = k (k + 1) / 2 + k + 1, or c_null_ptr
+            type(c_ptr), value :: normal_by_receiver      ! c_loc of real(c_double) (nn, nrec, ngroup), or c_null_ptr
+        end function
+
+        ! the same for a parameter list of ngroup * k sources, discretised and uploaded piece by piece
+        integer(c_int) function kiwi_hip_linear_fit_params( ctx, sourcetype, ngroup, k, params, piece, receiver_weight, anarchy, &
+                coef, misfit, status, pivot_min, normal, normal_by_receiver ) bind(C, name='kiwi_hip_linear_fit_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, anarchy
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            type(c_ptr), value :: receiver_weight
+            real(c_double), intent(out) :: coef(*), misfit(*)
+            integer(c_int), intent(out) :: status(*)
+            type(c_ptr), value :: pivot_min, normal, normal_by_receiver
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_max_basis() bind(C, name='kiwi_hip_linear_fit_max_basis')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_ms( ctx, ms ) bind(C, name='kiwi_hip_get_linear_fit_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(3)
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -94,12 +94,28 @@ class MisfitGrid:
         self.best_source = self.misfits_by_s = self.misfits_by_r = self.variability_by_r = None
         self.bootstrap_sources = self.stats = None
 
-    def compute(self, engine, dist=None, device=0):
+    def compute(self, engine, dist=None, device=0, linear_mt=False):
         """Trace misfits for every grid node (and the reference source), `engine` = kiwi_amd.Engine set up for
-        the inversion.  With a torch.distributed group the grid is sharded over the ranks (kiwi_amd/shard.py)."""
+        the inversion.  With a torch.distributed group the grid is sharded over the ranks (kiwi_amd/shard.py).
+        linear_mt=True (`moment_tensor`, `mt_eikonal`; l2norm): the grid runs over the OTHER parameters and every node gets
+        the moment tensor that fits best (kiwi_amd/mtfit.py, six evaluations per node): `fitted_tensors`, `fit_misfits`,
+        `fit_status`, `fit_pivot_min` per node, the tensor columns of `sources` replaced by the fitted tensors, `ibest`,
+        `best_source` and `misfits_by_s` from the fit.  The fitted sources are then evaluated like any grid, so that
+        `postprocess` (bootstrap over the receivers) works on them unchanged."""
         self.receiver_mask = np.array(engine.enabled, bool)
         self.nreceivers = len(engine.components)
         self.ncomponents = [len(c) for c in engine.components]
+        if linear_mt and len(self.sources):
+            from . import mtfit
+            if dist is not None:
+                raise KiwiHipError("linear_mt: a sharded fit is the caller's split of the grid at node boundaries (INTEGRATION.md)")
+            c0 = mtfit.TENSOR_COLUMN.get(SOURCE_TYPES[self.sourcetype])
+            if c0 is None or any(p in mtfit.COMPONENTS for p in self.sourceparams):
+                raise KiwiHipError("linear_mt: the source type must be moment_tensor or mt_eikonal and the grid must not run over tensor components")
+            self.fitted_tensors, self.fit_misfits, self.fit_status, self.fit_pivot_min = mtfit.fit_moment_tensors(
+                engine, self.sourcetype, self.sources)
+            solved = self.fit_status == 0
+            self.sources[solved, c0:c0 + 6] = self.fitted_tensors[solved].astype(np.float32)
         if len(self.sources):
             if dist is not None:
                 from .shard import sharded_misfits_for_sources
@@ -113,6 +129,10 @@ class MisfitGrid:
         self.ref_misfits_by_src, self.ref_norms_by_src, _ = engine.make_misfits_for_sources(self.sourcetype,
                                                                                           self.ref_params[None, :])
         self.best_source = None
+        if linear_mt and len(self.sources):
+            self.misfits_by_s = self.fit_misfits
+            self.ibest = int(np.nanargmin(self.fit_misfits)) if np.any(np.isfinite(self.fit_misfits)) else 0
+            self.best_source = self.sources[self.ibest]
 
     def _best_source(self, **cfg):
         g, g_sr = make_global_misfits(self.misfits_by_src, self.norms_by_src, receiver_mask=self.receiver_mask, **cfg)

@@ -1,0 +1,95 @@
+"""Best moment tensor per trial location by linear least squares.
+
+The seismograms of a `moment_tensor` or `mt_eikonal` source are linear in the six tensor components (they enter the
+centroid table as factors), so under the time-domain `l2norm` the global misfit is a quadratic form in the tensor and its
+minimum a 6 x 6 solve.  `elementary_params` turns every trial row into six basis sources (unit tensors), which share their
+geometry and run through the engine as one run of geometry-identical sources; `Engine.linear_fit_params` evaluates them,
+forms the inner products between their synthetics on the device and solves (kiwi_hip_linear_fit)."""
+import numpy as np
+
+from .engine import SOURCE_TYPES
+from .lib import KiwiHipError
+
+# first tensor column (mxx, myy, mzz, mxy, mxz, myz follow each other) of the source types whose tensor is free
+TENSOR_COLUMN = {6: 4, 5: 13}            # moment_tensor, mt_eikonal (source_moment_tensor.f90, source_mt_eikonal.f90:71-72)
+COMPONENTS = ("mxx", "myy", "mzz", "mxy", "mxz", "myz")
+
+
+def _tensor_column(sourcetype):
+    st = SOURCE_TYPES.get(sourcetype, sourcetype)
+    if st not in TENSOR_COLUMN:
+        raise KiwiHipError("a free moment tensor needs the source type moment_tensor or mt_eikonal, not %s" % (sourcetype,))
+    return st, TENSOR_COLUMN[st]
+
+
+def elementary_params(sourcetype, params, unit=1e18):
+    """Every row of params[N, nparams] repeated six times with the tensor columns replaced by `unit` x the six unit tensors
+    (order mxx, myy, mzz, mxy, mxz, myz): [6 N, nparams] float32, the six basis sources of a row consecutive."""
+    _, c0 = _tensor_column(sourcetype)
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    out = np.repeat(p, 6, axis=0)
+    out[:, c0:c0 + 6] = np.tile(np.eye(6, dtype=np.float32) * np.float32(unit), (len(p), 1))
+    return out
+
+
+# orthonormal basis of the trace-free tensors in the six-component order above: columns of T [6, 5]
+_s2, _s6 = np.sqrt(0.5), np.sqrt(1.0 / 6.0)
+DEVIATORIC_BASIS = np.array([[_s2, _s6, 0, 0, 0], [-_s2, _s6, 0, 0, 0], [0, -2 * _s6, 0, 0, 0],
+                             [0, 0, 1, 0, 0], [0, 0, 0, 1, 0], [0, 0, 0, 0, 1.]])
+
+
+def _unpack(normal):
+    G = np.zeros((6, 6))
+    k = 0
+    for i in range(6):
+        for j in range(i, 6):
+            G[i, j] = G[j, i] = normal[k]
+            k += 1
+    return G, np.array(normal[21:27]), float(normal[27])
+
+
+def solve_deviatoric(normal):
+    """Trace-free least squares from one row of `normal` (G upper triangle by rows, b, R of the six unit tensors), on the
+    host in fp64: coefficients [6] with mxx + myy + mzz = 0, misfit, status (0 solved, 1 no solution), smallest Cholesky
+    pivot of the unit-diagonal 5 x 5 matrix."""
+    G, b, R = _unpack(normal)
+    T = DEVIATORIC_BASIS
+    G5, b5 = T.T @ G @ T, T.T @ b
+    d = np.diag(G5)
+    nan6 = np.full(6, np.nan)
+    if not np.all(d > 0) or not R > 0:
+        return nan6, np.nan, 1, 0.0
+    s = 1.0 / np.sqrt(d)
+    A = G5 * s[:, None] * s[None, :]
+    try:
+        L = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        return nan6, np.nan, 1, 0.0
+    piv = float(np.min(np.diag(L)) ** 2)
+    if not piv > 5 * 2.0 ** -52:
+        return nan6, np.nan, 1, piv
+    y = np.linalg.solve(L.T, np.linalg.solve(L, b5 * s)) * s
+    x = T @ y
+    val = R - 2.0 * x @ b + x @ G @ x
+    return x, float(np.sqrt(max(val, 0.0) / R)), 0, piv
+
+
+def fit_moment_tensors(engine, sourcetype, params, unit=1e18, deviatoric=False, receiver_weights=None, anarchy=False, piece=0):
+    """The best moment tensor of every row of params[N, nparams] (its own tensor columns are ignored) under the engine's
+    references, tapers and filters, l2norm inside and outside.  Returns (tensors[N, 6] in N m, misfit[N] -- the global misfit
+    of the fitted tensor --, status[N]: 0 solved, 1 no solution, 2 the row failed to discretise; pivot_min[N]: the smallest
+    Cholesky pivot of the unit-diagonal normal matrix, small where the data do not resolve the tensor).  deviatoric=True
+    solves the trace-free problem (mxx + myy + mzz = 0) on the host from the device's normal equations."""
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    fit = engine.linear_fit_params(sourcetype, elementary_params(sourcetype, p, unit), 6, receiver_weights=receiver_weights,
+                                   anarchy=anarchy, normal=deviatoric, piece=piece)
+    if not deviatoric:
+        return fit.coef * float(unit), fit.misfit, fit.status, fit.pivot_min
+    tensors, misfit = np.full((len(p), 6), np.nan), np.full(len(p), np.nan)
+    status, pivot = np.array(fit.status, np.int32), np.zeros(len(p))
+    for g in range(len(p)):
+        if fit.status[g] == 2:
+            continue
+        x, m, st, piv = solve_deviatoric(fit.normal[g])
+        tensors[g], misfit[g], status[g], pivot[g] = x * float(unit), m, st, piv
+    return tensors, misfit, status, pivot
