@@ -394,6 +394,41 @@ int kiwi_hip_linear_fit_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, in
 int kiwi_hip_linear_fit_max_basis(void);
 /* HIP-event durations [ms] of the last linear fit on this context: ms[0] evaluation, ms[1] fit kernels, ms[2] downloads */
 int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *ctx, float ms[3]);
+/* The same coefficients under an l1 OUTER norm -- one noisy receiver must not drag the fit --, by iteratively reweighted least
+ * squares on the device (kiwi_amd/csrc/kiwi_linfit_robust.hpp).  The INNER norm is the context's misfit method; outer_norm is 1
+ * l1norm or 2 l2norm as for kiwi_hip_outer_misfits.  With x_0 the solution of kiwi_hip_linear_fit (same weights, same anarchy),
+ * R_r, b_r, G_r its per-receiver sums, w_r = receiver_weight[r] (NULL: ones; 0 and disabled receivers never count; a receiver whose
+ * R_r is not positive is skipped), T_r the samples of receiver r's windows:
+ *   l2norm, 2   forwards to kiwi_hip_linear_fit: its coef, misfit and status bit for bit; niter and eps are ignored;
+ *               trace[g][0] holds that misfit in both columns, the other entries NaN
+ *   l2norm, 1   per iteration m_r = sqrt(max(R_r - 2 x.b_r + x.G_r.x, 0)), n_r = sqrt(R_r), v_r = w_r (anarchy: w_r / n_r),
+ *               u_r = v_r / max(m_r, eps n_r); solve sum_r u_r (G_r, b_r).  misfit = sum v_r m_r / sum v_r n_r: make_global_misfits'
+ *               l1norm on the l2norm misfits per receiver.  All iterations in one launch on the sums the l2 start left behind
+ *   l1norm, 1   per iteration one pass over the kept synthetics: e[t] = d[t] - sum_k x_k s_k[t], a_r = eps sqrt(R_r / (dt T_r)) (eps x
+ *               the receiver's reference RMS), om[t] = 1 / max(|e[t]|, a_r); G_r = dt sum om s_i s_j, b_r = dt sum om s_i d,
+ *               L_r = dt sum |e|, D_r = dt sum |d|; v_r = w_r (anarchy: w_r / D_r); solve sum_r v_r (G_r, b_r).  misfit =
+ *               sum v_r L_r / sum v_r D_r: the global misfit with l1norm inside and outside
+ *   l1norm, 2   refused: the square of a sum of absolute values has no quadratic majoriser of this form
+ * Each solve is kiwi_hip_linear_fit's (diagonal scaling, Cholesky, pivot test K 2^-52).  niter >= 0 reweighted solves are made;
+ * eps > 0 (relative; 1e-3 is a good start) bounds the weights, and the iteration descends on the Huber function with that
+ * threshold, which lies within eps / 2 x (threshold sum / norm sum) below the true misfit.
+ *   coef    [ngroup][K]  x_niter            misfit  [ngroup]  the true misfit (above) at x_niter
+ *   status  [ngroup]     0 solved; 1 no l2 start; 2 a basis source failed to discretise (both answer NaN, as kiwi_hip_linear_fit);
+ *                        3 a reweighted system failed the pivot test at iteration i: coef is x_i, misfit its misfit
+ *   trace   [ngroup][niter + 1][2] or NULL: (smoothed objective, true misfit) at x_i; NaN rows after a status 3, and for status 1, 2
+ * No host round trip between iterations; every sum in a fixed order (tests/linfit_robust_restatement.py): the answer does not
+ * depend on chunking, isrc0, piece or the number of devices.  The basis sources' misfits are left as an evaluation under the
+ * context's method leaves them.  Refused: what kiwi_hip_linear_fit refuses (with l1norm allowed beside outer_norm 1), niter < 0, eps
+ * that is not positive and finite. */
+int kiwi_hip_linear_fit_robust(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int outer_norm, const double *receiver_weight,
+                               int anarchy, int niter, double eps, double *coef, double *misfit, int *status, double *trace);
+/* ... for a parameter list, cut into pieces and over devices as kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_robust_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                      int outer_norm, const double *receiver_weight, int anarchy, int niter, double eps,
+                                      double *coef, double *misfit, int *status, double *trace);
+/* HIP-event durations [ms] of the last linear fit of either kind: ms[0] evaluation, ms[1] l2 start (Gram and solve kernels),
+ * ms[2] reweighting passes, ms[3] downloads */
+int kiwi_hip_get_linear_fit_robust_ms(kiwi_hip_ctx *ctx, float ms[4]);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each
  * (layout in kiwi_amd/csrc/kiwi_kernels.hpp); for parity tests */
 int kiwi_hip_get_geometry(kiwi_hip_ctx *ctx, int isrc, int irec, int maxcent, int *ncent, void *records);

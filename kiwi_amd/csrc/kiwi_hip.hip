@@ -234,7 +234,7 @@ struct kiwi_hip_ctx {
     int proc_chunk0 = 0, proc_chunkn = 0, proc_which_held = 0;   // what proc_d currently holds
     size_t chunk_bytes_limit = (size_t)16 << 30;      // workspace per launch; the device has 288 GB
     float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
-    float linfit_ms[3] = { 0.f, 0.f, 0.f };           // evaluation, fit kernels, download of the last kiwi_hip_linear_fit (kiwi_linfit.hpp)
+    float linfit_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, l2 fit kernels, reweighting passes, download of the last linear fit (kiwi_linfit.hpp)
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
 
@@ -1426,6 +1426,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_gfk.hpp"
 #include "kiwi_outer.hpp"
 #include "kiwi_linfit.hpp"
+#include "kiwi_linfit_robust.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2768,7 +2769,7 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
 // so results do not depend on `piece` (a source's evaluation does not depend on its batch: tests).
 // (kiwi_hip_linear_fit_params goes through the same pieces with `fit` set: the list is then groups of fit->K consecutive basis
 // sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
-struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; };
+struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit)
@@ -2778,7 +2779,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (np < 0) throw std::runtime_error("source type not supported by the host discretiser");
     if (nsrc < 1) throw std::runtime_error("need at least one source");
     HIPCHECK(hipSetDevice(c->device));
-    if (fit) linfit::check_setup(c, fit->K, fit->out);
+    if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust);
     const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
@@ -2939,7 +2940,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         }
         upload_batch(c, hb);
         const double t_up = now();
-        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all));
+        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust);
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -2966,7 +2967,7 @@ int kiwi_hip_linear_fit(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const dou
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = 0.f;
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
     linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver });
     return 0;
     GUARD_END(c)
@@ -2981,8 +2982,8 @@ int kiwi_hip_linear_fit_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int 
     if (K < 1 || K > linfit::kMaxBasis)
         return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
     if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = 0.f;
-    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver } };
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver }, nullptr };
     return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
 }
 
@@ -2992,7 +2993,75 @@ int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *c, float ms[3])
 {
     if (!c) return fail(nullptr, "null context");
     if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 3; i++) ms[i] = c->linfit_ms[i];
+    ms[0] = c->linfit_ms[0]; ms[1] = c->linfit_ms[1]; ms[2] = c->linfit_ms[3];
+    return 0;
+}
+
+// The same fits under an l1 outer norm by iteratively reweighted least squares (kiwi_linfit_robust.hpp).  What the arguments
+// choose: 0 forward to the l2 fit, 1 mode A, 2 mode B; everything else is refused here or by linfit::check_setup
+static int robust_mode(kiwi_hip_ctx *c, int outer_norm, int niter, double eps)
+{
+    if (outer_norm != 1 && outer_norm != 2) throw std::runtime_error("linear_fit_robust: outer_norm must be 1 (l1norm) or 2 (l2norm)");
+    if (c->method == KIWI_L1NORM && outer_norm == 2)
+        throw std::runtime_error("linear_fit_robust: inner l1norm with outer l2norm is not supported (the square of a sum of absolute values has "
+                                 "no quadratic majoriser of this form); set outer_norm l1norm, or the misfit method l2norm");
+    if (outer_norm == 2) return 0;
+    if (niter < 0) throw std::runtime_error("linear_fit_robust: niter = " + std::to_string(niter) + " must not be negative");
+    if (!(eps > 0.0) || !std::isfinite(eps)) throw std::runtime_error("linear_fit_robust: eps must be positive and finite");
+    return c->method == KIWI_L1NORM ? 1 : 2;
+}
+
+// l2norm inside and outside: the l2 fit's answer, its misfit as the one trace row there is
+static void robust_forwarded_trace(int ngroup, int niter, const double *misfit, double *trace)
+{
+    if (!trace) return;
+    const size_t rows = (size_t)(niter > 0 ? niter : 0) + 1;
+    std::fill(trace, trace + (size_t)ngroup * rows * 2, std::numeric_limits<double>::quiet_NaN());
+    for (int g = 0; g < ngroup; g++) trace[(size_t)g * rows * 2] = trace[(size_t)g * rows * 2 + 1] = misfit[g];
+}
+
+int kiwi_hip_linear_fit_robust(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int outer_norm, const double *receiver_weight, int anarchy,
+                               int niter, double eps, double *coef, double *misfit, int *status, double *trace)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    const int mode = robust_mode(c, outer_norm, niter, eps);
+    if (mode == 0) {
+        linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status });
+        robust_forwarded_trace(ngroup, niter, misfit, trace);
+        return 0;
+    }
+    const linfit::Robust rb{ mode, niter, eps };
+    linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, nullptr, nullptr, nullptr, trace, niter + 1 }, &rb);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_robust_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int outer_norm,
+                                      const double *receiver_weight, int anarchy, int niter, double eps, double *coef, double *misfit,
+                                      int *status, double *trace)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    int mode = 0;
+    try { mode = robust_mode(c, outer_norm, niter, eps); } catch (const std::exception &e) { return fail(c, e.what()); }
+    const linfit::Robust rb{ mode, niter, eps };
+    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, nullptr, nullptr, nullptr, mode ? trace : nullptr, niter + 1 },
+                          mode ? &rb : nullptr };
+    const int rc = for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+    if (rc == 0 && mode == 0) robust_forwarded_trace(ngroup, niter, misfit, trace);
+    return rc;
+}
+
+int kiwi_hip_get_linear_fit_robust_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->linfit_ms[i];
     return 0;
 }
 

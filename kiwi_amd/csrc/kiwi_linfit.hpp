@@ -22,7 +22,8 @@
 //             The order is the same for every K, chunk size, isrc0 and group position.  No atomics.
 //   solve     one thread per group.  Receivers r ascending: w = receiver_weight[r] (0 for a disabled receiver); a receiver with
 //             w == 0 is skipped; anarchy: w = R_r > 0 ? w / sqrt(R_r) : 0; N[p] = N[p] + (w w) N_r[p].  D_i = G_ii; scaling
-//             s_i = 1 / sqrt(D_i); A_ij = (G_ij s_i) s_j, A_ii = 1.  Cholesky A = L L^T by columns j ascending:
+//             s_i = 1 / sqrt(D_i); A_ij = (G_ij s_i) s_j, A_ii = 1 (from here to coef_i: scaled_cholesky, which the reweighted
+//             solves of kiwi_linfit_robust.hpp share).  Cholesky A = L L^T by columns j ascending:
 //                 d = 1; d = d - L_jk L_jk (k < j ascending); pivot d; L_jj = sqrt(d);
 //                 v = A_ij; v = v - L_ik L_jk (k < j ascending); L_ij = v / L_jj   (i > j)
 //             y_i = (b_i s_i - sum_{k < i} L_ik y_k) / L_ii; z_i = (y_i - sum_{k > i} L_ki z_k) / L_ii (i descending, k
@@ -97,40 +98,15 @@ __global__ __launch_bounds__(kThreads) void linfit_gram_kernel(const float *__re
     }
 }
 
-// w: [nrec] receiver weights with zeros for disabled receivers.  normal: [ng][NN] or null
-template <int K>
-__global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restrict__ nbr, const double *__restrict__ w, int nrec,
-                                                          int anarchy, int ng, double *__restrict__ coef, double *__restrict__ misfit,
-                                                          int *__restrict__ status, double *__restrict__ pivot_min,
-                                                          double *__restrict__ normal)
+// The solve of linfit_solve_kernel (header comment) on sums laid out as G upper triangle by rows, then b: 0 and x, or 1 (a diagonal
+// element not positive, or a pivot <= K 2^-52) and NaN in x.  pmin: the smallest pivot up to and including the one that broke down
+template <int K, int M>
+__device__ __forceinline__ int scaled_cholesky(const double (&N)[M], double (&x)[K], double &pmin)
 {
-    constexpr int NG = K * (K + 1) / 2, NN = NG + K + 1;
-    const int g = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (g >= ng) return;
-    double N[NN];
-#pragma unroll
-    for (int p = 0; p < NN; p++) N[p] = 0.0;
-    for (int r = 0; r < nrec; r++) {
-        double wr = w[r];
-        if (wr == 0.0) continue;
-        const double *__restrict__ q = nbr + ((size_t)g * nrec + r) * NN;
-        if (anarchy) {
-            const double Rr = q[NN - 1];
-            wr = Rr > 0.0 ? wr / sqrt(Rr) : 0.0;
-            if (wr == 0.0) continue;
-        }
-        const double w2 = wr * wr;
-#pragma unroll
-        for (int p = 0; p < NN; p++) N[p] = N[p] + w2 * q[p];
-    }
-    if (normal)
-#pragma unroll
-        for (int p = 0; p < NN; p++) normal[(size_t)g * NN + p] = N[p];
-    const double R = N[NN - 1];
+    constexpr int NG = K * (K + 1) / 2;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     int st = 0;
-    double pmin = 0.0;
-    double x[K];
+    pmin = 0.0;
 #pragma unroll
     for (int i = 0; i < K; i++) x[i] = nan;
     bool diag_ok = true;
@@ -186,6 +162,43 @@ __global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restri
             for (int i = 0; i < K; i++) x[i] = y[i] * s[i];
         }
     }
+    return st;
+}
+
+// w: [nrec] receiver weights with zeros for disabled receivers.  normal: [ng][NN] or null
+template <int K>
+__global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restrict__ nbr, const double *__restrict__ w, int nrec,
+                                                          int anarchy, int ng, double *__restrict__ coef, double *__restrict__ misfit,
+                                                          int *__restrict__ status, double *__restrict__ pivot_min,
+                                                          double *__restrict__ normal)
+{
+    constexpr int NG = K * (K + 1) / 2, NN = NG + K + 1;
+    const int g = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (g >= ng) return;
+    double N[NN];
+#pragma unroll
+    for (int p = 0; p < NN; p++) N[p] = 0.0;
+    for (int r = 0; r < nrec; r++) {
+        double wr = w[r];
+        if (wr == 0.0) continue;
+        const double *__restrict__ q = nbr + ((size_t)g * nrec + r) * NN;
+        if (anarchy) {
+            const double Rr = q[NN - 1];
+            wr = Rr > 0.0 ? wr / sqrt(Rr) : 0.0;
+            if (wr == 0.0) continue;
+        }
+        const double w2 = wr * wr;
+#pragma unroll
+        for (int p = 0; p < NN; p++) N[p] = N[p] + w2 * q[p];
+    }
+    if (normal)
+#pragma unroll
+        for (int p = 0; p < NN; p++) normal[(size_t)g * NN + p] = N[p];
+    const double R = N[NN - 1];
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double pmin;
+    double x[K];
+    int st = scaled_cholesky<K>(N, x, pmin);
     if (!(R > 0.0)) st = 1;
     double mf = nan;
     if (st == 0) {
@@ -238,28 +251,36 @@ static void launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, con
     }
 }
 
-// host arrays of the caller, each for the groups of ONE call of run(); any of pivot_min, normal, by_receiver may be null
+// host arrays of the caller, each for the groups of ONE call of run(); any of pivot_min, normal, by_receiver, trace may be null
+// (trace: [group][trace_rows][2], the iterations of a robust fit)
 struct Out {
     double *coef, *misfit;
     int *status;
-    double *pivot_min, *normal, *by_receiver;
+    double *pivot_min, *normal, *by_receiver, *trace;
+    int trace_rows;
     Out at(int g, int K, int nrec) const
     {
         const size_t nn = (size_t)nn_of(K);
         return Out{ coef + (size_t)g * K, misfit + g, status + g, pivot_min ? pivot_min + g : nullptr,
-                    normal ? normal + (size_t)g * nn : nullptr, by_receiver ? by_receiver + (size_t)g * nrec * nn : nullptr };
+                    normal ? normal + (size_t)g * nn : nullptr, by_receiver ? by_receiver + (size_t)g * nrec * nn : nullptr,
+                    trace ? trace + (size_t)g * trace_rows * 2 : nullptr, trace_rows };
     }
 };
 
+// the reweighting passes behind the l2 solve (kiwi_linfit_robust.hpp); mode 1: A (inner l1norm), 2: B (inner l2norm)
+struct Robust { int mode; int niter; double eps; };
+static void robust_launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, const double *nbr,
+                              const Robust &rb, double *wbr, double *x, double *misfit, int *status, double *trace);
+
 // what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.
-static void check_setup(kiwi_hip_ctx *c, int K, const Out &out)
+static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr)
 {
     if (K < 1 || K > kMaxBasis)
         throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(kMaxBasis) + " are supported");
     if (!out.coef || !out.misfit || !out.status) throw std::runtime_error("linear_fit: null coef, misfit or status array");
     if (c->method == KIWI_FLOATING_L2NORM || c->method == KIWI_FLOATING_L1NORM)
         throw std::runtime_error("linear_fit: floating shift ranges make the misfit a minimum over shifts, which is not quadratic in the coefficients; set l2norm");
-    if (c->method != KIWI_L2NORM)
+    if (c->method != KIWI_L2NORM && !(rb && rb->mode == 1 && c->method == KIWI_L1NORM))
         throw std::runtime_error("linear_fit: the misfit method must be l2norm (the only inner norm that is quadratic in the coefficients)");
     prepare(c);
     if (c->synth_only) throw std::runtime_error("linear_fit: every enabled receiver component needs a reference seismogram");
@@ -267,10 +288,12 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Out &out)
         throw std::runtime_error("linear_fit: an enabled receiver has no misfit taper (its comparison span follows the source, so the basis traces have no common span)");
 }
 
-// the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->linfit_ms
-static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Out &out)
+// the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->linfit_ms.  rb: the reweighting
+// passes of a robust fit behind the l2 solve of every chunk, or null
+static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Out &out,
+                const Robust *rb = nullptr)
 {
-    check_setup(c, K, out);
+    check_setup(c, K, out, rb);
     if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
         throw std::runtime_error("linear_fit: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
                                  " are not inside the uploaded batch of " + std::to_string(c->nsrc));
@@ -295,15 +318,16 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     std::vector<double> w((size_t)nrec, 0.0);
     for (int r = 0; r < nrec; r++)
         if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
-    DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d;
+    DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d, wbr_d, trace_d;
+    const size_t trace_len = rb ? (size_t)(rb->niter + 1) * 2 : 0;
     DevBuf<int> st_d;
     w_d.alloc((size_t)nrec, &c->dev_bytes);
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 4; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    hipEvent_t ev[5];
+    for (int i = 0; i < 5; i++) ev[i] = c->get_event();
+    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 5; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
     std::vector<double> piv_h;
     int g0 = 0;
     while (g0 < ngroup) {
@@ -316,7 +340,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
                 const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
                 add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float) * 2;
             }
-            add += (size_t)nrec * NN * sizeof(double);
+            add += (size_t)nrec * (NN + (rb && rb->mode == 1 ? NN + 2 : 0)) * sizeof(double);
             if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
             if (c->fft_needed && (ng + 1) * K > c->fft_cap) break;
             bytes += add; ng++;
@@ -333,6 +357,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, coef_d.p, mis_d.p,
                    st_d.p, piv_d.p, out.normal ? normal_d.p : (double *)nullptr);
         HIPCHECK(hipEventRecord(ev[2], c->stream));
+        if (rb) {
+            if (rb->mode == 1) wbr_d.ensure((size_t)ng * nrec * (NN + 2), &c->dev_bytes);
+            trace_d.ensure((size_t)ng * trace_len, &c->dev_bytes);
+            robust_launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, *rb, wbr_d.p,
+                              coef_d.p, mis_d.p, st_d.p, trace_d.p);
+        }
+        HIPCHECK(hipEventRecord(ev[3], c->stream));
         piv_h.resize((size_t)ng);
         HIPCHECK(hipMemcpyAsync(out.coef + (size_t)g0 * K, coef_d.p, (size_t)ng * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipMemcpyAsync(out.misfit + g0, mis_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -342,9 +373,11 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             HIPCHECK(hipMemcpyAsync(out.normal + (size_t)g0 * NN, normal_d.p, (size_t)ng * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (out.by_receiver)
             HIPCHECK(hipMemcpyAsync(out.by_receiver + (size_t)g0 * nrec * NN, nbr_d.p, (size_t)ng * nrec * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(hipEventRecord(ev[3], c->stream));
+        if (rb && out.trace)
+            HIPCHECK(hipMemcpyAsync(out.trace + (size_t)g0 * trace_len, trace_d.p, (size_t)ng * trace_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipEventRecord(ev[4], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 3; i++) {
+        for (int i = 0; i < 4; i++) {
             float t = 0.f;
             HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
             c->linfit_ms[i] += t;
@@ -364,6 +397,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         out.status[g] = 2;
         out.misfit[g] = nan;
         for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
+        if (out.trace) std::fill(out.trace + (size_t)g * out.trace_rows * 2, out.trace + (size_t)(g + 1) * out.trace_rows * 2, nan);
     }
 }
 
@@ -377,6 +411,7 @@ static void fill_failed(int ngroup, int K, int nrec, const Out &out)
         for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
         if (out.pivot_min) out.pivot_min[g] = 0.0;
     }
+    if (out.trace) std::fill(out.trace, out.trace + (size_t)ngroup * out.trace_rows * 2, nan);
     if (out.normal) std::memset(out.normal, 0, (size_t)ngroup * nn * sizeof(double));
     if (out.by_receiver) std::memset(out.by_receiver, 0, (size_t)ngroup * nrec * nn * sizeof(double));
 }

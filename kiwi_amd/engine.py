@@ -18,6 +18,7 @@ NORMS = {"l2norm": 1, "l1norm": 2, "ampspec_l2norm": 3, "ampspec_l1norm": 4, "sc
          "peak": 6, "floating_l2norm": 7, "floating_l1norm": 8}      # comparator.f90:137-146
 
 LinearFit = collections.namedtuple("LinearFit", "coef misfit status pivot_min normal by_receiver")
+RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
                    ("f", np.float32, 6), ("cl", np.float32), ("sl", np.float32), ("flags", np.int32),
@@ -164,6 +165,7 @@ class Engine:
             self.h = None
             raise KiwiHipError("kiwi_hip_init: " + buf.value.decode())
         self.nsrc = 0
+        self.misfit_method = "l2norm"      # the library's default
         if eikonal_solver is not None:
             self.set_eikonal_solver(eikonal_solver)
 
@@ -312,6 +314,7 @@ class Engine:
         if not isinstance(name, int) and name not in NORMS:
             raise KiwiHipError("set_misfit_method: nok > unknown norm: %s" % name)   # minimizer.f90:842-873
         self._ck(self.L.kiwi_hip_set_misfit_method(self.h, NORMS.get(name, name)), "set_misfit_method")
+        self.misfit_method = {v: k for k, v in NORMS.items()}.get(name, name)
 
     def shift_ref_seismogram(self, irec, shift):
         """`shift_ref_seismogram ireceiver shift` (seconds)."""
@@ -693,10 +696,14 @@ class Engine:
         except KiwiHipError:
             self.nsrc = 0
             raise
-        # the context holds the first piece (list order) that uploaded anything; a group's status does not say whether ALL of
-        # its piece failed to discretise, so the context is asked: the longest range of source statuses it answers
-        before = self.nsrc
-        buf = np.zeros(max(before, len(p), 1), np.int32)
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def _uploaded_sources(self, nlist):
+        """how many sources the context holds after a list call of `nlist` rows: its first piece (list order) that uploaded
+        anything; a group's status does not say whether ALL of its piece failed to discretise, so the context is asked: the
+        longest range of source statuses it answers"""
+        buf = np.zeros(max(self.nsrc, nlist, 1), np.int32)
         lo, hi = 0, len(buf)
         while lo < hi:
             mid = (lo + hi + 1) // 2
@@ -704,13 +711,64 @@ class Engine:
                 lo = mid
             else:
                 hi = mid - 1
-        self.nsrc = lo
-        return out
+        return lo
 
     def linear_fit_ms(self):
         """HIP-event durations [ms] of the last linear fit: (evaluation, fit kernels, downloads)."""
         ms = np.zeros(3, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_ms(self.h, _fp(ms)), "get_linear_fit_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ robust linear fit (kiwi_hip_linear_fit_robust)
+    def _robust_fit_arrays(self, ngroup, K, outer_norm, receiver_weights, niter, eps):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        w, fit, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
+        out = RobustFit(fit.coef, fit.misfit, fit.status, np.zeros((int(ngroup), max(int(niter), 0) + 1, 2)))
+        return code, w, out, dp
+
+    def linear_fit_robust(self, isrc0, ngroup, K, outer_norm="l1norm", receiver_weights=None, anarchy=False, niter=8, eps=1e-3):
+        """`linear_fit` under an l1 outer norm by iteratively reweighted least squares on the device
+        (kiwi_hip_linear_fit_robust); the inner norm is the engine's misfit method: l2norm (the receivers' l2 misfits are
+        summed) or l1norm (the samples' absolute residuals are).  `niter` reweighted solves from the l2 solution; `eps`
+        (relative) bounds the weights.  outer_norm="l2norm" with the method l2norm forwards to `linear_fit`.  Returns a
+        `RobustFit`: coef[ngroup, K], misfit[ngroup] (the global misfit under the two norms), status[ngroup] (0 solved, 1 no
+        l2 start, 2 a basis source failed to discretise, 3 a reweighted system broke down: coef and misfit of the iterate
+        before), trace[ngroup, niter + 1, 2] ((smoothed objective, misfit) per iterate)."""
+        code, w, out, dp = self._robust_fit_arrays(ngroup, K, outer_norm, receiver_weights, niter, eps)
+        self._ck(self.L.kiwi_hip_linear_fit_robust(self.h, int(isrc0), int(ngroup), int(K), code, dp(w), 1 if anarchy else 0, int(niter),
+                                                   float(eps), dp(out.coef), dp(out.misfit), _ip(out.status), dp(out.trace)),
+                 "linear_fit_robust")
+        return out
+
+    def linear_fit_robust_params(self, sourcetype, params, K, outer_norm="l1norm", receiver_weights=None, anarchy=False, niter=8,
+                                 eps=1e-3, piece=0):
+        """`linear_fit_robust` for a parameter list of any length (kiwi_hip_linear_fit_robust_params), cut into pieces and
+        over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        code, w, out, dp = self._robust_fit_arrays(ngroup, K, outer_norm, receiver_weights, niter, eps)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_robust_params(self.h, st, ngroup, K, _fp(p), int(piece), code, dp(w), 1 if anarchy else 0,
+                                                              int(niter), float(eps), dp(out.coef), dp(out.misfit), _ip(out.status),
+                                                              dp(out.trace)), "linear_fit_robust")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_robust_ms(self):
+        """HIP-event durations [ms] of the last linear fit of either kind: (evaluation, l2 start, reweighting passes, downloads)."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_robust_ms(self.h, _fp(ms)), "get_linear_fit_robust_ms")
         return tuple(float(x) for x in ms)
 
 

@@ -362,6 +362,39 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(3)
         end function
 
+        ! the same under an l1 outer norm by iteratively reweighted least squares; the inner norm is the misfit method (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_linear_fit_robust( ctx, isrc0, ngroup, k, outer_norm, receiver_weight, anarchy, niter, eps, &
+                coef, misfit, status, trace ) bind(C, name='kiwi_hip_linear_fit_robust')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, outer_norm, anarchy, niter      ! isrc0 0-based; outer_norm 1 l1norm, 2 l2norm
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            real(c_double), value :: eps
+            real(c_double), intent(out) :: coef(*)        ! (k, ngroup)
+            real(c_double), intent(out) :: misfit(*)      ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: trace                   ! c_loc of real(c_double) (2, niter + 1, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_robust_params( ctx, sourcetype, ngroup, k, params, piece, outer_norm, &
+                receiver_weight, anarchy, niter, eps, coef, misfit, status, trace ) bind(C, name='kiwi_hip_linear_fit_robust_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, outer_norm, anarchy, niter
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            type(c_ptr), value :: receiver_weight
+            real(c_double), value :: eps
+            real(c_double), intent(out) :: coef(*), misfit(*)
+            integer(c_int), intent(out) :: status(*)
+            type(c_ptr), value :: trace
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_robust_ms( ctx, ms ) bind(C, name='kiwi_hip_get_linear_fit_robust_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

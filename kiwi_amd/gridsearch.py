@@ -94,14 +94,16 @@ class MisfitGrid:
         self.best_source = self.misfits_by_s = self.misfits_by_r = self.variability_by_r = None
         self.bootstrap_sources = self.stats = None
 
-    def compute(self, engine, dist=None, device=0, linear_mt=False):
+    def compute(self, engine, dist=None, device=0, linear_mt=False, outer_norm="l2norm", niter=8, eps=1e-3):
         """Trace misfits for every grid node (and the reference source), `engine` = kiwi_amd.Engine set up for
         the inversion.  With a torch.distributed group the grid is sharded over the ranks (kiwi_amd/shard.py).
         linear_mt=True (`moment_tensor`, `mt_eikonal`; l2norm): the grid runs over the OTHER parameters and every node gets
         the moment tensor that fits best (kiwi_amd/mtfit.py, six evaluations per node): `fitted_tensors`, `fit_misfits`,
         `fit_status`, `fit_pivot_min` per node, the tensor columns of `sources` replaced by the fitted tensors, `ibest`,
         `best_source` and `misfits_by_s` from the fit.  The fitted sources are then evaluated like any grid, so that
-        `postprocess` (bootstrap over the receivers) works on them unchanged."""
+        `postprocess` (bootstrap over the receivers) works on them unchanged.  outer_norm="l1norm" (or an engine whose misfit
+        method is l1norm) fits the tensors robustly, `niter` reweighted solves with the relative bound `eps`
+        (`mtfit.fit_moment_tensors`); a node whose reweighting broke down (status 3) keeps the tensor it reached."""
         self.receiver_mask = np.array(engine.enabled, bool)
         self.nreceivers = len(engine.components)
         self.ncomponents = [len(c) for c in engine.components]
@@ -113,8 +115,8 @@ class MisfitGrid:
             if c0 is None or any(p in mtfit.COMPONENTS for p in self.sourceparams):
                 raise KiwiHipError("linear_mt: the source type must be moment_tensor or mt_eikonal and the grid must not run over tensor components")
             self.fitted_tensors, self.fit_misfits, self.fit_status, self.fit_pivot_min = mtfit.fit_moment_tensors(
-                engine, self.sourcetype, self.sources)
-            solved = self.fit_status == 0
+                engine, self.sourcetype, self.sources, outer_norm=outer_norm, niter=niter, eps=eps)
+            solved = (self.fit_status == 0) | (self.fit_status == 3)
             self.sources[solved, c0:c0 + 6] = self.fitted_tensors[solved].astype(np.float32)
         if len(self.sources):
             if dist is not None:

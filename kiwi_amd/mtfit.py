@@ -74,13 +74,24 @@ def solve_deviatoric(normal):
     return x, float(np.sqrt(max(val, 0.0) / R)), 0, piv
 
 
-def fit_moment_tensors(engine, sourcetype, params, unit=1e18, deviatoric=False, receiver_weights=None, anarchy=False, piece=0):
+def fit_moment_tensors(engine, sourcetype, params, unit=1e18, deviatoric=False, receiver_weights=None, anarchy=False, piece=0,
+                       outer_norm="l2norm", niter=8, eps=1e-3):
     """The best moment tensor of every row of params[N, nparams] (its own tensor columns are ignored) under the engine's
     references, tapers and filters, l2norm inside and outside.  Returns (tensors[N, 6] in N m, misfit[N] -- the global misfit
     of the fitted tensor --, status[N]: 0 solved, 1 no solution, 2 the row failed to discretise; pivot_min[N]: the smallest
     Cholesky pivot of the unit-diagonal normal matrix, small where the data do not resolve the tensor).  deviatoric=True
-    solves the trace-free problem (mxx + myy + mzz = 0) on the host from the device's normal equations."""
+    solves the trace-free problem (mxx + myy + mzz = 0) on the host from the device's normal equations.
+    outer_norm="l1norm", or an engine whose misfit method is l1norm: the robust fit (`Engine.linear_fit_robust_params`, `niter`
+    reweighted solves with the relative bound `eps`) under the engine's method inside and `outer_norm` outside; status 3 then
+    marks a reweighted system that broke down (the tensor of the iterate before), pivot_min is NaN, and deviatoric=True is
+    refused (the host's trace-free solve works from l2 normal equations)."""
     p = np.atleast_2d(np.asarray(params, np.float32))
+    if outer_norm != "l2norm" or getattr(engine, "misfit_method", "l2norm") != "l2norm":
+        if deviatoric:
+            raise KiwiHipError("fit_moment_tensors: deviatoric=True works from l2 normal equations; not available with a robust fit")
+        fit = engine.linear_fit_robust_params(sourcetype, elementary_params(sourcetype, p, unit), 6, outer_norm=outer_norm,
+                                              receiver_weights=receiver_weights, anarchy=anarchy, niter=niter, eps=eps, piece=piece)
+        return fit.coef * float(unit), fit.misfit, fit.status, np.full(len(p), np.nan)
     fit = engine.linear_fit_params(sourcetype, elementary_params(sourcetype, p, unit), 6, receiver_weights=receiver_weights,
                                    anarchy=anarchy, normal=deviatoric, piece=piece)
     if not deviatoric:
