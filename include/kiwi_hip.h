@@ -429,6 +429,45 @@ int kiwi_hip_linear_fit_robust_params(kiwi_hip_ctx *ctx, int sourcetype, int ngr
 /* HIP-event durations [ms] of the last linear fit of either kind: ms[0] evaluation, ms[1] l2 start (Gram and solve kernels),
  * ms[2] reweighting passes, ms[3] downloads */
 int kiwi_hip_get_linear_fit_robust_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* kiwi_hip_linear_fit for 1 <= K <= kiwi_hip_linear_fit_wide_max_basis() basis sources per group, with an optional quadratic
+ * penalty and optional non-negative coefficients: the multi-time-window slip inversion, where every patch of a fault in every
+ * time window is a basis source whose moment must not be negative and neighbouring patches are tied by a smoothing term
+ * (kiwi_amd/slipfit.py; kiwi_amd/csrc/kiwi_linfit_wide.hpp).  The same s_i, d, G_r, b_r, R_r, layout (NN = K (K + 1) / 2 + K + 1),
+ * fold (receiver_weight, anarchy), scaling to unit diagonal, Cholesky, pivot test K 2^-52, misfit formula and statuses 0, 1, 2;
+ * for K <= 8 with nonneg = 0 and no penalty every output equals kiwi_hip_linear_fit's bit for bit.
+ *   penalty    [K (K + 1) / 2] or NULL: the upper triangle by rows of a symmetric P.  After the fold G_ij = G_ij + lam P_ij with
+ *              lam = 1 (penalty_relative = 0) or lam = (sum_i G_ii) / K, the mean diagonal before the penalty is added
+ *              (penalty_relative != 0).  `normal` returns the sums WITHOUT the penalty and `misfit` is the data misfit
+ *              sqrt(max(R - 2 x.b + x.G.x, 0) / R) with them; pivot_min, and the diagonal test of status 1, refer to the penalised matrix
+ *   nonneg     0: free coefficients.  1: every coefficient >= 0, by the active-set method of Lawson and Hanson on the normal
+ *              equations in the scaled variables (A the scaled penalised matrix, c_i = b_i s_i, x = 0, passive set P empty):
+ *              (1) w_i = c_i - sum_{j in P} A_ij x_j for i outside P and not barred; the largest (lowest index among equals) joins
+ *              P as i*, unless there is none or it is not > 10 K 2^-52 max_i |c_i|: finished.  (2) Solve A_PP z = c_P by the same
+ *              Cholesky over P ascending; a failed pivot takes i* out of P and bars it for the rest of the call (a dependent
+ *              column), back to (1).  (3) Every z_i > 0: x_P = z, back to (1); otherwise x moves towards z by alpha = min over i in P
+ *              with z_i <= 0 of x_i / (x_i - z_i) (lowest index among equals), that index becomes exactly 0, every i with x_i <= 0
+ *              leaves P, back to (2).  After 3 K solves: status 4, the current (feasible) x is returned.  Status 1 then only for
+ *              a diagonal that is not positive, R not positive, or a scaled b_i or matrix element that is not finite (pivot_min 0);
+ *              pivot_min is otherwise the smallest pivot of the last solve that did not break down
+ *   status     additionally 4: the cap of 3 K solves was reached (coef and misfit of the feasible iterate)
+ *   npositive  [ngroup] or NULL: the coefficients > 0        nsolves  [ngroup] or NULL: Cholesky solves made (1 with nonneg = 0)
+ * The whole active-set loop runs on the device without a host round trip; every sum has a fixed order
+ * (tests/linfit_wide_restatement.py): the answer does not depend on chunking, isrc0, piece or the number of devices.  Refused:
+ * what kiwi_hip_linear_fit refuses, K outside 1 .. 64, nonneg other than 0 or 1, a penalty entry that is not finite.
+ * kiwi_hip_get_linear_fit_ms reports the call (ms[1]: Gram and solve kernels). */
+int kiwi_hip_linear_fit_wide(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, int nonneg,
+                             const double *penalty, int penalty_relative, double *coef, double *misfit, int *status,
+                             double *pivot_min, int *npositive, int *nsolves, double *normal, double *normal_by_receiver);
+/* ... for a parameter list, cut into pieces and over devices as kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                    const double *receiver_weight, int anarchy, int nonneg, const double *penalty,
+                                    int penalty_relative, double *coef, double *misfit, int *status, double *pivot_min,
+                                    int *npositive, int *nsolves, double *normal, double *normal_by_receiver);
+/* HIP-event durations [ms] of the last wide linear fit, which kiwi_hip_get_linear_fit_ms reports as one figure: ms[0] Gram kernels,
+ * ms[1] solve kernel (fold, penalty, Cholesky or active-set loop) */
+int kiwi_hip_get_linear_fit_wide_ms(kiwi_hip_ctx *ctx, float ms[2]);
+/* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
+int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each
  * (layout in kiwi_amd/csrc/kiwi_kernels.hpp); for parity tests */
 int kiwi_hip_get_geometry(kiwi_hip_ctx *ctx, int isrc, int irec, int maxcent, int *ncent, void *records);

@@ -234,6 +234,7 @@ struct kiwi_hip_ctx {
     int proc_chunk0 = 0, proc_chunkn = 0, proc_which_held = 0;   // what proc_d currently holds
     size_t chunk_bytes_limit = (size_t)16 << 30;      // workspace per launch; the device has 288 GB
     float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
+    float linfit_wide_ms[2] = { 0.f, 0.f };           // Gram kernels, solve kernel of the last wide linear fit (kiwi_linfit_wide.hpp)
     float linfit_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, l2 fit kernels, reweighting passes, download of the last linear fit (kiwi_linfit.hpp)
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
@@ -1427,6 +1428,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_outer.hpp"
 #include "kiwi_linfit.hpp"
 #include "kiwi_linfit_robust.hpp"
+#include "kiwi_linfit_wide.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2769,7 +2771,7 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
 // so results do not depend on `piece` (a source's evaluation does not depend on its batch: tests).
 // (kiwi_hip_linear_fit_params goes through the same pieces with `fit` set: the list is then groups of fit->K consecutive basis
 // sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
-struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; };
+struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; const linfit::Wide *wide; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit)
@@ -2779,7 +2781,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (np < 0) throw std::runtime_error("source type not supported by the host discretiser");
     if (nsrc < 1) throw std::runtime_error("need at least one source");
     HIPCHECK(hipSetDevice(c->device));
-    if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust);
+    if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust, fit->wide);
     const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
@@ -2940,7 +2942,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         }
         upload_batch(c, hb);
         const double t_up = now();
-        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust);
+        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust, fit->wide);
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -2988,6 +2990,49 @@ int kiwi_hip_linear_fit_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int 
 }
 
 int kiwi_hip_linear_fit_max_basis(void) { return linfit::kMaxBasis; }
+
+// The same fit for up to 64 basis sources, with a penalty and non-negative coefficients (kiwi_linfit_wide.hpp)
+int kiwi_hip_linear_fit_wide_max_basis(void) { return linfit::kWideMaxBasis; }
+
+int kiwi_hip_linear_fit_wide(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, int nonneg,
+                             const double *penalty, int penalty_relative, double *coef, double *misfit, int *status, double *pivot_min,
+                             int *npositive, int *nsolves, double *normal, double *normal_by_receiver)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    c->linfit_wide_ms[0] = c->linfit_wide_ms[1] = 0.f;
+    const linfit::Wide wd{ nonneg, penalty, penalty_relative ? 1 : 0 };
+    linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy,
+                linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves }, nullptr, &wd);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_get_linear_fit_wide_ms(kiwi_hip_ctx *c, float ms[2])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    ms[0] = c->linfit_wide_ms[0]; ms[1] = c->linfit_wide_ms[1];
+    return 0;
+}
+
+int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                    const double *receiver_weight, int anarchy, int nonneg, const double *penalty, int penalty_relative,
+                                    double *coef, double *misfit, int *status, double *pivot_min, int *npositive, int *nsolves,
+                                    double *normal, double *normal_by_receiver)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kWideMaxBasis)
+        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kWideMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    c->linfit_wide_ms[0] = c->linfit_wide_ms[1] = 0.f;
+    const linfit::Wide wd{ nonneg, penalty, penalty_relative ? 1 : 0 };
+    const LinFitCall fit{ K, receiver_weight, anarchy,
+                          linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves }, nullptr, &wd };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+}
 
 int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *c, float ms[3])
 {

@@ -224,13 +224,35 @@ __global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restri
 }
 
 template <int K>
-static void launch(kiwi_hip_ctx *c, int ng, const FftPair *pairs, const double *w_d, int anarchy, double *nbr, double *coef,
-                   double *misfit, int *status, double *pivot, double *normal)
+static void launch_gram(kiwi_hip_ctx *c, int ng, const FftPair *pairs, double *nbr)
 {
     const int nrec = (int)c->recv.size();
     hipLaunchKernelGGL(linfit_gram_kernel<K>, dim3((unsigned)nrec, (unsigned)ng), dim3(kThreads), 0, c->stream, c->proc_d.p, c->syn_stride,
                        c->recv_d.p, c->comps_d.p, c->reft_d.p, c->reffilt_d.p, pairs, c->nmis, nrec, c->syn_factor, c->gm.dt, nbr);
     HIPCHECK(hipGetLastError());
+}
+
+// the Gram kernel alone (the wide fit's for K <= 8: kiwi_linfit_wide.hpp)
+static void launch_gram_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, double *nbr)
+{
+    switch (K) {
+    case 1: launch_gram<1>(c, ng, pairs, nbr); break;
+    case 2: launch_gram<2>(c, ng, pairs, nbr); break;
+    case 3: launch_gram<3>(c, ng, pairs, nbr); break;
+    case 4: launch_gram<4>(c, ng, pairs, nbr); break;
+    case 5: launch_gram<5>(c, ng, pairs, nbr); break;
+    case 6: launch_gram<6>(c, ng, pairs, nbr); break;
+    case 7: launch_gram<7>(c, ng, pairs, nbr); break;
+    default: launch_gram<8>(c, ng, pairs, nbr); break;
+    }
+}
+
+template <int K>
+static void launch(kiwi_hip_ctx *c, int ng, const FftPair *pairs, const double *w_d, int anarchy, double *nbr, double *coef,
+                   double *misfit, int *status, double *pivot, double *normal)
+{
+    const int nrec = (int)c->recv.size();
+    launch_gram<K>(c, ng, pairs, nbr);
     hipLaunchKernelGGL(linfit_solve_kernel<K>, dim3((unsigned)((ng + 63) / 64)), dim3(64), 0, c->stream, nbr, w_d, nrec, anarchy, ng, coef,
                        misfit, status, pivot, normal);
     HIPCHECK(hipGetLastError());
@@ -258,12 +280,14 @@ struct Out {
     int *status;
     double *pivot_min, *normal, *by_receiver, *trace;
     int trace_rows;
+    int *npositive, *nsolves;                       // the wide fit's (kiwi_linfit_wide.hpp), else null
     Out at(int g, int K, int nrec) const
     {
         const size_t nn = (size_t)nn_of(K);
         return Out{ coef + (size_t)g * K, misfit + g, status + g, pivot_min ? pivot_min + g : nullptr,
                     normal ? normal + (size_t)g * nn : nullptr, by_receiver ? by_receiver + (size_t)g * nrec * nn : nullptr,
-                    trace ? trace + (size_t)g * trace_rows * 2 : nullptr, trace_rows };
+                    trace ? trace + (size_t)g * trace_rows * 2 : nullptr, trace_rows, npositive ? npositive + g : nullptr,
+                    nsolves ? nsolves + g : nullptr };
     }
 };
 
@@ -272,11 +296,26 @@ struct Robust { int mode; int niter; double eps; };
 static void robust_launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, const double *nbr,
                               const Robust &rb, double *wbr, double *x, double *misfit, int *status, double *trace);
 
+// the wide fit (kiwi_linfit_wide.hpp) in place of the l2 kernels: up to 64 basis sources, a penalty [K (K + 1) / 2] (host
+// pointer, or null), non-negative coefficients
+struct Wide { int nonneg; const double *penalty; int relative; };
+constexpr int kWideMaxBasis = 64;
+static void wide_launch(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, const Wide &wd,
+                        const double *penalty_d, double *nbr, double *coef, double *misfit, int *status, double *pivot, int *npos,
+                        int *nsol, double *normal, hipEvent_t between);
+
 // what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.
-static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr)
+static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr, const Wide *wd = nullptr)
 {
-    if (K < 1 || K > kMaxBasis)
-        throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(kMaxBasis) + " are supported");
+    const int kmax = wd ? kWideMaxBasis : kMaxBasis;
+    if (K < 1 || K > kmax)
+        throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(kmax) + " are supported");
+    if (wd) {
+        if (wd->nonneg != 0 && wd->nonneg != 1) throw std::runtime_error("linear_fit_wide: nonneg = " + std::to_string(wd->nonneg) + " must be 0 or 1");
+        if (wd->penalty)
+            for (int p = 0; p < K * (K + 1) / 2; p++)
+                if (!std::isfinite(wd->penalty[p])) throw std::runtime_error("linear_fit_wide: penalty entry " + std::to_string(p) + " is not finite");
+    }
     if (!out.coef || !out.misfit || !out.status) throw std::runtime_error("linear_fit: null coef, misfit or status array");
     if (c->method == KIWI_FLOATING_L2NORM || c->method == KIWI_FLOATING_L1NORM)
         throw std::runtime_error("linear_fit: floating shift ranges make the misfit a minimum over shifts, which is not quadratic in the coefficients; set l2norm");
@@ -289,11 +328,11 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb
 }
 
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->linfit_ms.  rb: the reweighting
-// passes of a robust fit behind the l2 solve of every chunk, or null
+// passes of a robust fit behind the l2 solve of every chunk, or null.  wd: the wide fit in place of the l2 kernels, or null
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Out &out,
-                const Robust *rb = nullptr)
+                const Robust *rb = nullptr, const Wide *wd = nullptr)
 {
-    check_setup(c, K, out, rb);
+    check_setup(c, K, out, rb, wd);
     if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
         throw std::runtime_error("linear_fit: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
                                  " are not inside the uploaded batch of " + std::to_string(c->nsrc));
@@ -320,14 +359,19 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
     DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d, wbr_d, trace_d;
     const size_t trace_len = rb ? (size_t)(rb->niter + 1) * 2 : 0;
-    DevBuf<int> st_d;
+    DevBuf<int> st_d, npos_d, nsol_d;
+    DevBuf<double> penalty_d;
     w_d.alloc((size_t)nrec, &c->dev_bytes);
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (wd && wd->penalty) {
+        penalty_d.alloc((size_t)(K * (K + 1) / 2), &c->dev_bytes);
+        HIPCHECK(hipMemcpyAsync(penalty_d.p, wd->penalty, (size_t)(K * (K + 1) / 2) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    }
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 5; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    hipEvent_t ev[6];                                      // (ev[5]: between the Gram and the solve kernels of the wide fit)
+    for (int i = 0; i < 6; i++) ev[i] = c->get_event();
+    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 6; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
     std::vector<double> piv_h;
     int g0 = 0;
     while (g0 < ngroup) {
@@ -354,8 +398,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         st_d.ensure((size_t)ng, &c->dev_bytes);
         if (out.normal) normal_d.ensure((size_t)ng * NN, &c->dev_bytes);
         HIPCHECK(hipMemsetAsync(nbr_d.p, 0, (size_t)ng * nrec * NN * sizeof(double), c->stream));
-        launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, coef_d.p, mis_d.p,
-                   st_d.p, piv_d.p, out.normal ? normal_d.p : (double *)nullptr);
+        if (wd) {
+            npos_d.ensure((size_t)ng, &c->dev_bytes); nsol_d.ensure((size_t)ng, &c->dev_bytes);
+            wide_launch(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, *wd, penalty_d.p, nbr_d.p,
+                        coef_d.p, mis_d.p, st_d.p, piv_d.p, npos_d.p, nsol_d.p, out.normal ? normal_d.p : (double *)nullptr, ev[5]);
+        } else
+            launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, coef_d.p, mis_d.p,
+                       st_d.p, piv_d.p, out.normal ? normal_d.p : (double *)nullptr);
         HIPCHECK(hipEventRecord(ev[2], c->stream));
         if (rb) {
             if (rb->mode == 1) wbr_d.ensure((size_t)ng * nrec * (NN + 2), &c->dev_bytes);
@@ -373,6 +422,10 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             HIPCHECK(hipMemcpyAsync(out.normal + (size_t)g0 * NN, normal_d.p, (size_t)ng * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (out.by_receiver)
             HIPCHECK(hipMemcpyAsync(out.by_receiver + (size_t)g0 * nrec * NN, nbr_d.p, (size_t)ng * nrec * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (wd && out.npositive)
+            HIPCHECK(hipMemcpyAsync(out.npositive + g0, npos_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        if (wd && out.nsolves)
+            HIPCHECK(hipMemcpyAsync(out.nsolves + g0, nsol_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (rb && out.trace)
             HIPCHECK(hipMemcpyAsync(out.trace + (size_t)g0 * trace_len, trace_d.p, (size_t)ng * trace_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[4], c->stream));
@@ -381,6 +434,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             float t = 0.f;
             HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
             c->linfit_ms[i] += t;
+        }
+        if (wd) {
+            float t = 0.f;
+            HIPCHECK(hipEventElapsedTime(&t, ev[1], ev[5]));
+            c->linfit_wide_ms[0] += t;
+            HIPCHECK(hipEventElapsedTime(&t, ev[5], ev[2]));
+            c->linfit_wide_ms[1] += t;
         }
         g0 += ng;
     }
@@ -398,6 +458,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         out.misfit[g] = nan;
         for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
         if (out.trace) std::fill(out.trace + (size_t)g * out.trace_rows * 2, out.trace + (size_t)(g + 1) * out.trace_rows * 2, nan);
+        if (out.npositive) out.npositive[g] = 0;
+        if (out.nsolves) out.nsolves[g] = 0;
     }
 }
 
@@ -410,6 +472,8 @@ static void fill_failed(int ngroup, int K, int nrec, const Out &out)
         out.status[g] = 2; out.misfit[g] = nan;
         for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
         if (out.pivot_min) out.pivot_min[g] = 0.0;
+        if (out.npositive) out.npositive[g] = 0;
+        if (out.nsolves) out.nsolves[g] = 0;
     }
     if (out.trace) std::fill(out.trace, out.trace + (size_t)ngroup * out.trace_rows * 2, nan);
     if (out.normal) std::memset(out.normal, 0, (size_t)ngroup * nn * sizeof(double));

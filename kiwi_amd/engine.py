@@ -19,6 +19,7 @@ NORMS = {"l2norm": 1, "l1norm": 2, "ampspec_l2norm": 3, "ampspec_l1norm": 4, "sc
 
 LinearFit = collections.namedtuple("LinearFit", "coef misfit status pivot_min normal by_receiver")
 RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
+WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
                    ("f", np.float32, 6), ("cl", np.float32), ("sl", np.float32), ("flags", np.int32),
@@ -770,6 +771,80 @@ class Engine:
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_robust_ms(self.h, _fp(ms)), "get_linear_fit_robust_ms")
         return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ wide linear fit (kiwi_hip_linear_fit_wide)
+    def linear_fit_wide_max_basis(self):
+        """The most basis sources per group `linear_fit_wide` takes."""
+        return int(self.L.kiwi_hip_linear_fit_wide_max_basis())
+
+    def linear_fit_wide_ms(self):
+        """HIP-event durations [ms] of the last wide linear fit: (Gram kernels, solve kernel); `linear_fit_ms` has their sum."""
+        ms = np.zeros(2, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_wide_ms(self.h, _fp(ms)), "get_linear_fit_wide_ms")
+        return tuple(float(x) for x in ms)
+
+    def _wide_fit_arrays(self, ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver):
+        K, ngroup = int(K), int(ngroup)
+        if not 1 <= K <= self.linear_fit_wide_max_basis():
+            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_wide_max_basis()))
+        nrec, ng, nn = len(self.components), K * (K + 1) // 2, K * (K + 1) // 2 + K + 1
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        pen = None
+        if penalty is not None:
+            pen = np.ascontiguousarray(penalty, np.float64)
+            if pen.shape == (K, K):
+                if not np.array_equal(pen, pen.T):
+                    raise KiwiHipError("linear_fit_wide: the penalty matrix is not symmetric")
+                pen = np.ascontiguousarray(pen[np.triu_indices(K)])
+            if pen.shape != (ng,):
+                raise KiwiHipError("linear_fit_wide: the penalty must be [K, K] or the upper triangle by rows [K (K + 1) / 2]")
+        out = WideFit(np.zeros((ngroup, K)), np.zeros(ngroup), np.zeros(ngroup, np.int32), np.zeros(ngroup),
+                      np.zeros((ngroup, nn)) if normal else None, np.zeros((ngroup, nrec, nn)) if by_receiver else None,
+                      np.zeros(ngroup, np.int32), np.zeros(ngroup, np.int32))
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        code = nonneg if isinstance(nonneg, (int, np.integer)) and not isinstance(nonneg, bool) else (1 if nonneg else 0)
+        return w, pen, int(code), out, dp
+
+    def linear_fit_wide(self, isrc0, ngroup, K, receiver_weights=None, anarchy=False, nonneg=False, penalty=None,
+                        penalty_relative=False, normal=False, by_receiver=False):
+        """`linear_fit` for up to 64 basis sources per group (kiwi_hip_linear_fit_wide), optionally with a quadratic `penalty`
+        ([K, K] symmetric, or its upper triangle by rows; added to the folded normal matrix as given, or, `penalty_relative`,
+        times the mean of its diagonal) and with non-negative coefficients (`nonneg`: the active-set method of Lawson and
+        Hanson, on the device).  Returns a `WideFit`: the fields of `LinearFit` (misfit: the DATA misfit; normal: the sums
+        without the penalty; status additionally 4: the cap of 3 K solves was reached) plus npositive[ngroup] (coefficients
+        > 0) and nsolves[ngroup] (Cholesky solves made)."""
+        w, pen, code, out, dp = self._wide_fit_arrays(ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver)
+        self._ck(self.L.kiwi_hip_linear_fit_wide(self.h, int(isrc0), int(ngroup), int(K), dp(w), 1 if anarchy else 0, code, dp(pen),
+                                                 1 if penalty_relative else 0, dp(out.coef), dp(out.misfit), _ip(out.status),
+                                                 dp(out.pivot_min), _ip(out.npositive), _ip(out.nsolves), dp(out.normal),
+                                                 dp(out.by_receiver)), "linear_fit_wide")
+        return out
+
+    def linear_fit_wide_params(self, sourcetype, params, K, receiver_weights=None, anarchy=False, nonneg=False, penalty=None,
+                               penalty_relative=False, normal=False, by_receiver=False, piece=0):
+        """`linear_fit_wide` for a parameter list of any length (kiwi_hip_linear_fit_wide_params), cut into pieces and over
+        devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        w, pen, code, out, dp = self._wide_fit_arrays(ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_wide_params(self.h, st, ngroup, K, _fp(p), int(piece), dp(w), 1 if anarchy else 0, code,
+                                                            dp(pen), 1 if penalty_relative else 0, dp(out.coef), dp(out.misfit),
+                                                            _ip(out.status), dp(out.pivot_min), _ip(out.npositive), _ip(out.nsolves),
+                                                            dp(out.normal), dp(out.by_receiver)), "linear_fit_wide")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
 
 
 def bootstrap_draw_weights(nrec, ndraw, rng, receiver_mask=None, receiver_weights=None):

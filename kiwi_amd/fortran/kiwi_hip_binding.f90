@@ -395,6 +395,46 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(4)
         end function
 
+        ! up to 64 basis sources per group, with a penalty and non-negative coefficients (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_linear_fit_wide( ctx, isrc0, ngroup, k, receiver_weight, anarchy, nonneg, penalty, &
+                penalty_relative, coef, misfit, status, pivot_min, npositive, nsolves, normal, normal_by_receiver ) &
+                bind(C, name='kiwi_hip_linear_fit_wide')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, anarchy, nonneg, penalty_relative      ! isrc0 0-based
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            type(c_ptr), value :: penalty                 ! c_loc of real(c_double) (k (k + 1) / 2), or c_null_ptr
+            real(c_double), intent(out) :: coef(*)        ! (k, ngroup)
+            real(c_double), intent(out) :: misfit(*)      ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: pivot_min               ! c_loc of real(c_double) (ngroup), or c_null_ptr
+            type(c_ptr), value :: npositive, nsolves      ! c_loc of integer(c_int) (ngroup), or c_null_ptr
+            type(c_ptr), value :: normal, normal_by_receiver
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_wide_params( ctx, sourcetype, ngroup, k, params, piece, receiver_weight, anarchy, &
+                nonneg, penalty, penalty_relative, coef, misfit, status, pivot_min, npositive, nsolves, normal, &
+                normal_by_receiver ) bind(C, name='kiwi_hip_linear_fit_wide_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, anarchy, nonneg, penalty_relative
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            type(c_ptr), value :: receiver_weight, penalty
+            real(c_double), intent(out) :: coef(*), misfit(*)
+            integer(c_int), intent(out) :: status(*)
+            type(c_ptr), value :: pivot_min, npositive, nsolves, normal, normal_by_receiver
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_wide_max_basis() bind(C, name='kiwi_hip_linear_fit_wide_max_basis')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_wide_ms( ctx, ms ) bind(C, name='kiwi_hip_get_linear_fit_wide_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(2)                 ! Gram kernels, solve kernel
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -140,6 +140,13 @@ def load():
         "kiwi_hip_linear_fit_robust_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int,
                                               C.c_double, c_double_p, c_double_p, c_int_p, c_double_p],
         "kiwi_hip_get_linear_fit_robust_ms": [vp, c_float_p],
+        "kiwi_hip_linear_fit_wide": [vp, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
+                                     c_double_p, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p],
+        "kiwi_hip_linear_fit_wide_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p,
+                                            C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
+                                            c_double_p],
+        "kiwi_hip_linear_fit_wide_max_basis": [],
+        "kiwi_hip_get_linear_fit_wide_ms": [vp, c_float_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],
