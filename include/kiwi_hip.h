@@ -466,6 +466,39 @@ int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *ctx, int sourcetype, int ngrou
 /* HIP-event durations [ms] of the last wide linear fit, which kiwi_hip_get_linear_fit_ms reports as one figure: ms[0] Gram kernels,
  * ms[1] solve kernel (fold, penalty, Cholesky or active-set loop) */
 int kiwi_hip_get_linear_fit_wide_ms(kiwi_hip_ctx *ctx, float ms[2]);
+
+/* ---- misfits in several frequency bands and norms from ONE synthesis (kiwi_bands.hpp).  A band is a misfit method (1 to 6: l2norm,
+ * l1norm, ampspec_l2norm, ampspec_l1norm, scalar_product, peak) plus an optional frequency filter, the same for every receiver as
+ * kiwi_hip_set_filter(ctx, 0, ...) means it; npts[b] == 0: no filter.  x / y: the control points of the bands' filters
+ * concatenated band after band.  nband == 0 removes the bands.  Refused: more than kiwi_hip_misfit_bands_max() bands, a floating
+ * method, a filter of one control point.  Setting bands changes nothing about kiwi_hip_eval and kiwi_hip_get_misfits. */
+int kiwi_hip_misfit_bands_max(void);                       /* 16; answers without a device */
+int kiwi_hip_set_misfit_bands(kiwi_hip_ctx *ctx, int nband, const int *method, const int *npts, const float *x, const float *y);
+int kiwi_hip_get_misfit_bands(kiwi_hip_ctx *ctx, int *nband);
+/* Sources [isrc0, isrc0 + nsrc) of the uploaded batch are synthesised once and compared in every band: misfit and norm
+ * [nsrc][nband][nmis], global [nsrc][nband]; any of them may be NULL.  For every band b the three are bit for bit what
+ * kiwi_hip_get_misfits returns after kiwi_hip_set_filter(ctx, 0, band b's filter) + kiwi_hip_set_misfit_method(ctx, band b's method)
+ * + kiwi_hip_eval with everything else unchanged, whenever the two calls' synthetics are the same bits: always under
+ * KIWI_ARITH_EXACT; under KIWI_ARITH_FUSED a different batch shape may choose a different accumulate kernel instantiation, and the
+ * tolerance of that contract applies, 1e-6 of max(misfit, norm factor).  One exception under either contract: when no source of
+ * the uploaded batch has a rise time, a plain evaluation under an unfiltered time-domain method compares inside the accumulate
+ * kernel, with its fp64 partial sums in another fixed order than the band call's; such a band then agrees with it within 1e-6 of
+ * max(misfit, norm factor), and bit for bit where KIWI_HIP_FUSE=0 makes the plain evaluation use the order the bands use.  The context's own method and filters are not used for the
+ * bands and stay as they are; they are evaluated on the way by the separate comparator kernels, so that kiwi_hip_get_misfits
+ * afterwards returns for the range what a plain kiwi_hip_eval leaves (with the same two provisos) -- never band values.  Sources that
+ * failed to discretise read as zeros.  Refused, nothing approximated: no bands set; an enabled receiver without a taper or
+ * without references; a floating method as the context's own; a range outside the batch; with a band that has a filter or a
+ * spectral method: KIWI_HIP_FUSED_FFT=0, or a (source, slot) pair whose transform length lies outside 64 .. 32768 samples (the
+ * message names the length). */
+int kiwi_hip_band_misfits(kiwi_hip_ctx *ctx, int isrc0, int nsrc, float *misfit, float *norm, float *global);
+/* ... for a parameter list of any length: cut into pieces, the host discretiser overlapped and the list sharded over the devices
+ * of a kiwi_hip_init_multi context exactly as kiwi_hip_misfits_for_params does; status [nsrc] (or NULL) as there.  The results do
+ * not depend on piece, KIWI_HIP_CHUNK_MB, or the number of devices. */
+int kiwi_hip_band_misfits_for_params(kiwi_hip_ctx *ctx, int sourcetype, int nsrc, const float *params, int piece,
+                                     float *misfit, float *norm, float *global, int *status);
+/* HIP-event durations [ms] of the last band call on this context: ms[0] evaluation (geometry, accumulate, the context's own
+ * comparator), ms[1] band kernels (with the reference variants made on the way), ms[2] downloads */
+int kiwi_hip_get_band_misfits_ms(kiwi_hip_ctx *ctx, float ms[3]);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -116,6 +116,24 @@ struct FmmDev {
     }
 };
 
+// A misfit band (kiwi_bands.hpp): a method plus an optional frequency filter that applies to every receiver
+struct BandDef { int method; Plf filter; };
+
+// Reference side of the bands and the workspace of kiwi_hip_band_misfits: tables per (band, slot, transform length), made when a
+// length first occurs and kept until the context is prepared again or the bands change
+struct BandState {
+    bool valid = false, need_spec = false, attr = false;
+    unsigned prepare_gen = 0;
+    int nfilt = 0;
+    std::vector<float> refamp_h, filtw_h, reffilt_h, normtab_h;      // host mirrors (the master copies)
+    std::vector<int2> vtab_h;
+    DevBuf<CompDev> comps_d;
+    DevBuf<float> zmask_d, rows_d, refamp_d, filtw_d, reffilt_d, normtab_d, mis_d, norm_d, glob_d;
+    DevBuf<int2> vtab_d;
+    DevBuf<int> bt_d, ntr_d;
+    DevBuf<FftPair> prs_d;
+};
+
 } // namespace
 
 struct kiwi_hip_ctx {
@@ -236,6 +254,10 @@ struct kiwi_hip_ctx {
     float outer_ms[3] = { 0.f, 0.f, 0.f };            // upload, kernels, download of the last kiwi_hip_outer_misfits (kiwi_outer.hpp)
     float linfit_wide_ms[2] = { 0.f, 0.f };           // Gram kernels, solve kernel of the last wide linear fit (kiwi_linfit_wide.hpp)
     float linfit_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, l2 fit kernels, reweighting passes, download of the last linear fit (kiwi_linfit.hpp)
+    std::vector<BandDef> bands;                       // kiwi_hip_set_misfit_bands (kiwi_bands.hpp)
+    BandState band_state;
+    float bands_ms[3] = { 0.f, 0.f, 0.f };            // evaluation, band kernels, download of the last kiwi_hip_band_misfits
+    unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
 
@@ -375,6 +397,7 @@ void natural_spans(kiwi_hip_ctx *c, std::vector<int> &sb)
 void prepare(kiwi_hip_ctx *c)
 {
     if (c->prepared) return;
+    c->prepare_gen++;
     c->proc_which_held = 0;
     c->evaluated.assign((size_t)c->nsrc, 0);
     if (!c->have_db) throw std::runtime_error("no database set");
@@ -1429,6 +1452,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit.hpp"
 #include "kiwi_linfit_robust.hpp"
 #include "kiwi_linfit_wide.hpp"
+#include "kiwi_bands.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2771,10 +2795,12 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
 // so results do not depend on `piece` (a source's evaluation does not depend on its batch: tests).
 // (kiwi_hip_linear_fit_params goes through the same pieces with `fit` set: the list is then groups of fit->K consecutive basis
 // sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
+// (kiwi_hip_band_misfits_for_params the same with `band` set: a piece is evaluated by bands::run, which fills the band arrays)
 struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; const linfit::Wide *wide; };
+struct BandCall { bands::Out out; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
-                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit)
+                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2782,6 +2808,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (nsrc < 1) throw std::runtime_error("need at least one source");
     HIPCHECK(hipSetDevice(c->device));
     if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust, fit->wide);
+    if (band) bands::check_setup(c);
+    const size_t nband = c->bands.size();
     const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
@@ -2803,15 +2831,17 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const int s0 = bound(i), n = bound(i + 1) - s0;
             const bool fitting = fit != nullptr;
             const LinFitCall mine = fitting ? sub_fit(s0) : LinFitCall{};
+            const bool banding = band != nullptr;
+            const BandCall mine_band = banding ? BandCall{ band->out.at((size_t)s0, nband, nmis) } : BandCall{};
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
-                                       fitting ? &mine : nullptr);
+                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -2938,11 +2968,13 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (norm) std::memset(norm + (size_t)s0 * nmis, 0, (size_t)n * nmis * sizeof(float));
             if (global) std::memset(global + s0, 0, (size_t)n * sizeof(float));
             if (fit) linfit::fill_failed(n / unit, unit, nrec_all, fit->out.at(s0 / unit, unit, nrec_all));
+            if (band) bands::fill_failed((size_t)n, nband, nmis, band->out.at((size_t)s0, nband, nmis));
             continue;
         }
         upload_batch(c, hb);
         const double t_up = now();
         if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust, fit->wide);
+        else if (band) bands::run(c, 0, n, band->out.at((size_t)s0, nband, nmis));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3032,6 +3064,72 @@ int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *c, int sourcetype, int ngroup,
     const LinFitCall fit{ K, receiver_weight, anarchy,
                           linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves }, nullptr, &wd };
     return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+}
+
+// Misfits in several frequency bands and norms from one synthesis (kiwi_bands.hpp)
+int kiwi_hip_misfit_bands_max(void) { return bands::kMaxBands; }
+
+int kiwi_hip_set_misfit_bands(kiwi_hip_ctx *c, int nband, const int *method, const int *npts, const float *x, const float *y)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (nband < 0) return fail(c, "set_misfit_bands: negative number of bands");
+    if (nband > bands::kMaxBands)
+        return fail(c, "set_misfit_bands: " + std::to_string(nband) + " bands; at most " + std::to_string(bands::kMaxBands) + " are supported");
+    if (nband > 0 && (!method || !npts)) return fail(c, "set_misfit_bands: null method or npts array");
+    std::vector<BandDef> bs;
+    size_t ofs = 0;
+    for (int b = 0; b < nband; b++) {
+        if (method[b] == KIWI_FLOATING_L2NORM || method[b] == KIWI_FLOATING_L1NORM)
+            return fail(c, "set_misfit_bands: band " + std::to_string(b + 1) + " asks for a floating norm, which is a minimum over shifts of the unfiltered traces; "
+                           "bands take the methods 1 to 6");
+        if (method[b] < KIWI_L2NORM || method[b] > KIWI_PEAK) return fail(c, "set_misfit_bands: band " + std::to_string(b + 1) + ": unknown misfit method");
+        if (npts[b] < 0 || npts[b] == 1) return fail(c, "set_misfit_bands: band " + std::to_string(b + 1) + ": a filter needs at least two control points");
+        if (npts[b] > 0 && (!x || !y)) return fail(c, "set_misfit_bands: null control points");
+        BandDef bd;
+        bd.method = method[b];
+        if (npts[b] > 0) { bd.filter.x.assign(x + ofs, x + ofs + npts[b]); bd.filter.y.assign(y + ofs, y + ofs + npts[b]); }
+        ofs += (size_t)npts[b];
+        bs.push_back(bd);
+    }
+    c->bands = bs;
+    c->band_state.valid = false;
+    return forward(c, [&](kiwi_hip_ctx *m) { return kiwi_hip_set_misfit_bands(m, nband, method, npts, x, y); });
+}
+
+int kiwi_hip_get_misfit_bands(kiwi_hip_ctx *c, int *nband)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!nband) return fail(c, "null argument");
+    *nband = (int)c->bands.size();
+    return 0;
+}
+
+int kiwi_hip_band_misfits(kiwi_hip_ctx *c, int isrc0, int nsrc, float *misfit, float *norm, float *global)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->bands_ms[0] = c->bands_ms[1] = c->bands_ms[2] = 0.f;
+    bands::run(c, isrc0, nsrc, bands::Out{ misfit, norm, global });
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_band_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece, float *misfit, float *norm,
+                                     float *global, int *status)
+{
+    if (!c) return fail(nullptr, "null context");
+    c->bands_ms[0] = c->bands_ms[1] = c->bands_ms[2] = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) m->bands_ms[0] = m->bands_ms[1] = m->bands_ms[2] = 0.f;
+    const BandCall band{ bands::Out{ misfit, norm, global } };
+    return for_params_impl(c, sourcetype, nsrc, params, piece, nullptr, nullptr, nullptr, status, nullptr, &band);
+}
+
+int kiwi_hip_get_band_misfits_ms(kiwi_hip_ctx *c, float ms[3])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 3; i++) ms[i] = c->bands_ms[i];
+    return 0;
 }
 
 int kiwi_hip_get_linear_fit_ms(kiwi_hip_ctx *c, float ms[3])

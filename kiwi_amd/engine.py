@@ -536,10 +536,16 @@ class Engine:
         except KiwiHipError:
             self.nsrc = 0                  # (a call that fails midway leaves no batch this object may index)
             raise
+        self._hold_head_of_list(N, piece, st, status)
+        return m, n, g, status
+
+    def _hold_head_of_list(self, N, piece, st, status):
         # pieces are evaluated from the end of the list: the context holds the first piece that uploaded anything; with a
         # multi-device engine that is shard 0's (the first device keeps the head of the list)
         # (kiwi_hip_misfits_for_params: a list of ONE source takes the one-device path; otherwise min(N, devices) shards, shard i
         # = [N i / k, N (i + 1) / k))
+        if piece <= 0:
+            piece = 128 if st in (4, 5) else 2048
         ndev = self.ndevices()
         k = 1 if (ndev == 1 or N < 2) else min(N, ndev)
         n0 = N // k
@@ -550,7 +556,79 @@ class Engine:
                 break
         if held:
             self.nsrc = held               # (no piece uploaded anything: the context keeps what it held)
-        return m, n, g, status
+
+    # ------------------------------------------------------------------ misfit bands (kiwi_bands.hpp)
+    def misfit_bands_max(self):
+        """The most bands `set_misfit_bands` takes."""
+        return int(self.L.kiwi_hip_misfit_bands_max())
+
+    def set_misfit_bands(self, bands):
+        """bands: list of (method name, fx, fy) -- a misfit method (l2norm, l1norm, ampspec_l2norm, ampspec_l1norm,
+        scalar_product, peak) and the control points of a frequency filter for every receiver, fx None for no filter.
+        An empty list removes the bands.  eval / get_misfits are not affected."""
+        bands = list(bands)
+        meth, npts, xs, ys = [], [], [], []
+        for b in bands:
+            name, fx, fy = b
+            if not isinstance(name, int) and name not in NORMS:
+                raise KiwiHipError("set_misfit_bands: nok > unknown norm: %s" % name)
+            meth.append(NORMS.get(name, name))
+            fx = [] if fx is None else list(np.asarray(fx, np.float32))
+            fy = [] if fy is None or not len(fx) else list(np.asarray(fy, np.float32))
+            if len(fx) != len(fy):
+                raise KiwiHipError("set_misfit_bands: nok > filter abscissae and ordinates differ in length")
+            npts.append(len(fx))
+            xs += fx
+            ys += fy
+        meth = np.ascontiguousarray(meth, np.int32)
+        npts = np.ascontiguousarray(npts, np.int32)
+        xs = np.ascontiguousarray(xs, np.float32)
+        ys = np.ascontiguousarray(ys, np.float32)
+        self._ck(self.L.kiwi_hip_set_misfit_bands(self.h, len(bands), _ip(meth), _ip(npts), _fp(xs), _fp(ys)), "set_misfit_bands")
+
+    def misfit_bands(self):
+        """Number of bands set."""
+        n = C.c_int()
+        self._ck(self.L.kiwi_hip_get_misfit_bands(self.h, C.byref(n)), "set_misfit_bands")
+        return n.value
+
+    def band_misfits(self, isrc0=0, nsrc=None):
+        """(misfit[nsrc,nband,nmis], norm[nsrc,nband,nmis], global[nsrc,nband]) of uploaded sources from ONE synthesis: band b
+        is what set_misfit_filter(0, ...) + set_misfit_method + eval + get_misfits give with band b's filter and method."""
+        nsrc = self.nsrc - isrc0 if nsrc is None else nsrc
+        nb, nm = self.misfit_bands(), self.nmisfits()
+        m = np.zeros((nsrc, nb, nm), np.float32)
+        n = np.zeros((nsrc, nb, nm), np.float32)
+        g = np.zeros((nsrc, nb), np.float32)
+        self._ck(self.L.kiwi_hip_band_misfits(self.h, isrc0, nsrc, _fp(m), _fp(n), _fp(g)), "band_misfits")
+        return m, n, g
+
+    def band_misfits_for_params(self, sourcetype, params, piece=0):
+        """`band_misfits` for a whole trial list, in pieces and over the devices like misfits_for_params.  Returns
+        (misfit[N,nband,nmis], norm[N,nband,nmis], global[N,nband], failings); the rows of the failings are zeros."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        N, nb, nm = p.shape[0], self.misfit_bands(), self.nmisfits()
+        m = np.zeros((N, nb, nm), np.float32)
+        n = np.zeros((N, nb, nm), np.float32)
+        g = np.zeros((N, nb), np.float32)
+        status = np.zeros(N, np.int32)
+        try:
+            self._ck(self.L.kiwi_hip_band_misfits_for_params(self.h, st, N, _fp(p), piece, _fp(m), _fp(n), _fp(g), _ip(status)),
+                     "band_misfits")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self._hold_head_of_list(N, piece, st, status)
+        return m, n, g, [int(i) for i in np.nonzero(status)[0]]
+
+    def band_misfits_ms(self):
+        """HIP-event durations [ms] of the last band call: (evaluation, band kernels, downloads)."""
+        ms = np.zeros(3, np.float32)
+        self._ck(self.L.kiwi_hip_get_band_misfits_ms(self.h, _fp(ms)), "band_misfits")
+        return tuple(float(x) for x in ms)
 
     def make_misfits_for_sources(self, sourcetype=None, params=None, piece=0):
         """seismosizer.py:682-722: returns (misfits_by_src[N_s,N_r,N_k], norms_by_src[...], failings) -- float64 arrays,

@@ -435,6 +435,49 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(2)                 ! Gram kernels, solve kernel
         end function
 
+        ! misfits in several frequency bands and norms from one synthesis (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_misfit_bands_max() bind(C, name='kiwi_hip_misfit_bands_max')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_set_misfit_bands( ctx, nband, method, npts, x, y ) bind(C, name='kiwi_hip_set_misfit_bands')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: nband                      ! 0 removes the bands
+            integer(c_int), intent(in) :: method(*), npts(*)    ! (nband): method ids 1 to 6; control points of the band's filter, 0 = none
+            real(c_float), intent(in) :: x(*), y(*)             ! control points, band after band
+        end function
+
+        integer(c_int) function kiwi_hip_get_misfit_bands( ctx, nband ) bind(C, name='kiwi_hip_get_misfit_bands')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: nband
+        end function
+
+        integer(c_int) function kiwi_hip_band_misfits( ctx, isrc0, nsrc, misfit, norm, global ) bind(C, name='kiwi_hip_band_misfits')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, nsrc                ! isrc0 0-based
+            type(c_ptr), value :: misfit, norm                  ! c_loc of real(c_float) (nmis, nband, nsrc), or c_null_ptr
+            type(c_ptr), value :: global                        ! c_loc of real(c_float) (nband, nsrc), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_band_misfits_for_params( ctx, sourcetype, nsrc, params, piece, misfit, norm, global, status ) &
+                bind(C, name='kiwi_hip_band_misfits_for_params')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, nsrc, piece
+            real(c_float), intent(in) :: params(*)              ! (nparams, nsrc)
+            type(c_ptr), value :: misfit, norm, global          ! as in kiwi_hip_band_misfits
+            type(c_ptr), value :: status                        ! c_loc of integer(c_int) (nsrc), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_get_band_misfits_ms( ctx, ms ) bind(C, name='kiwi_hip_get_band_misfits_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(3)                 ! evaluation, band kernels, downloads
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -186,3 +186,42 @@ class MisfitGrid:
 
     def get_best_misfit(self):
         return self.ref_misfit if len(self.misfits_by_s) == 0 else float(np.nanmin(self.misfits_by_s))
+
+
+def band_slots_to_receivers(misfit, norm, components, enabled=None):
+    """[N_s, N_b, nmis] arrays of Engine.band_misfits -> [N_s, N_b, N_r, N_k] float64 in the layout of
+    Engine.make_misfits_for_sources: receivers in file order, components in string order, disabled receivers as zeros."""
+    m = np.asarray(misfit, np.float64)
+    n = np.asarray(norm, np.float64)
+    nrec = len(components)
+    enabled = [True] * nrec if enabled is None else list(enabled)
+    nk = max([len(c) for c in components] + [1])
+    mis = np.zeros(m.shape[:2] + (nrec, nk))
+    nor = np.zeros(m.shape[:2] + (nrec, nk))
+    j = 0
+    for ir, comps in enumerate(components):
+        if not enabled[ir]:
+            continue
+        k = len(comps)
+        mis[:, :, ir, :k] = m[:, :, j:j + k]
+        nor[:, :, ir, :k] = n[:, :, j:j + k]
+        j += k
+    return mis, nor
+
+
+def make_band_global_misfits(misfits_by_src, norms_by_src, band_weights=None, outer_norm="l2norm", receiver_weights=None,
+                             anarchy=False):
+    """One outer misfit per source from the misfits of several bands (Engine.band_misfits through band_slots_to_receivers):
+    [N_s, N_b, N_r, N_k] arrays.  Every (band, component) pair counts as a component of its receiver, its misfit and norm
+    factor multiplied by the band's weight (ones by default); the rest is make_global_misfits.  With one band of weight one
+    this IS make_global_misfits.  Returns (global[N_s], misfits per source and receiver [N_s, N_r]).  Host numpy."""
+    m = np.asarray(misfits_by_src, np.float64)
+    n = np.asarray(norms_by_src, np.float64)
+    if m.ndim != 4 or m.shape != n.shape:
+        raise KiwiHipError("make_band_global_misfits: misfits and norms must be [N_s, N_b, N_r, N_k] arrays of one shape")
+    ns, nb, nr, nk = m.shape
+    w = np.ones(nb) if band_weights is None else np.asarray(band_weights, np.float64)
+    if w.shape != (nb,):
+        raise KiwiHipError("make_band_global_misfits: one weight per band")
+    fold = lambda a: np.transpose(a * w[None, :, None, None], (0, 2, 1, 3)).reshape(ns, nr, nb * nk)  # noqa: E731
+    return make_global_misfits(fold(m), fold(n), outer_norm, receiver_weights, anarchy=anarchy)

@@ -147,6 +147,12 @@ def load():
                                             c_double_p],
         "kiwi_hip_linear_fit_wide_max_basis": [],
         "kiwi_hip_get_linear_fit_wide_ms": [vp, c_float_p],
+        "kiwi_hip_misfit_bands_max": [],
+        "kiwi_hip_set_misfit_bands": [vp, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p],
+        "kiwi_hip_get_misfit_bands": [vp, c_int_p],
+        "kiwi_hip_band_misfits": [vp, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p],
+        "kiwi_hip_band_misfits_for_params": [vp, C.c_int, C.c_int, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p, c_int_p],
+        "kiwi_hip_get_band_misfits_ms": [vp, c_float_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],

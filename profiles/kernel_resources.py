@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Register / LDS / spill table of the accumulate kernels, per kernel family and arithmetic contract, and of the outer-misfit
-kernels (kiwi_outer.hpp), from the compiler's own
+kernels (kiwi_outer.hpp) and the misfit-band kernels (kiwi_bands.hpp), from the compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands]"""
 import json
 import os
 import re
@@ -16,7 +16,7 @@ FAMILIES = {1: "direct", 2: "grouped", 3: "multi", 4: "cell"}
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::") for o in out]
+    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::") for o in out]
 
 
 KEYS = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"),
@@ -33,9 +33,10 @@ def collect_outer():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             cur = None
-            if m.group(1).startswith("_ZN5outer"):
-                cur = {"family": "outer", "arith": "exact", "mangled": m.group(1)}
-                rows.append(cur)
+            for prefix, fam in (("_ZN5outer", "outer"), ("_ZN5bands", "bands")):
+                if m.group(1).startswith(prefix):
+                    cur = {"family": fam, "arith": "exact", "mangled": m.group(1)}
+                    rows.append(cur)
             continue
         if cur is None:
             continue
@@ -46,9 +47,9 @@ def collect_outer():
     return rows
 
 
-def collect():
+def collect(only=None):
     rows = []
-    for fam in FAMILIES:
+    for fam in ([] if only else FAMILIES):
         for ar in ("exact", "fused"):
             r = subprocess.run(["make", "-s", "-C", CSRC, "asm", "FAMILY=%d" % fam, "ARITH=%s" % ar], capture_output=True, text=True)
             txt = r.stderr + r.stdout
@@ -68,7 +69,7 @@ def collect():
                     m = re.search(pat, line)
                     if m:
                         cur[key] = int(m.group(1))
-    rows += collect_outer()
+    rows += [r for r in collect_outer() if not only or r["family"] == only]
     names = demangle([r["mangled"] for r in rows])
     for r, n in zip(rows, names):
         r["kernel"] = n
@@ -77,7 +78,8 @@ def collect():
 
 
 def main():
-    rows = collect()
+    only = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--only=")]
+    rows = collect(only[0] if only else None)
     print("| kernel | contract | VGPR | AGPR | SGPR | VGPR spills | SGPR spills | scratch B/lane | LDS B | waves/SIMD |")
     print("|---|---|---|---|---|---|---|---|---|---|")
     for r in rows:
