@@ -499,6 +499,38 @@ int kiwi_hip_band_misfits_for_params(kiwi_hip_ctx *ctx, int sourcetype, int nsrc
 /* HIP-event durations [ms] of the last band call on this context: ms[0] evaluation (geometry, accumulate, the context's own
  * comparator), ms[1] band kernels (with the reference variants made on the way), ms[2] downloads */
 int kiwi_hip_get_band_misfits_ms(kiwi_hip_ctx *ctx, float ms[3]);
+
+/* ---- misfits at many origin times from ONE synthesis (kiwi_timescan.hpp).  Offsets are whole samples, k0 + j kstep for
+ * j = 0 .. nk - 1.  Definition: for an uploaded source s and an integer offset k the scan's misfit is what the comparator gives when
+ * the raw synthetic row of s is read k samples earlier, syn_k[t] = syn_0[t - k] -- the source k dt later -- and everything else is as
+ * in a plain evaluation: rise-time fold, moment, synthetics factor, the receiver's taper at its fixed place, the receiver's filter,
+ * the context's misfit method, the references and the reference variants (transform lengths) of the plain evaluation.  Offset 0 is
+ * the plain evaluation; the norm factors do not depend on the offset.  The scan equals separate evaluations at time + k dt in bits
+ * only where every centroid's time / dt is exact in fp32 (and, with a filter or a spectral method, where the moved source asks for the
+ * same transform length); otherwise the two differ by the rounding of the fractional shift.  As for the bands, an unfiltered
+ * time-domain method of a batch without rise times is compared inside the accumulate kernel by a plain evaluation, in another fixed
+ * order of its fp64 partial sums: the scan then agrees with it within 1e-6 of max(misfit, norm factor), and bit for bit under
+ * KIWI_HIP_FUSE=0; under KIWI_ARITH_FUSED the same 1e-6 applies throughout.
+ * misfit [nsrc][nk][nmis], norm [nsrc][nmis], global [nsrc][nk], best [nsrc]: index j of the smallest global misfit of the source,
+ * the lowest among equal values; any of them may be NULL.  Sources that failed to discretise read as zeros, best = -1.  The rows
+ * are made max |k| samples wider on either side for the duration of the call only: afterwards the context behaves as if the call
+ * had not happened, and kiwi_hip_get_misfits returns for the range what a plain kiwi_hip_eval leaves.  Refused, nothing
+ * approximated: a floating method; an enabled receiver without a taper or without references; a range outside the batch; nk < 1,
+ * nk > kiwi_hip_time_scan_max_offsets(), kstep < 1, an offset beyond kiwi_hip_time_scan_max_shift(); a row (window + 2 x (fold halo
+ * + max |k|)) too long for LDS (the message names the length; INTEGRATION.md, Limits); with a filtered or spectral slot:
+ * KIWI_HIP_FUSED_FFT=0, or a transform length outside 64 .. 32768 samples. */
+int kiwi_hip_time_scan_max_shift(void);                    /* 1024 samples; answers without a device */
+int kiwi_hip_time_scan_max_offsets(void);                  /* 256; answers without a device */
+int kiwi_hip_time_scan(kiwi_hip_ctx *ctx, int isrc0, int nsrc, int k0, int kstep, int nk,
+                       float *misfit, float *norm, float *global, int *best);
+/* ... for a parameter list of any length: pieces, overlapped discretiser and shards of a kiwi_hip_init_multi context exactly as
+ * kiwi_hip_misfits_for_params; status [nsrc] (or NULL) as there.  The results do not depend on piece, KIWI_HIP_CHUNK_MB, or the
+ * number of devices. */
+int kiwi_hip_time_scan_for_params(kiwi_hip_ctx *ctx, int sourcetype, int nsrc, const float *params, int piece, int k0, int kstep, int nk,
+                                  float *misfit, float *norm, float *global, int *best, int *status);
+/* HIP-event durations [ms] of the last scan call on this context: ms[0] evaluation (geometry, accumulate, the context's own
+ * comparator), ms[1] scan kernels, ms[2] downloads */
+int kiwi_hip_get_time_scan_ms(kiwi_hip_ctx *ctx, float ms[3]);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -134,6 +134,13 @@ struct BandState {
     DevBuf<FftPair> prs_d;
 };
 
+// Workspace of kiwi_hip_time_scan (kiwi_timescan.hpp)
+struct TimeScanState {
+    bool attr = false;
+    DevBuf<float> mis_d, norm_d, glob_d;
+    DevBuf<int> best_d;
+};
+
 } // namespace
 
 struct kiwi_hip_ctx {
@@ -173,6 +180,7 @@ struct kiwi_hip_ctx {
     int halo = 0;
     size_t syn_stride = 0;
     std::vector<CompDev> comps;
+    std::vector<RecvDev> recv_h;          // host copy of recv_d (kiwi_timescan.hpp lays the rows out again for a wider halo)
     std::vector<float> norm_h;
     std::vector<float> reft_h;            // tapered references over the windows (host copy)
     DevBuf<RecvDev> recv_d;
@@ -257,6 +265,8 @@ struct kiwi_hip_ctx {
     std::vector<BandDef> bands;                       // kiwi_hip_set_misfit_bands (kiwi_bands.hpp)
     BandState band_state;
     float bands_ms[3] = { 0.f, 0.f, 0.f };            // evaluation, band kernels, download of the last kiwi_hip_band_misfits
+    TimeScanState timescan_state;
+    float timescan_ms[3] = { 0.f, 0.f, 0.f };         // evaluation, scan kernels, downloads of the last kiwi_hip_time_scan
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
@@ -587,6 +597,7 @@ void prepare(kiwi_hip_ctx *c)
     HIPCHECK(hipMemcpyAsync(c->norm_d.p, c->norm_h.data(), c->norm_h.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(c->recfirst_d.p, recfirst.data(), recfirst.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));      // host vectors go out of scope
+    c->recv_h = rd;
     if (c->nsrc > 0) {
         c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
         c->global_d.ensure((size_t)c->nsrc, &c->dev_bytes);
@@ -1453,6 +1464,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_robust.hpp"
 #include "kiwi_linfit_wide.hpp"
 #include "kiwi_bands.hpp"
+#include "kiwi_timescan.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2797,10 +2809,13 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
 // sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
 // (kiwi_hip_band_misfits_for_params the same with `band` set: a piece is evaluated by bands::run, which fills the band arrays)
 struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; const linfit::Wide *wide; };
+// (kiwi_hip_time_scan_for_params the same with `scan` set: a piece is evaluated by timescan::run, which fills the scan arrays)
 struct BandCall { bands::Out out; };
+struct ScanCall { timescan::Out out; timescan::Offsets of; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
-                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr)
+                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
+                           const ScanCall *scan = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2809,6 +2824,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     HIPCHECK(hipSetDevice(c->device));
     if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust, fit->wide);
     if (band) bands::check_setup(c);
+    if (scan) timescan::check_setup(c, scan->of.k0, scan->of.kstep, scan->of.nk);
     const size_t nband = c->bands.size();
     const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
@@ -2833,15 +2849,17 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const LinFitCall mine = fitting ? sub_fit(s0) : LinFitCall{};
             const bool banding = band != nullptr;
             const BandCall mine_band = banding ? BandCall{ band->out.at((size_t)s0, nband, nmis) } : BandCall{};
+            const bool scanning = scan != nullptr;
+            const ScanCall mine_scan = scanning ? ScanCall{ scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis), scan->of } : ScanCall{};
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
-                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr);
+                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -2969,12 +2987,14 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (global) std::memset(global + s0, 0, (size_t)n * sizeof(float));
             if (fit) linfit::fill_failed(n / unit, unit, nrec_all, fit->out.at(s0 / unit, unit, nrec_all));
             if (band) bands::fill_failed((size_t)n, nband, nmis, band->out.at((size_t)s0, nband, nmis));
+            if (scan) timescan::fill_failed((size_t)n, (size_t)scan->of.nk, nmis, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
             continue;
         }
         upload_batch(c, hb);
         const double t_up = now();
         if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust, fit->wide);
         else if (band) bands::run(c, 0, n, band->out.at((size_t)s0, nband, nmis));
+        else if (scan) timescan::run(c, 0, n, scan->of, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3129,6 +3149,38 @@ int kiwi_hip_get_band_misfits_ms(kiwi_hip_ctx *c, float ms[3])
     if (!c) return fail(nullptr, "null context");
     if (!ms) return fail(c, "null argument");
     for (int i = 0; i < 3; i++) ms[i] = c->bands_ms[i];
+    return 0;
+}
+
+// Misfits at many origin times from one synthesis (kiwi_timescan.hpp)
+int kiwi_hip_time_scan_max_shift(void) { return timescan::kMaxShift; }
+int kiwi_hip_time_scan_max_offsets(void) { return timescan::kMaxOffsets; }
+
+int kiwi_hip_time_scan(kiwi_hip_ctx *c, int isrc0, int nsrc, int k0, int kstep, int nk, float *misfit, float *norm, float *global, int *best)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->timescan_ms[0] = c->timescan_ms[1] = c->timescan_ms[2] = 0.f;
+    timescan::run(c, isrc0, nsrc, timescan::Offsets{ k0, kstep, nk }, timescan::Out{ misfit, norm, global, best });
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_time_scan_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece, int k0, int kstep, int nk,
+                                  float *misfit, float *norm, float *global, int *best, int *status)
+{
+    if (!c) return fail(nullptr, "null context");
+    c->timescan_ms[0] = c->timescan_ms[1] = c->timescan_ms[2] = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) m->timescan_ms[0] = m->timescan_ms[1] = m->timescan_ms[2] = 0.f;
+    const ScanCall scan{ timescan::Out{ misfit, norm, global, best }, timescan::Offsets{ k0, kstep, nk } };
+    return for_params_impl(c, sourcetype, nsrc, params, piece, nullptr, nullptr, nullptr, status, nullptr, nullptr, &scan);
+}
+
+int kiwi_hip_get_time_scan_ms(kiwi_hip_ctx *c, float ms[3])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 3; i++) ms[i] = c->timescan_ms[i];
     return 0;
 }
 

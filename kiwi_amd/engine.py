@@ -630,6 +630,48 @@ class Engine:
         self._ck(self.L.kiwi_hip_get_band_misfits_ms(self.h, _fp(ms)), "band_misfits")
         return tuple(float(x) for x in ms)
 
+    # ------------------------------------------------------------------ time scan (kiwi_timescan.hpp)
+    def time_scan(self, isrc0=0, nsrc=None, k0=0, kstep=1, nk=1):
+        """(misfit[nsrc,nk,nmis], norm[nsrc,nmis], global[nsrc,nk], best[nsrc]) of uploaded sources at the origin-time offsets
+        (k0 + j kstep) dt, j < nk, from ONE synthesis: the raw synthetic read k samples earlier, everything else as eval +
+        get_misfits do it (include/kiwi_hip.h).  best: the offset index of the smallest global misfit, -1 for a failing."""
+        nsrc = self.nsrc - isrc0 if nsrc is None else nsrc
+        nk_, nm = max(int(nk), 0), self.nmisfits()
+        m = np.zeros((nsrc, nk_, nm), np.float32)
+        n = np.zeros((nsrc, nm), np.float32)
+        g = np.zeros((nsrc, nk_), np.float32)
+        b = np.zeros(nsrc, np.int32)
+        self._ck(self.L.kiwi_hip_time_scan(self.h, isrc0, nsrc, int(k0), int(kstep), int(nk), _fp(m), _fp(n), _fp(g), _ip(b)), "time_scan")
+        return m, n, g, b
+
+    def time_scan_for_params(self, sourcetype, params, k0=0, kstep=1, nk=1, piece=0):
+        """`time_scan` for a whole trial list, in pieces and over the devices like misfits_for_params.  Returns
+        (misfit[N,nk,nmis], norm[N,nmis], global[N,nk], best[N], failings); the rows of the failings are zeros, their best -1."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        N, nk_, nm = p.shape[0], max(int(nk), 0), self.nmisfits()
+        m = np.zeros((N, nk_, nm), np.float32)
+        n = np.zeros((N, nm), np.float32)
+        g = np.zeros((N, nk_), np.float32)
+        b = np.zeros(N, np.int32)
+        status = np.zeros(N, np.int32)
+        try:
+            self._ck(self.L.kiwi_hip_time_scan_for_params(self.h, st, N, _fp(p), piece, int(k0), int(kstep), int(nk), _fp(m), _fp(n),
+                                                          _fp(g), _ip(b), _ip(status)), "time_scan")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self._hold_head_of_list(N, piece, st, status)
+        return m, n, g, b, [int(i) for i in np.nonzero(status)[0]]
+
+    def time_scan_ms(self):
+        """HIP-event durations [ms] of the last scan call: (evaluation, scan kernels, downloads)."""
+        ms = np.zeros(3, np.float32)
+        self._ck(self.L.kiwi_hip_get_time_scan_ms(self.h, _fp(ms)), "time_scan")
+        return tuple(float(x) for x in ms)
+
     def make_misfits_for_sources(self, sourcetype=None, params=None, piece=0):
         """seismosizer.py:682-722: returns (misfits_by_src[N_s,N_r,N_k], norms_by_src[...], failings) -- float64 arrays,
         receivers in file order, components in string order, disabled receivers as zeros; `failings` lists the indices of

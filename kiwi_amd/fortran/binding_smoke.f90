@@ -23,6 +23,9 @@ program binding_smoke
     end do
     print '(a,i6,a,f10.6,a,f8.3)', 'ncent ', ncent, ' sum_mxx ', msum, ' moment ', moment
 
+    ! the limits of kiwi_hip_time_scan answer without a device
+    if (kiwi_hip_time_scan_max_shift() /= 1024 .or. kiwi_hip_time_scan_max_offsets() /= 256) stop 4
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

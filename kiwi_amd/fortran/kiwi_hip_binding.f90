@@ -478,6 +478,44 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(3)                 ! evaluation, band kernels, downloads
         end function
 
+        ! misfits at many origin times from one synthesis (kiwi_hip.h): offsets k0 + j kstep, j = 0 .. nk - 1, in samples
+        integer(c_int) function kiwi_hip_time_scan_max_shift() bind(C, name='kiwi_hip_time_scan_max_shift')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_time_scan_max_offsets() bind(C, name='kiwi_hip_time_scan_max_offsets')
+            import :: c_int
+        end function
+
+        integer(c_int) function kiwi_hip_time_scan( ctx, isrc0, nsrc, k0, kstep, nk, misfit, norm, global, best ) &
+                bind(C, name='kiwi_hip_time_scan')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, nsrc                ! isrc0 0-based
+            integer(c_int), value :: k0, kstep, nk
+            type(c_ptr), value :: misfit                        ! c_loc of real(c_float) (nmis, nk, nsrc), or c_null_ptr
+            type(c_ptr), value :: norm                          ! c_loc of real(c_float) (nmis, nsrc), or c_null_ptr
+            type(c_ptr), value :: global                        ! c_loc of real(c_float) (nk, nsrc), or c_null_ptr
+            type(c_ptr), value :: best                          ! c_loc of integer(c_int) (nsrc): 0-based offset index, -1 for a failing; or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_time_scan_for_params( ctx, sourcetype, nsrc, params, piece, k0, kstep, nk, misfit, norm, global, &
+                                                               best, status ) bind(C, name='kiwi_hip_time_scan_for_params')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, nsrc, piece
+            real(c_float), intent(in) :: params(*)              ! (nparams, nsrc)
+            integer(c_int), value :: k0, kstep, nk
+            type(c_ptr), value :: misfit, norm, global, best    ! as in kiwi_hip_time_scan
+            type(c_ptr), value :: status                        ! c_loc of integer(c_int) (nsrc), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_get_time_scan_ms( ctx, ms ) bind(C, name='kiwi_hip_get_time_scan_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(3)                 ! evaluation, scan kernels, downloads
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -62,6 +62,26 @@ def source_grid(sourcetype, base_params, grid_definition, source_constraints=Non
     return out.astype(np.float32)
 
 
+def split_time_axis(values, dt):
+    """(k0, kstep, nk) when the time axis `values` is evenly spaced by a whole number of samples of `dt` -- (v - v[0]) / dt is an
+    integer in fp32 for every value, checked exactly, the integers ascending in equal steps --, so that Engine.time_scan at
+    values[0] covers it; None otherwise.  A single value: (0, 1, 1)."""
+    v = np.asarray(values, np.float32).ravel()
+    if v.size == 0:
+        return None
+    q = (v - v[0]) / np.float32(dt)                       # fp32 throughout, as the engine takes its times
+    k = np.rint(q)
+    if not np.all(np.isfinite(q)) or np.any(q != k) or np.any(np.abs(k) > 2 ** 24):
+        return None
+    k = k.astype(np.int64)
+    if v.size == 1:
+        return 0, 1, 1
+    step = int(k[1] - k[0])
+    if step < 1 or np.any(np.diff(k) != step):
+        return None
+    return 0, step, int(v.size)
+
+
 class MisfitGridStats:
     """gridsearch.py:45-105 (the numbers, not the plots)."""
 
@@ -94,7 +114,42 @@ class MisfitGrid:
         self.best_source = self.misfits_by_s = self.misfits_by_r = self.variability_by_r = None
         self.bootstrap_sources = self.stats = None
 
-    def compute(self, engine, dist=None, device=0, linear_mt=False, outer_norm="l2norm", niter=8, eps=1e-3):
+    def _compute_time_scan(self, engine, dt):
+        """The grid's misfits from one synthesis per node of the grid WITHOUT its time axis, at the axis's first value, and a
+        scan of the axis (Engine.time_scan_for_params); the same arrays in the same order as the plain evaluation fills."""
+        axes = [i for i, (p, _) in enumerate(self.param_values) if p == "time"]
+        if len(axes) != 1:
+            raise ValueError("time_scan: the grid needs exactly one `time` axis")
+        ax = axes[0]
+        split = split_time_axis(self.param_values[ax][1], engine.dt if dt is None else dt)
+        if split is None:
+            raise ValueError("time_scan: the time axis is not evenly spaced by a whole number of samples")
+        k0, kstep, nk = split
+        dims = [len(v) for _, v in self.param_values]
+        if int(np.prod(dims)) != len(self.sources):
+            raise ValueError("time_scan: source constraints have switched grid nodes off; the scan needs the full grid")
+        idx = np.arange(len(self.sources)).reshape(dims)
+        first = np.take(idx, 0, axis=ax).ravel()                       # nodes at the axis's first value, grid order
+        m, n, _, _, failings = engine.time_scan_for_params(self.sourcetype, self.sources[first], k0, kstep, nk)
+        nrec = len(engine.components)
+        ncomp = max([len(c) for c in engine.components] + [1])
+        mis = np.zeros((len(self.sources), nrec, ncomp))
+        nor = np.zeros((len(self.sources), nrec, ncomp))
+        where = np.moveaxis(idx, ax, -1).reshape(len(first), nk)        # [node without time][offset] -> grid index
+        j = 0
+        for ir, comps in enumerate(engine.components):
+            if not engine.enabled[ir]:
+                continue
+            k = len(comps)
+            mis[where, ir, :k] = m[:, :, j:j + k]
+            nor[where, ir, :k] = n[:, None, j:j + k]
+            j += k
+        self.syntheses_saved = len(self.sources) - len(first)
+        self.misfits_by_src, self.norms_by_src = mis, nor
+        self.failings = sorted(int(i) for f in failings for i in where[f])
+
+    def compute(self, engine, dist=None, device=0, linear_mt=False, outer_norm="l2norm", niter=8, eps=1e-3, time_scan=False,
+                dt=None):
         """Trace misfits for every grid node (and the reference source), `engine` = kiwi_amd.Engine set up for
         the inversion.  With a torch.distributed group the grid is sharded over the ranks (kiwi_amd/shard.py).
         linear_mt=True (`moment_tensor`, `mt_eikonal`; l2norm): the grid runs over the OTHER parameters and every node gets
@@ -103,7 +158,15 @@ class MisfitGrid:
         `best_source` and `misfits_by_s` from the fit.  The fitted sources are then evaluated like any grid, so that
         `postprocess` (bootstrap over the receivers) works on them unchanged.  outer_norm="l1norm" (or an engine whose misfit
         method is l1norm) fits the tensors robustly, `niter` reweighted solves with the relative bound `eps`
-        (`mtfit.fit_moment_tensors`); a node whose reweighting broke down (status 3) keeps the tensor it reached."""
+        (`mtfit.fit_moment_tensors`); a node whose reweighting broke down (status 3) keeps the tensor it reached.
+        time_scan=True: the grid has a `time` axis evenly spaced by whole samples (`split_time_axis`; `dt`: the database's
+        sampling interval, default engine.dt); the grid without that axis is synthesised once at the axis's first value and the
+        axis is scanned (Engine.time_scan_for_params).  The same arrays in the same order; `syntheses_saved` counts what was
+        not synthesised.  ValueError where the axis does not split, and when combined with linear_mt."""
+        if time_scan and linear_mt:
+            raise ValueError("time_scan cannot be combined with linear_mt")
+        if time_scan and dist is not None:
+            raise ValueError("time_scan: a sharded scan is the caller's split of the grid without its time axis")
         self.receiver_mask = np.array(engine.enabled, bool)
         self.nreceivers = len(engine.components)
         self.ncomponents = [len(c) for c in engine.components]
@@ -118,7 +181,9 @@ class MisfitGrid:
                 engine, self.sourcetype, self.sources, outer_norm=outer_norm, niter=niter, eps=eps)
             solved = (self.fit_status == 0) | (self.fit_status == 3)
             self.sources[solved, c0:c0 + 6] = self.fitted_tensors[solved].astype(np.float32)
-        if len(self.sources):
+        if time_scan and len(self.sources):
+            self._compute_time_scan(engine, dt)
+        elif len(self.sources):
             if dist is not None:
                 from .shard import sharded_misfits_for_sources
                 self.misfits_by_src, self.norms_by_src, self.failings = sharded_misfits_for_sources(

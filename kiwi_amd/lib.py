@@ -153,6 +153,12 @@ def load():
         "kiwi_hip_band_misfits": [vp, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p],
         "kiwi_hip_band_misfits_for_params": [vp, C.c_int, C.c_int, c_float_p, C.c_int, c_float_p, c_float_p, c_float_p, c_int_p],
         "kiwi_hip_get_band_misfits_ms": [vp, c_float_p],
+        "kiwi_hip_time_scan_max_shift": [],
+        "kiwi_hip_time_scan_max_offsets": [],
+        "kiwi_hip_time_scan": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_int_p],
+        "kiwi_hip_time_scan_for_params": [vp, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                          c_float_p, c_int_p, c_int_p],
+        "kiwi_hip_get_time_scan_ms": [vp, c_float_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],
