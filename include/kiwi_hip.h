@@ -531,6 +531,48 @@ int kiwi_hip_time_scan_for_params(kiwi_hip_ctx *ctx, int sourcetype, int nsrc, c
 /* HIP-event durations [ms] of the last scan call on this context: ms[0] evaluation (geometry, accumulate, the context's own
  * comparator), ms[1] scan kernels, ms[2] downloads */
 int kiwi_hip_get_time_scan_ms(kiwi_hip_ctx *ctx, float ms[3]);
+/* ---- the linear fit at many origin times from ONE synthesis of the basis (kiwi_amd/csrc/kiwi_linfit_timescan.hpp): the best
+ * coefficients of every group at every offset k0 + j kstep, j < nk -- with six elementary tensors per group, a free moment tensor at
+ * every (location, origin time) node from six syntheses per location.  Groups are kiwi_hip_linear_fit's: K consecutive basis sources,
+ * 1 <= K <= kiwi_hip_linear_fit_max_basis().  Offsets are kiwi_hip_time_scan's, with its limits kiwi_hip_time_scan_max_offsets() and
+ * kiwi_hip_time_scan_max_shift().  Definition: for group g and offset k, basis source i has row_i = its folded, moment-scaled,
+ * untapered synthetic, and over the receiver's window
+ *     s_{i,k}[t] = fp32(syn_factor x fp32(row_i[t - k] x taper[t]))
+ * -- the source k dt later, under the receiver's taper at its fixed place --; d[t] is the tapered reference.  G_r(k), b_r(k), R_r
+ * (which does not depend on k), the layout NN = K (K + 1) / 2 + K + 1, the fold over the receivers (receiver_weight, anarchy), the
+ * scaling, the Cholesky, the pivot test, the misfit formula and the statuses 0 / 1 / 2 are exactly kiwi_hip_linear_fit's.
+ *   coef       [ngroup][nk][K]       misfit  [ngroup][nk]       status  [ngroup][nk]
+ *   pivot_min  [ngroup][nk] or NULL
+ *   best       [ngroup] or NULL: the index j of the smallest misfit[g][j] among the offsets with status 0, the lowest index among
+ *                           equal values; -1 when no offset is solved
+ *   normal     [ngroup][nk][NN] or NULL: the weighted sums G, b, R (unscaled)
+ * A group with a basis source that failed to discretise has status 2 and NaN at every offset, best = -1.
+ * Equalities: offset 0 is kiwi_hip_linear_fit bit for bit (same kept sample, same summation order).  Offset k is bit for bit
+ * kiwi_hip_linear_fit on a context whose references and tapers are moved by -k samples.  Offset k equals a fit of the sources moved to
+ * time + k dt in bits only where every centroid's time / dt is exact in fp32; otherwise the two differ by the rounding of the
+ * fractional shift.  (Always under KIWI_ARITH_EXACT; under KIWI_ARITH_FUSED two calls' synthetics may come from different accumulate
+ * kernel instantiations, and the answers then agree within that contract's 1e-6 of the traces times the condition number of G.)
+ * Every sum has a fixed order: the answer does not depend on nk's split into passes, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or
+ * the number of devices.  The rows are made max |k| samples wider for the duration of the call only, as by kiwi_hip_time_scan:
+ * afterwards the context behaves as if the call had not happened, and kiwi_hip_get_misfits returns for the basis sources what a
+ * plain kiwi_hip_eval leaves.  There is no limit on the window length.
+ * Refused, nothing approximated: everything kiwi_hip_linear_fit refuses; everything kiwi_hip_time_scan refuses about nk, kstep and
+ * the offsets; an enabled receiver with a misfit filter (the taper sits in front of the filter, so every basis source and offset
+ * would need a transform of its own).  There is no robust, wide or per-receiver-shift form and no normal_by_receiver. */
+int kiwi_hip_linear_fit_time_scan(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int k0, int kstep, int nk,
+                                  const double *receiver_weight, int anarchy, double *coef, double *misfit, int *status,
+                                  double *pivot_min, int *best, double *normal);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_time_scan_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                         int k0, int kstep, int nk, const double *receiver_weight, int anarchy, double *coef,
+                                         double *misfit, int *status, double *pivot_min, int *best, double *normal);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram-scan kernel, ms[2] solve kernels,
+ * ms[3] downloads */
+int kiwi_hip_get_linear_fit_time_scan_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the Gram-scan kernel walks its work for K basis sources: *per_pass offsets per workgroup (their accumulators are registers),
+ * *tile window samples per LDS tile; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_linear_fit_time_scan_shape(int K, int *per_pass, int *tile);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

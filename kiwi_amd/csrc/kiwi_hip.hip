@@ -267,6 +267,8 @@ struct kiwi_hip_ctx {
     float bands_ms[3] = { 0.f, 0.f, 0.f };            // evaluation, band kernels, download of the last kiwi_hip_band_misfits
     TimeScanState timescan_state;
     float timescan_ms[3] = { 0.f, 0.f, 0.f };         // evaluation, scan kernels, downloads of the last kiwi_hip_time_scan
+    float linfit_timescan_ms[4] = { 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, downloads of the last kiwi_hip_linear_fit_time_scan
+    unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
     mutable FmmDev fmm;                               // (used by discretise_batch, which reads the context only)
@@ -1465,6 +1467,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_wide.hpp"
 #include "kiwi_bands.hpp"
 #include "kiwi_timescan.hpp"
+#include "kiwi_linfit_timescan.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2812,10 +2815,13 @@ struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; c
 // (kiwi_hip_time_scan_for_params the same with `scan` set: a piece is evaluated by timescan::run, which fills the scan arrays)
 struct BandCall { bands::Out out; };
 struct ScanCall { timescan::Out out; timescan::Offsets of; };
+// (kiwi_hip_linear_fit_time_scan_params the same with `fitscan` set: groups of K basis sources as for `fit`, a piece is evaluated by
+// linfit_timescan::run)
+struct FitScanCall { int K; const double *weight; int anarchy; linfit_timescan::Out out; timescan::Offsets of; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
-                           const ScanCall *scan = nullptr)
+                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2825,8 +2831,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust, fit->wide);
     if (band) bands::check_setup(c);
     if (scan) timescan::check_setup(c, scan->of.k0, scan->of.kstep, scan->of.nk);
+    if (fitscan) linfit_timescan::check_setup(c, fitscan->K, fitscan->of, fitscan->out);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : 1;             // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : 1;             // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2851,15 +2858,19 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const BandCall mine_band = banding ? BandCall{ band->out.at((size_t)s0, nband, nmis) } : BandCall{};
             const bool scanning = scan != nullptr;
             const ScanCall mine_scan = scanning ? ScanCall{ scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis), scan->of } : ScanCall{};
+            const bool fitscanning = fitscan != nullptr;
+            FitScanCall mine_fitscan{};
+            if (fitscanning) { mine_fitscan = *fitscan; mine_fitscan.out = fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
-                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr);
+                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
+                                       fitscanning ? &mine_fitscan : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -2988,6 +2999,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (fit) linfit::fill_failed(n / unit, unit, nrec_all, fit->out.at(s0 / unit, unit, nrec_all));
             if (band) bands::fill_failed((size_t)n, nband, nmis, band->out.at((size_t)s0, nband, nmis));
             if (scan) timescan::fill_failed((size_t)n, (size_t)scan->of.nk, nmis, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
+            if (fitscan) linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)fitscan->of.nk,
+                                                      fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
             continue;
         }
         upload_batch(c, hb);
@@ -2995,6 +3008,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust, fit->wide);
         else if (band) bands::run(c, 0, n, band->out.at((size_t)s0, nband, nmis));
         else if (scan) timescan::run(c, 0, n, scan->of, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
+        else if (fitscan) linfit_timescan::run(c, 0, n / unit, unit, fitscan->of, fitscan->weight, fitscan->anarchy,
+                                               fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3181,6 +3196,50 @@ int kiwi_hip_get_time_scan_ms(kiwi_hip_ctx *c, float ms[3])
     if (!c) return fail(nullptr, "null context");
     if (!ms) return fail(c, "null argument");
     for (int i = 0; i < 3; i++) ms[i] = c->timescan_ms[i];
+    return 0;
+}
+
+// The linear fit at many origin times from one synthesis of the basis (kiwi_linfit_timescan.hpp)
+int kiwi_hip_linear_fit_time_scan(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int k0, int kstep, int nk, const double *receiver_weight,
+                                  int anarchy, double *coef, double *misfit, int *status, double *pivot_min, int *best, double *normal)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->linfit_timescan_ms) t = 0.f;
+    linfit_timescan::run(c, isrc0, ngroup, K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy,
+                         linfit_timescan::Out{ coef, misfit, status, pivot_min, best, normal });
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_time_scan_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int k0, int kstep,
+                                         int nk, const double *receiver_weight, int anarchy, double *coef, double *misfit, int *status,
+                                         double *pivot_min, int *best, double *normal)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->linfit_timescan_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_timescan_ms) t = 0.f;
+    const FitScanCall fitscan{ K, receiver_weight, anarchy, linfit_timescan::Out{ coef, misfit, status, pivot_min, best, normal },
+                               timescan::Offsets{ k0, kstep, nk } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fitscan);
+}
+
+int kiwi_hip_linear_fit_time_scan_shape(int K, int *per_pass, int *tile)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !per_pass || !tile) return 1;
+    *per_pass = linfit_timescan::kPerPass[K];
+    *tile = linfit_timescan::kTile;
+    return 0;
+}
+
+int kiwi_hip_get_linear_fit_time_scan_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->linfit_timescan_ms[i];
     return 0;
 }
 

@@ -19,6 +19,7 @@ NORMS = {"l2norm": 1, "l1norm": 2, "ampspec_l2norm": 3, "ampspec_l1norm": 4, "sc
 
 LinearFit = collections.namedtuple("LinearFit", "coef misfit status pivot_min normal by_receiver")
 RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
+ScanFit = collections.namedtuple("ScanFit", "coef misfit status pivot_min best normal")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -838,6 +839,64 @@ class Engine:
         """HIP-event durations [ms] of the last linear fit: (evaluation, fit kernels, downloads)."""
         ms = np.zeros(3, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_ms(self.h, _fp(ms)), "get_linear_fit_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ linear fit at many origin times (kiwi_hip_linear_fit_time_scan)
+    def linear_fit_time_scan_shape(self, K):
+        """(offsets per workgroup, window samples per LDS tile) of the Gram-scan kernel for K basis sources."""
+        j, t = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_linear_fit_time_scan_shape(int(K), _ip(j), _ip(t)):
+            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(j[0]), int(t[0])
+
+    def _scan_fit_arrays(self, ngroup, K, nk, receiver_weights, normal):
+        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
+        ngroup, K, nk_ = int(ngroup), int(K), max(int(nk), 0)
+        nn = K * (K + 1) // 2 + K + 1
+        out = ScanFit(np.zeros((ngroup, nk_, K)), np.zeros((ngroup, nk_)), np.zeros((ngroup, nk_), np.int32), np.zeros((ngroup, nk_)),
+                      np.zeros(ngroup, np.int32), np.zeros((ngroup, nk_, nn)) if normal else None)
+        return w, out, dp
+
+    def linear_fit_time_scan(self, isrc0, ngroup, K, k0=0, kstep=1, nk=1, receiver_weights=None, anarchy=False, normal=False):
+        """`linear_fit` at the origin-time offsets (k0 + j kstep) dt, j < nk, from ONE synthesis of the basis sources
+        (kiwi_hip_linear_fit_time_scan): the basis synthetics read k samples earlier under the receivers' tapers at their fixed
+        places.  Returns a `ScanFit`: coef[ngroup, nk, K], misfit[ngroup, nk], status[ngroup, nk], pivot_min[ngroup, nk],
+        best[ngroup] (the offset index of the smallest misfit among the solved offsets, -1 if there is none) and on request
+        normal[ngroup, nk, NN].  Offset 0 is `linear_fit` bit for bit."""
+        w, out, dp = self._scan_fit_arrays(ngroup, K, nk, receiver_weights, normal)
+        self._ck(self.L.kiwi_hip_linear_fit_time_scan(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), dp(w),
+                                                      1 if anarchy else 0, dp(out.coef), dp(out.misfit), _ip(out.status),
+                                                      dp(out.pivot_min), _ip(out.best), dp(out.normal)), "linear_fit_time_scan")
+        return out
+
+    def linear_fit_time_scan_params(self, sourcetype, params, K, k0=0, kstep=1, nk=1, receiver_weights=None, anarchy=False, normal=False,
+                                    piece=0):
+        """`linear_fit_time_scan` for a parameter list of any length, cut into pieces and over the devices at group boundaries as
+        `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        w, out, dp = self._scan_fit_arrays(ngroup, K, nk, receiver_weights, normal)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep), int(nk),
+                                                                 dp(w), 1 if anarchy else 0, dp(out.coef), dp(out.misfit),
+                                                                 _ip(out.status), dp(out.pivot_min), _ip(out.best), dp(out.normal)),
+                     "linear_fit_time_scan")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_time_scan_ms(self):
+        """HIP-event durations [ms] of the last `linear_fit_time_scan`: (evaluation, Gram-scan kernel, solve kernels, downloads)."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_time_scan_ms(self.h, _fp(ms)), "get_linear_fit_time_scan_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ robust linear fit (kiwi_hip_linear_fit_robust)

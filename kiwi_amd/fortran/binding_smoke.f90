@@ -9,7 +9,7 @@ program binding_smoke
     implicit none
 
     real(c_float) :: params(14), cent(10,4096), moment, risetime, msum
-    integer(c_int) :: ncent, rc
+    integer(c_int) :: ncent, rc, per_pass, tile
     type(c_ptr) :: ctx
     integer :: i
 
@@ -25,6 +25,10 @@ program binding_smoke
 
     ! the limits of kiwi_hip_time_scan answer without a device
     if (kiwi_hip_time_scan_max_shift() /= 1024 .or. kiwi_hip_time_scan_max_offsets() /= 256) stop 4
+
+    ! so does the shape of the linear fit's time scan: offsets per pass and samples per tile for six basis sources
+    if (kiwi_hip_linear_fit_time_scan_shape( 6_c_int, per_pass, tile ) /= 0) stop 5
+    if (per_pass < 1 .or. tile < 256 .or. mod(tile, 256) /= 0) stop 6
 
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then

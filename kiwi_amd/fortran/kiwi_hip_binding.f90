@@ -516,6 +516,49 @@ module kiwi_hip_binding
             real(c_float), intent(out) :: ms(3)                 ! evaluation, scan kernels, downloads
         end function
 
+        ! the linear fit at many origin times from one synthesis of the basis (kiwi_hip.h): groups as kiwi_hip_linear_fit, offsets as
+        ! kiwi_hip_time_scan
+        integer(c_int) function kiwi_hip_linear_fit_time_scan( ctx, isrc0, ngroup, k, k0, kstep, nk, receiver_weight, anarchy, coef, &
+                misfit, status, pivot_min, best, normal ) bind(C, name='kiwi_hip_linear_fit_time_scan')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, anarchy      ! isrc0 0-based
+            integer(c_int), value :: k0, kstep, nk
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            real(c_double), intent(out) :: coef(*)        ! (k, nk, ngroup)
+            real(c_double), intent(out) :: misfit(*)      ! (nk, ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (nk, ngroup)
+            type(c_ptr), value :: pivot_min               ! c_loc of real(c_double) (nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: best                    ! c_loc of integer(c_int) (ngroup): 0-based offset index, -1 if none is solved; or c_null_ptr
+            type(c_ptr), value :: normal                  ! c_loc of real(c_double) (nn, nk, ngroup), nn = k (k + 1) / 2 + k + 1, or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_time_scan_params( ctx, sourcetype, ngroup, k, params, piece, k0, kstep, nk, &
+                receiver_weight, anarchy, coef, misfit, status, pivot_min, best, normal ) &
+                bind(C, name='kiwi_hip_linear_fit_time_scan_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, anarchy
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            integer(c_int), value :: k0, kstep, nk
+            type(c_ptr), value :: receiver_weight
+            real(c_double), intent(out) :: coef(*), misfit(*)
+            integer(c_int), intent(out) :: status(*)
+            type(c_ptr), value :: pivot_min, best, normal ! as in kiwi_hip_linear_fit_time_scan
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_time_scan_ms( ctx, ms ) bind(C, name='kiwi_hip_get_linear_fit_time_scan_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, Gram-scan kernel, solve kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_time_scan_shape( k, per_pass, tile ) bind(C, name='kiwi_hip_linear_fit_time_scan_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: per_pass, tile      ! offsets per workgroup, window samples per LDS tile
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -148,6 +148,52 @@ class MisfitGrid:
         self.misfits_by_src, self.norms_by_src = mis, nor
         self.failings = sorted(int(i) for f in failings for i in where[f])
 
+    def compute_mt_time_scan(self, engine, dt=None, evaluate_fitted=True):
+        """A free moment tensor at every node of a grid with a `time` axis, from six syntheses per node of the grid WITHOUT that
+        axis (`mtfit.fit_moment_tensors_time_scan`, kiwi_hip_linear_fit_time_scan): the linear fit inside the time scan.  The
+        grid has exactly one `time` axis that `split_time_axis` accepts (`dt`: the database's sampling interval, default
+        engine.dt), no tensor axes, every node switched on, and its source type is `moment_tensor` or `mt_eikonal`; l2norm.
+        Fills, in grid order, `fitted_tensors`, `fit_misfits`, `fit_status`, `fit_pivot_min`, the tensor columns of `sources`,
+        `ibest`, `best_source`, `misfits_by_s` and `syntheses_saved` (against six syntheses per node of the full grid).  With
+        `evaluate_fitted` the fitted sources are then evaluated like any grid, as `compute(linear_mt=True)` does, so that
+        `postprocess` works on them."""
+        from . import mtfit
+        c0 = mtfit.TENSOR_COLUMN.get(SOURCE_TYPES.get(self.sourcetype, self.sourcetype))
+        if c0 is None or any(p in mtfit.COMPONENTS for p in self.sourceparams):
+            raise KiwiHipError("linear_mt: the source type must be moment_tensor or mt_eikonal and the grid must not run over tensor components")
+        axes = [i for i, (p, _) in enumerate(self.param_values) if p == "time"]
+        if len(axes) != 1:
+            raise ValueError("time_scan: the grid needs exactly one `time` axis")
+        ax = axes[0]
+        split = split_time_axis(self.param_values[ax][1], engine.dt if dt is None else dt)
+        if split is None:
+            raise ValueError("time_scan: the time axis is not evenly spaced by a whole number of samples")
+        k0, kstep, nk = split
+        dims = [len(v) for _, v in self.param_values]
+        if int(np.prod(dims)) != len(self.sources):
+            raise ValueError("time_scan: source constraints have switched grid nodes off; the scan needs the full grid")
+        self.receiver_mask = np.array(engine.enabled, bool)
+        self.nreceivers = len(engine.components)
+        self.ncomponents = [len(c) for c in engine.components]
+        idx = np.arange(len(self.sources)).reshape(dims)
+        first = np.take(idx, 0, axis=ax).ravel()                       # nodes at the axis's first value, grid order
+        where = np.moveaxis(idx, ax, -1).reshape(len(first), nk)        # [node without time][offset] -> grid index
+        tensors, misfit, status, pivot, _ = mtfit.fit_moment_tensors_time_scan(engine, self.sourcetype, self.sources[first], k0, kstep, nk)
+        n = len(self.sources)
+        self.fitted_tensors, self.fit_misfits = np.full((n, 6), np.nan), np.full(n, np.nan)
+        self.fit_status, self.fit_pivot_min = np.zeros(n, np.int32), np.zeros(n)
+        self.fitted_tensors[where], self.fit_misfits[where] = tensors, misfit
+        self.fit_status[where], self.fit_pivot_min[where] = status, pivot
+        solved = self.fit_status == 0
+        self.sources[solved, c0:c0 + 6] = self.fitted_tensors[solved].astype(np.float32)
+        self.syntheses_saved = 6 * (n - len(first))
+        if evaluate_fitted:
+            self.misfits_by_src, self.norms_by_src, self.failings = engine.make_misfits_for_sources(self.sourcetype, self.sources)
+            self.ref_misfits_by_src, self.ref_norms_by_src, _ = engine.make_misfits_for_sources(self.sourcetype, self.ref_params[None, :])
+        self.misfits_by_s = self.fit_misfits
+        self.ibest = int(np.nanargmin(self.fit_misfits)) if np.any(np.isfinite(self.fit_misfits)) else 0
+        self.best_source = self.sources[self.ibest]
+
     def compute(self, engine, dist=None, device=0, linear_mt=False, outer_norm="l2norm", niter=8, eps=1e-3, time_scan=False,
                 dt=None):
         """Trace misfits for every grid node (and the reference source), `engine` = kiwi_amd.Engine set up for

@@ -104,3 +104,31 @@ def fit_moment_tensors(engine, sourcetype, params, unit=1e18, deviatoric=False, 
         x, m, st, piv = solve_deviatoric(fit.normal[g])
         tensors[g], misfit[g], status[g], pivot[g] = x * float(unit), m, st, piv
     return tensors, misfit, status, pivot
+
+
+def fit_moment_tensors_time_scan(engine, sourcetype, params, k0, kstep, nk, unit=1e18, deviatoric=False, receiver_weights=None,
+                                 anarchy=False, piece=0):
+    """`fit_moment_tensors` at the origin-time offsets (k0 + j kstep) dt, j < nk, of every row of params[N, nparams], from the six
+    syntheses per row of a single time (`Engine.linear_fit_time_scan_params`): the best moment tensor of every (row, offset).
+    Returns (tensors[N, nk, 6] in N m, misfit[N, nk], status[N, nk], pivot_min[N, nk], best[N]): as `fit_moment_tensors` per
+    offset, and the offset index of the smallest misfit among the solved offsets of a row, -1 where there is none.
+    deviatoric=True solves the trace-free problem per offset on the host from the device's normal equations
+    (`solve_deviatoric`); `best` then follows the trace-free misfits."""
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    fit = engine.linear_fit_time_scan_params(sourcetype, elementary_params(sourcetype, p, unit), 6, k0, kstep, nk,
+                                             receiver_weights=receiver_weights, anarchy=anarchy, normal=deviatoric, piece=piece)
+    if not deviatoric:
+        return fit.coef * float(unit), fit.misfit, fit.status, fit.pivot_min, fit.best
+    nk = fit.status.shape[1]
+    tensors, misfit = np.full((len(p), nk, 6), np.nan), np.full((len(p), nk), np.nan)
+    status, pivot, best = np.array(fit.status, np.int32), np.zeros((len(p), nk)), np.full(len(p), -1, np.int32)
+    for g in range(len(p)):
+        for j in range(nk):
+            if fit.status[g, j] == 2:
+                continue
+            x, m, st, piv = solve_deviatoric(fit.normal[g, j])
+            tensors[g, j], misfit[g, j], status[g, j], pivot[g, j] = x * float(unit), m, st, piv
+        ok = np.nonzero(status[g] == 0)[0]
+        if len(ok):
+            best[g] = ok[int(np.argmin(misfit[g][ok]))]
+    return tensors, misfit, status, pivot, best
