@@ -573,6 +573,50 @@ int kiwi_hip_get_linear_fit_time_scan_ms(kiwi_hip_ctx *ctx, float ms[4]);
 /* how the Gram-scan kernel walks its work for K basis sources: *per_pass offsets per workgroup (their accumulators are registers),
  * *tile window samples per LDS tile; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_time_scan_shape(int K, int *per_pass, int *tile);
+/* ---- the misfits of MANY GIVEN coefficient vectors per group from the normal equations kiwi_hip_linear_fit keeps on the device
+ * (kiwi_amd/csrc/kiwi_linfit_candidates.hpp): the synthetics are linear in the coefficients, so a whole grid of trial mechanisms
+ * at a location -- every double couple over strike x dip x rake as a combination of the six elementary tensors -- costs the six
+ * syntheses of the basis and no more.  Groups, K, receiver_weight and anarchy are kiwi_hip_linear_fit's; the context's misfit method
+ * (the INNER norm) must be l2norm.  candidates [ncand][K] is shared by all groups.  With G_r, b_r, R_r the sums of receiver r, G, b, R
+ * their weighted fold, and for a vector x: x.b = sum_i x_i b_i from zero, (G x)_i = sum_j G_ij x_j from zero, x.G.x = sum_i x_i (G x)_i,
+ * all in ascending index order, q(x; G, b, R) = max((R - 2 x.b) + x.G.x, 0):
+ *   outer_norm 2 (l2norm)  misfit = sqrt(q(x; G, b, R) / R): kiwi_hip_linear_fit's misfit expression at the given x
+ *   outer_norm 1 (l1norm)  receivers r ascending, skipped where w_r == 0 or R_r <= 0: m_r = sqrt(q(x; G_r, b_r, R_r)), n_r = sqrt(R_r),
+ *                          v_r = w_r (anarchy: w_r / n_r); misfit = (sum v_r m_r) / (sum v_r n_r): make_global_misfits' l1norm over the
+ *                          receivers' l2norm misfits, iterate 0 of kiwi_hip_linear_fit_robust (inner l2norm) at the given x
+ *   free_scale 1           (outer_norm 2 only) a candidate is a direction u: a = (u.b) / (u.G.u) on the folded sums, x = a u, the
+ *                          misfit as above; NaN for both unless u.G.u > 0.  A negative a is returned as it is (the opposite mechanism)
+ *   best_index  [ngroup]   the candidate of the smallest misfit: NaN misfits passed over, the LOWEST index among equal values; -1 if none
+ *   best_misfit [ngroup]   its misfit, or NaN
+ *   status      [ngroup]   0 evaluated; 1 no data (l2norm: R not positive; l1norm: no receiver counts): NaN, best_index -1;
+ *                          2 a basis source of the group failed to discretise: NaN, best_index -1
+ *   misfit      [ngroup][ncand] or NULL        scale  [ngroup][ncand] or NULL (free_scale only): a
+ *   receiver_misfit  float [ngroup][ncand][nrec] or NULL: m_r;  receiver_norm  float [ngroup][nrec] or NULL: n_r; 0 for receivers that
+ *                          are disabled or skipped (and for status 2), NaN m_r for a candidate whose scale is NaN.  With one slot per
+ *                          receiver they are what kiwi_hip_outer_misfits takes: the bootstrap over the receivers of a mechanism grid
+ *   fit_coef    [ngroup][K] or NULL, fit_misfit [ngroup] or NULL: the free fit of the same groups, kiwi_hip_linear_fit's bits
+ * Every sum has a fixed order (tests/linfit_candidates_restatement.py): the answer does not depend on how candidates and receivers
+ * are tiled, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.  Afterwards the context is what
+ * kiwi_hip_linear_fit leaves.  Refused, nothing approximated: everything kiwi_hip_linear_fit refuses; ncand < 1; a candidate entry
+ * that is not finite; outer_norm other than 1, 2; free_scale other than 0, 1; free_scale with outer_norm 1; scale without free_scale.
+ * Under the outer l1norm a receiver of several components counts with the l2 misfit of all its components together. */
+int kiwi_hip_linear_fit_candidates(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                   const double *receiver_weight, int anarchy, int free_scale, int *best_index, double *best_misfit,
+                                   int *status, double *misfit, double *scale, float *receiver_misfit, float *receiver_norm,
+                                   double *fit_coef, double *fit_misfit);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_candidates_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                          int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                          int anarchy, int free_scale, int *best_index, double *best_misfit, int *status,
+                                          double *misfit, double *scale, float *receiver_misfit, float *receiver_norm,
+                                          double *fit_coef, double *fit_misfit);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram and solve kernels, ms[2] candidate
+ * kernels, ms[3] downloads */
+int kiwi_hip_get_linear_fit_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the candidate kernel walks its work: *candidates_per_workgroup (one per lane), *receivers_per_stage rows of sums per LDS
+ * stage; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -1465,6 +1465,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit.hpp"
 #include "kiwi_linfit_robust.hpp"
 #include "kiwi_linfit_wide.hpp"
+#include "kiwi_linfit_candidates.hpp"
 #include "kiwi_bands.hpp"
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
@@ -2818,10 +2819,13 @@ struct ScanCall { timescan::Out out; timescan::Offsets of; };
 // (kiwi_hip_linear_fit_time_scan_params the same with `fitscan` set: groups of K basis sources as for `fit`, a piece is evaluated by
 // linfit_timescan::run)
 struct FitScanCall { int K; const double *weight; int anarchy; linfit_timescan::Out out; timescan::Offsets of; };
+// (kiwi_hip_linear_fit_candidates_params the same with `cand` set: groups of K basis sources as for `fit`, a piece is evaluated by
+// linfit::run with the candidates behind its l2 kernels)
+struct CandCall { int K; const double *weight; int anarchy; linfit::Out out; linfit::Candidates cand; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
-                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr)
+                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2832,8 +2836,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (band) bands::check_setup(c);
     if (scan) timescan::check_setup(c, scan->of.k0, scan->of.kstep, scan->of.nk);
     if (fitscan) linfit_timescan::check_setup(c, fitscan->K, fitscan->of, fitscan->out);
+    if (cand) { linfit::check_candidates(cand->cand, cand->K); linfit::check_setup(c, cand->K, cand->out); }
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : 1;             // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2861,16 +2866,19 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool fitscanning = fitscan != nullptr;
             FitScanCall mine_fitscan{};
             if (fitscanning) { mine_fitscan = *fitscan; mine_fitscan.out = fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk); }
+            const bool canding = cand != nullptr;
+            CandCall mine_cand{};
+            if (canding) { mine_cand = *cand; mine_cand.out = cand->out.at(s0 / unit, unit, nrec_all); mine_cand.cand = cand->cand.at(s0 / unit, nrec_all); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
-                                       fitscanning ? &mine_fitscan : nullptr);
+                                       fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3001,6 +3009,10 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (scan) timescan::fill_failed((size_t)n, (size_t)scan->of.nk, nmis, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
             if (fitscan) linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)fitscan->of.nk,
                                                       fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
+            if (cand) {
+                linfit::fill_failed(n / unit, unit, nrec_all, cand->out.at(s0 / unit, unit, nrec_all));
+                linfit::cand_fill_failed(n / unit, nrec_all, cand->cand.at(s0 / unit, nrec_all));
+            }
             continue;
         }
         upload_batch(c, hb);
@@ -3010,7 +3022,10 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         else if (scan) timescan::run(c, 0, n, scan->of, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
         else if (fitscan) linfit_timescan::run(c, 0, n / unit, unit, fitscan->of, fitscan->weight, fitscan->anarchy,
                                                fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
-        else eval_impl(c, 0, n, c->keep_which);
+        else if (cand) {
+            const linfit::Candidates mine = cand->cand.at(s0 / unit, nrec_all);
+            linfit::run(c, 0, n / unit, unit, cand->weight, cand->anarchy, cand->out.at(s0 / unit, unit, nrec_all), nullptr, nullptr, &mine);
+        } else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
         if (trace) {
@@ -3240,6 +3255,72 @@ int kiwi_hip_get_linear_fit_time_scan_ms(kiwi_hip_ctx *c, float ms[4])
     if (!c) return fail(nullptr, "null context");
     if (!ms) return fail(c, "null argument");
     for (int i = 0; i < 4; i++) ms[i] = c->linfit_timescan_ms[i];
+    return 0;
+}
+
+// The misfits of given coefficient vectors from the kept normal equations (kiwi_linfit_candidates.hpp).  The free fit of the same
+// groups is made on the way; where the caller does not want it, it goes to arrays of this call
+struct CandFitArrays {
+    std::vector<double> coef, misfit;
+    std::vector<int> status;
+    linfit::Out out(int ngroup, int K, double *fit_coef, double *fit_misfit)
+    {
+        if (!fit_coef) coef.resize((size_t)std::max(ngroup, 0) * K);
+        if (!fit_misfit) misfit.resize((size_t)std::max(ngroup, 0));
+        status.resize((size_t)std::max(ngroup, 0));
+        return linfit::Out{ fit_coef ? fit_coef : coef.data(), fit_misfit ? fit_misfit : misfit.data(), status.data() };
+    }
+};
+
+int kiwi_hip_linear_fit_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                   const double *receiver_weight, int anarchy, int free_scale, int *best_index, double *best_misfit,
+                                   int *status, double *misfit, double *scale, float *receiver_misfit, float *receiver_norm,
+                                   double *fit_coef, double *fit_misfit)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    if (K < 1 || K > linfit::kMaxBasis)
+        throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    const linfit::Candidates cd{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale, receiver_misfit,
+                                 receiver_norm };
+    CandFitArrays fa;
+    linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, fa.out(ngroup, K, fit_coef, fit_misfit), nullptr, nullptr, &cd);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_candidates_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int ncand,
+                                          const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                          int free_scale, int *best_index, double *best_misfit, int *status, double *misfit, double *scale,
+                                          float *receiver_misfit, float *receiver_norm, double *fit_coef, double *fit_misfit)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
+    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) m->linfit_ms[0] = m->linfit_ms[1] = m->linfit_ms[2] = m->linfit_ms[3] = 0.f;
+    CandFitArrays fa;
+    const CandCall cand{ K, receiver_weight, anarchy, fa.out(ngroup, K, fit_coef, fit_misfit),
+                         linfit::Candidates{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale,
+                                             receiver_misfit, receiver_norm } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cand);
+}
+
+int kiwi_hip_get_linear_fit_candidates_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->linfit_ms[i];
+    return 0;
+}
+
+int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !receivers_per_stage) return 1;
+    *candidates_per_workgroup = linfit::kCandThreads;
+    *receivers_per_stage = linfit::kCandStage;
     return 0;
 }
 

@@ -304,6 +304,38 @@ static void wide_launch(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, co
                         const double *penalty_d, double *nbr, double *coef, double *misfit, int *status, double *pivot, int *npos,
                         int *nsol, double *normal, hipEvent_t between);
 
+// the misfits of given coefficient vectors behind the l2 kernels (kiwi_linfit_candidates.hpp): x [ncand][K] (host), shared by all
+// groups; outer_norm 1 l1norm, 2 l2norm; free_scale: a candidate is a direction, its best scale is found (l2norm only).  Host
+// arrays for the groups of ONE call of run(): best_index, best_misfit, status [group]; misfit, scale [group][ncand],
+// receiver_misfit [group][ncand][nrec], receiver_norm [group][nrec], each of the four may be null
+struct Candidates {
+    const double *x; int ncand, outer_norm, free_scale;
+    int *best_index; double *best_misfit; int *status;
+    double *misfit, *scale;
+    float *receiver_misfit, *receiver_norm;
+    Candidates at(int g, int nrec) const
+    {
+        Candidates c = *this;
+        c.best_index += g; c.best_misfit += g; c.status += g;
+        if (misfit) c.misfit += (size_t)g * ncand;
+        if (scale) c.scale += (size_t)g * ncand;
+        if (receiver_misfit) c.receiver_misfit += (size_t)g * ncand * nrec;
+        if (receiver_norm) c.receiver_norm += (size_t)g * nrec;
+        return c;
+    }
+};
+// device buffers of the candidate kernels, kept over the chunks of one run
+struct CandBufs {
+    DevBuf<double> x, misfit, scale, tile_v, best_misfit;
+    DevBuf<float> rmis, rnorm;
+    DevBuf<int> tile_i, best_index, status;
+};
+static void check_candidates(const Candidates &cd, int K);
+static size_t cand_bytes(const Candidates &cd, int nrec);
+static void cand_chunk(kiwi_hip_ctx *c, int K, int g0, int ng, const double *w_d, int anarchy, const double *nbr, const double *normal,
+                       const Candidates &cd, CandBufs &b, hipEvent_t after_kernels);
+static void cand_fill_failed(int ngroup, int nrec, const Candidates &cd);
+
 // what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.
 static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr, const Wide *wd = nullptr)
 {
@@ -328,10 +360,12 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb
 }
 
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->linfit_ms.  rb: the reweighting
-// passes of a robust fit behind the l2 solve of every chunk, or null.  wd: the wide fit in place of the l2 kernels, or null
+// passes of a robust fit behind the l2 solve of every chunk, or null.  wd: the wide fit in place of the l2 kernels, or null.
+// cd: candidate coefficient vectors evaluated behind the l2 kernels of every chunk, or null
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Out &out,
-                const Robust *rb = nullptr, const Wide *wd = nullptr)
+                const Robust *rb = nullptr, const Wide *wd = nullptr, const Candidates *cd = nullptr)
 {
+    if (cd) check_candidates(*cd, K);
     check_setup(c, K, out, rb, wd);
     if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
         throw std::runtime_error("linear_fit: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
@@ -361,6 +395,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     const size_t trace_len = rb ? (size_t)(rb->niter + 1) * 2 : 0;
     DevBuf<int> st_d, npos_d, nsol_d;
     DevBuf<double> penalty_d;
+    CandBufs cand;
     w_d.alloc((size_t)nrec, &c->dev_bytes);
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (wd && wd->penalty) {
@@ -385,6 +420,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
                 add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float) * 2;
             }
             add += (size_t)nrec * (NN + (rb && rb->mode == 1 ? NN + 2 : 0)) * sizeof(double);
+            if (cd) add += cand_bytes(*cd, nrec);
             if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
             if (c->fft_needed && (ng + 1) * K > c->fft_cap) break;
             bytes += add; ng++;
@@ -396,7 +432,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         nbr_d.ensure((size_t)ng * nrec * NN, &c->dev_bytes);
         coef_d.ensure((size_t)ng * K, &c->dev_bytes); mis_d.ensure((size_t)ng, &c->dev_bytes); piv_d.ensure((size_t)ng, &c->dev_bytes);
         st_d.ensure((size_t)ng, &c->dev_bytes);
-        if (out.normal) normal_d.ensure((size_t)ng * NN, &c->dev_bytes);
+        if (out.normal || cd) normal_d.ensure((size_t)ng * NN, &c->dev_bytes);
         HIPCHECK(hipMemsetAsync(nbr_d.p, 0, (size_t)ng * nrec * NN * sizeof(double), c->stream));
         if (wd) {
             npos_d.ensure((size_t)ng, &c->dev_bytes); nsol_d.ensure((size_t)ng, &c->dev_bytes);
@@ -404,7 +440,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
                         coef_d.p, mis_d.p, st_d.p, piv_d.p, npos_d.p, nsol_d.p, out.normal ? normal_d.p : (double *)nullptr, ev[5]);
         } else
             launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, coef_d.p, mis_d.p,
-                       st_d.p, piv_d.p, out.normal ? normal_d.p : (double *)nullptr);
+                       st_d.p, piv_d.p, out.normal || cd ? normal_d.p : (double *)nullptr);
         HIPCHECK(hipEventRecord(ev[2], c->stream));
         if (rb) {
             if (rb->mode == 1) wbr_d.ensure((size_t)ng * nrec * (NN + 2), &c->dev_bytes);
@@ -412,7 +448,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             robust_launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, *rb, wbr_d.p,
                               coef_d.p, mis_d.p, st_d.p, trace_d.p);
         }
-        HIPCHECK(hipEventRecord(ev[3], c->stream));
+        if (cd) cand_chunk(c, K, g0, ng, w_d.p, anarchy ? 1 : 0, nbr_d.p, normal_d.p, *cd, cand, ev[3]);    // (its downloads are queued behind ev[3])
+        else HIPCHECK(hipEventRecord(ev[3], c->stream));
         piv_h.resize((size_t)ng);
         HIPCHECK(hipMemcpyAsync(out.coef + (size_t)g0 * K, coef_d.p, (size_t)ng * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipMemcpyAsync(out.misfit + g0, mis_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -460,6 +497,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         if (out.trace) std::fill(out.trace + (size_t)g * out.trace_rows * 2, out.trace + (size_t)(g + 1) * out.trace_rows * 2, nan);
         if (out.npositive) out.npositive[g] = 0;
         if (out.nsolves) out.nsolves[g] = 0;
+        if (cd) cand_fill_failed(1, nrec, cd->at(g, nrec));
     }
 }
 

@@ -20,6 +20,8 @@ NORMS = {"l2norm": 1, "l1norm": 2, "ampspec_l2norm": 3, "ampspec_l1norm": 4, "sc
 LinearFit = collections.namedtuple("LinearFit", "coef misfit status pivot_min normal by_receiver")
 RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
 ScanFit = collections.namedtuple("ScanFit", "coef misfit status pivot_min best normal")
+CandidateScan = collections.namedtuple("CandidateScan", "best_index best_misfit status misfit scale receiver_misfit receiver_norm "
+                                                        "fit_coef fit_misfit")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -897,6 +899,77 @@ class Engine:
         """HIP-event durations [ms] of the last `linear_fit_time_scan`: (evaluation, Gram-scan kernel, solve kernels, downloads)."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_time_scan_ms(self.h, _fp(ms)), "get_linear_fit_time_scan_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ candidate coefficient vectors (kiwi_hip_linear_fit_candidates)
+    def linear_fit_candidates_shape(self, K):
+        """(candidates per workgroup, receivers per LDS stage) of the candidate kernel for K basis sources."""
+        c, s = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_linear_fit_candidates_shape(int(K), _ip(c), _ip(s)):
+            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(s[0])
+
+    def _candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        w, fit, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != int(K):
+            raise KiwiHipError("linear_fit_candidates: candidates must be [ncand, K = %d]" % int(K))
+        ng, nc, nrec = int(ngroup), len(x), len(self.components)
+        out = CandidateScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nc)) if misfit else None,
+                            np.zeros((ng, nc)) if free_scale else None,
+                            np.zeros((ng, nc, nrec), np.float32) if receiver_misfit else None,
+                            np.zeros((ng, nrec), np.float32) if receiver_misfit else None, fit.coef, fit.misfit)
+        tail = (nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.misfit), dp(out.scale),      # noqa: E731
+                        None if out.receiver_misfit is None else _fp(out.receiver_misfit),
+                        None if out.receiver_norm is None else _fp(out.receiver_norm), dp(out.fit_coef), dp(out.fit_misfit))
+        return tail, out, outs
+
+    def linear_fit_candidates(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                              free_scale=False, misfit=True, receiver_misfit=False):
+        """The misfits of the coefficient vectors candidates[ncand, K] for every group of `linear_fit`, from the normal
+        equations the fit keeps on the device (kiwi_hip_linear_fit_candidates): no synthesis per candidate.  The engine's
+        misfit method (the inner norm) must be l2norm; `outer_norm` combines the receivers.  free_scale (l2norm only): a
+        candidate is a direction whose best scale is found.  Returns a `CandidateScan`: best_index[ngroup] (-1: none),
+        best_misfit[ngroup], status[ngroup] (0 evaluated, 1 no data, 2 a basis source failed to discretise), misfit[ngroup,
+        ncand] (misfit=True), scale[ngroup, ncand] (free_scale), receiver_misfit[ngroup, ncand, nrec] and receiver_norm[ngroup,
+        nrec] float32 (receiver_misfit=True: what `outer_misfits` takes with one slot per receiver), fit_coef[ngroup, K] and
+        fit_misfit[ngroup]: `linear_fit` of the same groups."""
+        tail, out, outs = self._candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
+                                                       1 if free_scale else 0, *outs()), "linear_fit_candidates")
+        return out
+
+    def linear_fit_candidates_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                                     free_scale=False, misfit=True, receiver_misfit=False, piece=0):
+        """`linear_fit_candidates` for a parameter list of any length (kiwi_hip_linear_fit_candidates_params), cut into pieces
+        and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        tail, out, outs = self._candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_candidates_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail, 1 if anarchy else 0,
+                                                                  1 if free_scale else 0, *outs()), "linear_fit_candidates")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_candidates_ms(self):
+        """HIP-event durations [ms] of the last `linear_fit_candidates`: (evaluation, Gram and solve kernels, candidate kernels,
+        downloads)."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_ms(self.h, _fp(ms)), "get_linear_fit_candidates_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ robust linear fit (kiwi_hip_linear_fit_robust)

@@ -9,7 +9,7 @@ program binding_smoke
     implicit none
 
     real(c_float) :: params(14), cent(10,4096), moment, risetime, msum
-    integer(c_int) :: ncent, rc, per_pass, tile
+    integer(c_int) :: ncent, rc, per_pass, tile, per_group, per_stage
     type(c_ptr) :: ctx
     integer :: i
 
@@ -29,6 +29,10 @@ program binding_smoke
     ! so does the shape of the linear fit's time scan: offsets per pass and samples per tile for six basis sources
     if (kiwi_hip_linear_fit_time_scan_shape( 6_c_int, per_pass, tile ) /= 0) stop 5
     if (per_pass < 1 .or. tile < 256 .or. mod(tile, 256) /= 0) stop 6
+
+    ! and the shape of the candidate kernel: candidates per workgroup and receivers per LDS stage
+    if (kiwi_hip_linear_fit_candidates_shape( 6_c_int, per_group, per_stage ) /= 0) stop 7
+    if (per_group < 64 .or. per_stage < 1) stop 8
 
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then

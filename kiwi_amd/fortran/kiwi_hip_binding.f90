@@ -559,6 +559,52 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: per_pass, tile      ! offsets per workgroup, window samples per LDS tile
         end function
 
+        ! the misfits of many given coefficient vectors per group from the kept normal equations: a mechanism grid from the six
+        ! syntheses of the basis (kiwi_hip.h)
+        integer(c_int) function kiwi_hip_linear_fit_candidates( ctx, isrc0, ngroup, k, ncand, candidates, outer_norm, receiver_weight, &
+                anarchy, free_scale, best_index, best_misfit, status, misfit, scale, receiver_misfit, receiver_norm, fit_coef, &
+                fit_misfit ) bind(C, name='kiwi_hip_linear_fit_candidates')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, ncand, outer_norm, anarchy, free_scale      ! isrc0 0-based; outer_norm 1 l1norm, 2 l2norm
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_index(*)  ! (ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: misfit, scale           ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: receiver_misfit         ! c_loc of real(c_float) (nrec, ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: receiver_norm           ! c_loc of real(c_float) (nrec, ngroup), or c_null_ptr
+            type(c_ptr), value :: fit_coef, fit_misfit    ! c_loc of real(c_double) (k, ngroup) and (ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_params( ctx, sourcetype, ngroup, k, params, piece, ncand, candidates, &
+                outer_norm, receiver_weight, anarchy, free_scale, best_index, best_misfit, status, misfit, scale, receiver_misfit, &
+                receiver_norm, fit_coef, fit_misfit ) bind(C, name='kiwi_hip_linear_fit_candidates_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, ncand, outer_norm, anarchy, free_scale
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_index(*), status(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: misfit, scale, receiver_misfit, receiver_norm, fit_coef, fit_misfit      ! as in kiwi_hip_linear_fit_candidates
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_candidates_ms( ctx, ms ) bind(C, name='kiwi_hip_get_linear_fit_candidates_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, Gram and solve kernels, candidate kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_shape( k, candidates_per_workgroup, receivers_per_stage ) &
+                bind(C, name='kiwi_hip_linear_fit_candidates_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, receivers_per_stage
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -132,3 +132,53 @@ def fit_moment_tensors_time_scan(engine, sourcetype, params, k0, kstep, nk, unit
         if len(ok):
             best[g] = ok[int(np.argmin(misfit[g][ok]))]
     return tensors, misfit, status, pivot, best
+
+
+def double_couple_candidates(strikes, dips, rakes, moment=1.0):
+    """The double couples over strikes x dips x rakes [degrees] (first axis slowest, the order of `synthetic.mt_sdr_grid`) with
+    the scalar moment `moment`: (tensors [n, 6] float64 in COMPONENTS order -- `synthetic.mt_from_sdr`'s R m_unrot R^T with
+    R = euler(dip, strike, -rake) --, sdr [n, 3] float64: the strike, dip and rake of every row)."""
+    s, d, r = (np.asarray(list(a), np.float64) for a in (strikes, dips, rakes))
+    sdr = np.stack([g.ravel() for g in np.meshgrid(s, d, r, indexing="ij")], axis=1)
+    a, b, g = np.radians(sdr[:, 1]), np.radians(sdr[:, 0]), -np.radians(sdr[:, 2])
+    ca, cb, cg, sa, sb, sg = np.cos(a), np.cos(b), np.cos(g), np.sin(a), np.sin(b), np.sin(g)
+    R = np.array([[cb * cg - ca * sb * sg, -cb * sg - ca * sb * cg, sa * sb],
+                  [sb * cg + ca * cb * sg, -sb * sg + ca * cb * cg, -sa * cb],
+                  [sa * sg, sa * cg, ca]]).transpose(2, 0, 1)
+    mu = np.array([[0, 0, -1.], [0, 0, 0], [-1., 0, 0]])
+    m = R @ mu @ R.transpose(0, 2, 1) * float(moment)
+    return np.stack([m[:, 0, 0], m[:, 1, 1], m[:, 2, 2], m[:, 0, 1], m[:, 0, 2], m[:, 1, 2]], axis=1), sdr
+
+
+def scan_double_couples(engine, sourcetype, params, strikes, dips, rakes, moment=None, outer_norm="l1norm", unit=1e18,
+                        receiver_weights=None, anarchy=False, piece=0, cube=False, receiver_misfit=False):
+    """The best double couple of every row of params[N, nparams] (its own tensor columns are ignored) over the grid strikes x
+    dips x rakes, from the SIX syntheses of the row's elementary tensors (`Engine.linear_fit_candidates_params`): every
+    mechanism of the grid is a combination of them, so no mechanism is synthesised.  moment=None: the best scalar moment of
+    every mechanism is found on the way (outer l2norm only; it may come out negative: the opposite mechanism); otherwise all
+    mechanisms have that moment [N m].  Returns a dict: strike, dip, rake, moment, misfit [N] of the best mechanism (NaN where
+    there is none), index [N] its row in the grid (-1: none), status [N] (0 evaluated, 1 no data, 2 the row failed to
+    discretise), tensor [N, 6] in N m and tensor_misfit [N]: the free tensor of `fit_moment_tensors` (l2norm) of the same
+    row, scan: the `CandidateScan`; cube=True adds cube [N, ns, nd, nr], every mechanism's misfit (and moments, the same
+    shape, where moment is None)."""
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    free = moment is None
+    if free and outer_norm != "l2norm":
+        raise KiwiHipError("scan_double_couples: moment=None (the best moment per mechanism) needs outer_norm l2norm; give a moment")
+    s, d, r = list(strikes), list(dips), list(rakes)
+    cand, sdr = double_couple_candidates(s, d, r, 1.0 if free else float(moment) / float(unit))
+    scan = engine.linear_fit_candidates_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, outer_norm=outer_norm,
+                                               receiver_weights=receiver_weights, anarchy=anarchy, free_scale=free,
+                                               misfit=cube or free, receiver_misfit=receiver_misfit, piece=piece)
+    has = scan.best_index >= 0
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, None], sdr[at], np.nan)
+    rows = np.arange(len(p))
+    mom = np.where(has, scan.scale[rows, at] * float(unit) if free else float(moment), np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=mom, misfit=scan.best_misfit, index=scan.best_index,
+               status=scan.status, tensor=scan.fit_coef * float(unit), tensor_misfit=scan.fit_misfit, scan=scan)
+    if cube:
+        out["cube"] = scan.misfit.reshape(len(p), len(s), len(d), len(r))
+        if free:
+            out["moments"] = (scan.scale * float(unit)).reshape(len(p), len(s), len(d), len(r))
+    return out
