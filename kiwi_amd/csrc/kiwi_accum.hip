@@ -57,23 +57,34 @@ void launch_grouped(const AccumArgs &a, dim3 grid, int T, int ntiles, const int 
 #endif
 
 #if KIWI_FAMILY == 3
-template <int NG, int NS, bool COMPACT>
+template <int NG, int NS, bool COMPACT, bool PLAN>
 static void multi_t(const AccumArgs &a, dim3 grid, int ntiles, const int *mate, const int *wider)
 {
-    if (a.fuse) hipLaunchKernelGGL((accumulate_multi_kernel<NG, true, NS, COMPACT>), grid, dim3(256), 0, a.stream, KIWI_COMMON_ARGS, ntiles, a.tab, a.coefs, a.fp,
-                                   a.pairflag, mate, wider);
-    else        hipLaunchKernelGGL((accumulate_multi_kernel<NG, false, NS, COMPACT>), grid, dim3(256), 0, a.stream, KIWI_COMMON_ARGS, ntiles, a.tab, a.coefs, a.fp,
-                                   a.pairflag, mate, wider);
+    if (a.fuse) hipLaunchKernelGGL((accumulate_multi_kernel<NG, true, NS, COMPACT, PLAN>), grid, dim3(256), 0, a.stream, KIWI_COMMON_ARGS, ntiles, a.tab, a.coefs, a.fp,
+                                   a.pairflag, mate, wider, a.plan, a.plan_ofs);
+    else        hipLaunchKernelGGL((accumulate_multi_kernel<NG, false, NS, COMPACT, PLAN>), grid, dim3(256), 0, a.stream, KIWI_COMMON_ARGS, ntiles, a.tab, a.coefs, a.fp,
+                                   a.pairflag, mate, wider, a.plan, a.plan_ofs);
 }
 template <int NG, int NS>
 static void multi_c(const AccumArgs &a, dim3 grid, int ntiles, const int *mate, const int *wider)
 {
-    if (a.compact) multi_t<NG, NS, true>(a, grid, ntiles, mate, wider); else multi_t<NG, NS, false>(a, grid, ntiles, mate, wider);
+    // (plans hold compact descriptors: the 512-byte descriptor rows keep the loop top that reads the head records)
+    if (a.compact && a.plan) multi_t<NG, NS, true, true>(a, grid, ntiles, mate, wider);
+    else if (a.compact) multi_t<NG, NS, true, false>(a, grid, ntiles, mate, wider);
+    else multi_t<NG, NS, false, false>(a, grid, ntiles, mate, wider);
 }
 void launch_multi(const AccumArgs &a, dim3 grid, int NS, int ntiles, const int *mate, const int *wider)
 {
     if (a.ng == 10) { if (NS == 4) multi_c<10, 4>(a, grid, ntiles, mate, wider); else multi_c<10, 2>(a, grid, ntiles, mate, wider); }
     else            { if (NS == 4) multi_c<8, 4>(a, grid, ntiles, mate, wider); else multi_c<8, 2>(a, grid, ntiles, mate, wider); }
+}
+void launch_multi_plan(const AccumArgs &a, int NS, int ngroups, const int *mate, const int *wider, PlanSrc *plan)
+{
+    const dim3 grid((unsigned)ngroups, (unsigned)((a.nrec + 63) / 64));
+    if (NS == 4) hipLaunchKernelGGL(multi_plan_kernel<4>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.recv, a.tab, a.pairflag, mate, wider,
+                                    a.plan_ofs, (int4 *)plan);
+    else         hipLaunchKernelGGL(multi_plan_kernel<2>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.recv, a.tab, a.pairflag, mate, wider,
+                                    a.plan_ofs, (int4 *)plan);
 }
 #endif
 

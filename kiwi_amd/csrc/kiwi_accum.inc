@@ -381,23 +381,61 @@ __device__ __forceinline__ void pair_finish(const f4u (&v)[2][BLEND ? 4 : 1], fl
 // ds_bpermute.  halo_issue only loads; halo_finish blends and stores.
 struct HaloRegs { f4u v[4]; };
 
-template <bool BLEND, bool FAST>
-__device__ __forceinline__ HaloRegs halo_issue(bool active, int ig, int ph, int jb, const float *__restrict__ G, int pitch,
-                                               int ta, int tb)
+// The load descriptors of a centroid group as the build reads them: a(ig, k) / b(ig, k): ta / tb of node k's row of component ig,
+// wave-uniform; ha / hb: the same for the component of a halo lane.
+// DescLanes: the lane-distributed descriptor row (write_tab's layout, or desc_expand's copy of it): read-lanes and, for the halo,
+// ds_bpermute.
+struct DescLanes {
+    int ta, tb;
+    __device__ __forceinline__ int a(int ig, int k) const { return REC_I(ta, 4 * ig + k); }
+    __device__ __forceinline__ int b(int ig, int k) const { return REC_I(tb, 4 * ig + k); }
+    __device__ __forceinline__ int ha(int hig, int k) const { return __shfl(ta, 4 * hig + k, 64); }
+    __device__ __forceinline__ int hb(int hig, int k) const { return __shfl(tb, 4 * hig + k, 64); }
+    // every row of the group covers LDS positions 0 .. lds_tile - 1 of a tile that starts at trace sample jb without clamping
+    __device__ __forceinline__ bool fast(int jb, int lds_tile, int pitch, int lane, int ng) const
+    {
+        const bool lane_ok = lane >= 4 * ng || (ta + jb >= tb && ta + jb + lds_tile <= tb + pitch);
+        return __builtin_amdgcn_ballot_w64(lane_ok) == ~0ull;
+    }
+};
+// DescPlan: compact descriptors held in scalar registers (PlanSrc::row, o): what desc_expand lays out in lanes, tb = (row_k + ig -
+// row_0) pitch and ta = tb + o_k, as scalar arithmetic (the same 32-bit sums); `hoff`: the halo lane's component times pitch.
+struct DescPlan {
+    int b0[4], o[4], pitch, hoff;
+    __device__ __forceinline__ int b(int ig, int k) const { return b0[k] + ig * pitch; }
+    __device__ __forceinline__ int a(int ig, int k) const { return b0[k] + ig * pitch + o[k]; }
+    __device__ __forceinline__ int hb(int, int k) const { return b0[k] + hoff; }
+    __device__ __forceinline__ int ha(int, int k) const { return b0[k] + hoff + o[k]; }
+    __device__ __forceinline__ bool fast(int jb, int lds_tile, int pitch_, int, int) const
+    {
+        // (ta - tb = o_k in every lane below 4 ng: the lanes' test is that of the smallest and the largest o_k)
+        const int omin = min(min(o[0], o[1]), min(o[2], o[3])), omax = max(max(o[0], o[1]), max(o[2], o[3]));
+        return omin + jb >= 0 && omax + jb + lds_tile <= pitch_;
+    }
+};
+
+template <bool BLEND, bool FAST, typename D>
+__device__ __forceinline__ HaloRegs halo_issue(bool active, int ig, int ph, int jb, const float *__restrict__ G, int pitch, const D &d)
 {
     HaloRegs h;
 #pragma unroll
     for (int k = 0; k < (BLEND ? 4 : 1); k++) {
-        const int base = __shfl(ta, 4 * ig + k, 64);
+        const int base = d.ha(ig, k);
         int idx = base + jb + ph;
         if constexpr (!FAST) {
-            const int lo = __shfl(tb, 4 * ig + k, 64);
+            const int lo = d.hb(ig, k);
             idx = min(max(idx, lo), lo + pitch - 4);
         }
         h.v[k] = f4u{ 0.f, 0.f, 0.f, 0.f };
         if (active) h.v[k] = *(const f4u *)(G + (size_t)(unsigned)idx);
     }
     return h;
+}
+template <bool BLEND, bool FAST>
+__device__ __forceinline__ HaloRegs halo_issue(bool active, int ig, int ph, int jb, const float *__restrict__ G, int pitch,
+                                               int ta, int tb)
+{
+    return halo_issue<BLEND, FAST>(active, ig, ph, jb, G, pitch, DescLanes{ ta, tb });
 }
 
 template <bool BLEND>
@@ -1345,18 +1383,18 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(3))) void acc
     }
 }
 
-template <bool BLEND, bool FAST>
+template <bool BLEND, bool FAST, typename D>
 __device__ __forceinline__ void one_issue(f4u (&v)[BLEND ? 4 : 1], int ig, int p, int jb, const float *__restrict__ G,
-                                          int pitch, int ta, int tb)
+                                          int pitch, const D &d)
 {
     const int j = jb + p;
 #pragma unroll
     for (int k = 0; k < (BLEND ? 4 : 1); k++) {
-        const int base = REC_I(ta, 4 * ig + k);
+        const int base = d.a(ig, k);
         if constexpr (FAST) {
             v[k] = buf_load4(gf_rsrc(G), p, base + jb);
         } else {
-            const int lo = REC_I(tb, 4 * ig + k);
+            const int lo = d.b(ig, k);
             const int idx = min(max(base + j, lo), lo + pitch - 4);
             v[k] = *(const f4u *)(G + (size_t)(unsigned)idx);
         }
@@ -1371,14 +1409,15 @@ __device__ __forceinline__ void one_issue(f4u (&v)[BLEND ? 4 : 1], int ig, int p
 // statement vm_wait<>, which takes the task's registers as operands so that nothing that uses them can be scheduled in front of it.
 // vmcnt counts loads in flight and they return in order: vm_wait<4 k> lets the k wave-tasks issued behind this one stay in flight
 // (a load the compiler issues in between -- the group's integer shifts in shadow() -- makes the wait one load stricter, never weaker).
-__device__ __forceinline__ void one_issue_hidden(f4u (&v)[4], int ig, int p, int jb, const float *__restrict__ G, int ta)
+template <typename D>
+__device__ __forceinline__ void one_issue_hidden(f4u (&v)[4], int ig, int p, int jb, const float *__restrict__ G, const D &d)
 {
     const size_t gi = (size_t)G;
     const v4i_t rs = { (int)(unsigned)gi, (int)((unsigned)(gi >> 32) & 0xffffu), -1, 0x00020000 };      // (= gf_rsrc(G))
     const int voff = (int)(4u * (unsigned)p);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int soff = (int)(4u * (unsigned)(REC_I(ta, 4 * ig + k) + jb));
+        const int soff = (int)(4u * (unsigned)(d.a(ig, k) + jb));
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v[k]) : "v"(voff), "s"(rs), "s"(soff));
     }
 }
@@ -1436,14 +1475,15 @@ typedef float f4m __attribute__((ext_vector_type(4)));
 struct RowsDw { float r[4][4]; };      // [node][64-sample chunk] of one wave-task: lane l holds sample 64 m + l of the slab
 
 // the 16 loads of a wave-task, hidden from the compiler's wait-count bookkeeping like one_issue_hidden's
-__device__ __forceinline__ void rows_issue_dw(RowsDw &v, int ig, int lane, int jb, const float *__restrict__ G, int ta)
+template <typename D>
+__device__ __forceinline__ void rows_issue_dw(RowsDw &v, int ig, int lane, int jb, const float *__restrict__ G, const D &d)
 {
     const size_t gi = (size_t)G;
     const v4i_t rs = { (int)(unsigned)gi, (int)((unsigned)(gi >> 32) & 0xffffu), -1, 0x00020000 };      // (= gf_rsrc(G))
     const int voff = (int)(4u * (unsigned)lane);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int soff = (int)(4u * (unsigned)(REC_I(ta, 4 * ig + k) + jb));
+        const int soff = (int)(4u * (unsigned)(d.a(ig, k) + jb));
         asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(v.r[k][0]) : "v"(voff), "s"(rs), "s"(soff));
         asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:256" : "=v"(v.r[k][1]) : "v"(voff), "s"(rs), "s"(soff));
         asm volatile("buffer_load_dword %0, %1, %2, %3 offen offset:512" : "=v"(v.r[k][2]) : "v"(voff), "s"(rs), "s"(soff));
@@ -1491,9 +1531,9 @@ template <int NG, int NS> __host__ __device__ constexpr int multi_set_stride() {
 // blended with the weights of each source into its tile set (gfdb.f90:946-949, summed in this order) -- `only` >= 0: into that
 // source's set alone.  A centroid exactly on a node carries the weights (1, 0, 0, 0) over four copies of its row:
 // 1 v + 0 v + 0 v + 0 v is v bit for bit, so there is no unblended variant.
-template <int NG, bool FAST, int NS, typename Shadow>
+template <int NG, bool FAST, int NS, typename D, typename Shadow>
 __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, int lane, int tid, int jb, const float *__restrict__ G,
-                                            int pitch, int ta, int tb, const GeoRec (&gw)[NS], int only, bool hact, bool whalo, int hig, int hph,
+                                            int pitch, const D &d, const GeoRec (&gw)[NS], int only, bool hact, bool whalo, int hig, int hph,
                                             Shadow shadow)
 {
     constexpr int TILE = 1024 / NS, LDS_TILE = TILE + kHalo, DEPTH = 3, SET = multi_set_stride<NG, NS>();
@@ -1502,14 +1542,14 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
     auto comp = [&](int i) { return (NS == 2) ? 2 * i + (wv >> 1) : wv + 4 * i; };
     HaloRegs hv;
     // (a wave without a halo lane skips the halo; in the others inactive lanes load a valid chunk too: no merge of registers)
-    if (whalo) hv = halo_issue<true, FAST>(true, hig, hph, jb, G, pitch, ta, tb);
+    if (whalo) hv = halo_issue<true, FAST>(true, hig, hph, jb, G, pitch, d);
     // (tasks 0 .. N - 2 exist in every wave, the last one only where its component does: NS = 4, NG = 10: waves 0 and 1)
     const bool last_ok = comp(N - 1) < NG;
     if constexpr (KIWI_MFMA_BLEND && FAST && NS == 4 && KIWI_ARITH == 0) {
         // ---- the products of the blend on the matrix pipe (see mfma_finish); `only` >= 0: every lane blends, the lanes of that source write
         RowsDw v[N];
 #pragma unroll
-        for (int i = 0; i < DEPTH && i < N; i++) if (i < N - 1 || last_ok) rows_issue_dw(v[i], comp(i), lane, jb, G, ta);
+        for (int i = 0; i < DEPTH && i < N; i++) if (i < N - 1 || last_ok) rows_issue_dw(v[i], comp(i), lane, jb, G, d);
         __syncthreads();                                 // (as below)
         shadow();
         const int me = lane & 3;
@@ -1532,7 +1572,7 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
                 }
                 mfma_finish(v[i], dst + comp(i) * LDS_TILE, w, write);
             }
-            if (i + DEPTH < N && (i + DEPTH < N - 1 || last_ok)) rows_issue_dw(v[i + DEPTH], comp(i + DEPTH), lane, jb, G, ta);
+            if (i + DEPTH < N && (i + DEPTH < N - 1 || last_ok)) rows_issue_dw(v[i + DEPTH], comp(i + DEPTH), lane, jb, G, d);
         }
         if (whalo) {
 #pragma unroll
@@ -1543,8 +1583,8 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
     }
     f4u v[N][4];
     auto issue = [&](int i) __attribute__((always_inline)) {
-        if constexpr (FAST) one_issue_hidden(v[i], comp(i), p, jb, G, ta);
-        else one_issue<true, false>(v[i], comp(i), p, jb, G, pitch, ta, tb);
+        if constexpr (FAST) one_issue_hidden(v[i], comp(i), p, jb, G, d);
+        else one_issue<true, false>(v[i], comp(i), p, jb, G, pitch, d);
     };
 #pragma unroll
     for (int i = 0; i < DEPTH && i < N; i++) if (i < N - 1 || last_ok) issue(i);
@@ -1625,16 +1665,97 @@ __device__ __forceinline__ bool multi_taken(const RecvDev &rv, const int *__rest
     return f == 0;
 }
 
-template <int NG, bool FUSE, int NS, bool COMPACT /* `tab` holds compact descriptors, four ints per record (geometry_kernel's off4; desc_expand), not 128-int rows */>
+// ---- the plans of accumulate_multi_kernel (PlanSrc, kiwi_common.hpp).  At the top of every centroid group each of the kernel's waves
+// used to derive the group's parameters from the head records of its NS sources: NS lane-distributed record loads, some thirty
+// read-lanes, ballots over the sources' rows, the merge of their shift ranges, desc_expand's shuffle -- vector-pipe instructions all,
+// the same in the four waves of the sixteen (NS = 4) tile workgroups of a (source group, receiver) pair.  Here ONE thread does it per
+// (source group, receiver), once per evaluation, and walks the pair's centroid groups; the decisions are those of the kernel's own
+// loop top (the !PLAN branch there), statement for statement.
+template <int NS>
+__global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict__ recs, const int *__restrict__ cent_ofs, int isrc0, int nrec,
+    const RecvDev *__restrict__ recv, const int *__restrict__ off4, const int *__restrict__ pairflag, const int *__restrict__ mate,
+    const int *__restrict__ mate_wider, const int *__restrict__ plan_ofs, int4 *__restrict__ plan)
+{
+    constexpr int TILE = 1024 / NS, LDS_TILE = TILE + kHalo;
+    const int k = (int)blockIdx.x, s0 = NS * k, r = (int)(blockIdx.y * 64 + threadIdx.x);
+    if (r >= nrec) return;
+    const RecvDev &rv = recv[r];
+    if (!rv.enabled) return;
+    if (!multi_taken<NS>(rv, pairflag, mate, s0, nrec, r)) return;
+    if constexpr (NS == 2) { if (multi_taken<4>(rv, pairflag, mate_wider, s0, nrec, r)) return; }
+    const int cb = cent_ofs[isrc0];
+    const int nc = cent_ofs[isrc0 + s0 + 1] - cent_ofs[isrc0 + s0];
+    const size_t pbeg = (size_t)plan_ofs[k], pend = (size_t)plan_ofs[k + 1];      // (the host counted the groups: nothing is written past them)
+    size_t pi = pbeg + (size_t)r;
+    for (int c = 0; c < nc && pi < pend; pi += (size_t)nrec) {
+        const GeoRec *h[NS];
+        int smaxs[NS], smins[NS], npos = 0;
+        bool shared = true, same_rows = true;
+#pragma unroll
+        for (int i = 0; i < NS; i++) {
+            h[i] = recs + ((size_t)(cent_ofs[isrc0 + s0 + i] - cb) * nrec + (size_t)r * nc + c);
+            smaxs[i] = h[i]->ishift + ((h[i]->pad >> 8) & 0xff);
+            smins[i] = h[i]->ishift - ((h[i]->pad >> 16) & 0xff);
+            npos = max(npos, TILE + (smaxs[i] - smins[i]) + 8);
+            if (i > 0) {
+                same_rows = same_rows && h[i]->row[0] == h[0]->row[0] && h[i]->row[1] == h[0]->row[1] && h[i]->row[2] == h[0]->row[2] && h[i]->row[3] == h[0]->row[3];
+                shared = shared && smaxs[i] == smaxs[0];
+            }
+        }
+        shared = shared && same_rows;
+        if (same_rows && !shared) {
+            int smax_c = smaxs[0], smin_c = smins[0];
+#pragma unroll
+            for (int i = 1; i < NS; i++) { smax_c = max(smax_c, smaxs[i]); smin_c = min(smin_c, smins[i]); }
+            if (TILE + (smax_c - smin_c) + 8 <= LDS_TILE) {
+                shared = true;
+                npos = TILE + (smax_c - smin_c) + 8;
+#pragma unroll
+                for (int i = 0; i < NS; i++) smaxs[i] = smax_c;
+            }
+        }
+        const int glen = h[0]->pad & 0xff;
+        int4 *__restrict__ out = plan + pi * (kPlanStride / 16);
+#pragma unroll
+        for (int i = 0; i < NS; i++) {
+            const int4 o = *(const int4 *)(off4 + ((size_t)(cent_ofs[isrc0 + s0 + i] - cb) * nrec + (size_t)r * nc + c) * 4);
+            const int head = (h[i]->flags & 0xffff) | (glen << 16) | ((shared ? 1 : 0) << 23) | ((npos - TILE) << 24);
+            out[4 * i + 0] = make_int4(h[i]->row[0], h[i]->row[1], h[i]->row[2], h[i]->row[3]);
+            out[4 * i + 1] = o;
+            out[4 * i + 2] = make_int4(__float_as_int(h[i]->w[0]), __float_as_int(h[i]->w[1]), __float_as_int(h[i]->w[2]), __float_as_int(h[i]->w[3]));
+            out[4 * i + 3] = make_int4(smaxs[i], head, __float_as_int(h[i]->cl), __float_as_int(h[i]->sl));
+        }
+        if (glen < 1) break;
+        c += glen;
+    }
+}
+
+typedef const __attribute__((address_space(4))) v4i_t *plan_cptr;
+// Scalar loads whose only purpose is to bring the NS lines of a plan into the scalar data cache (see coef_warm).
+template <int NS>
+__device__ __forceinline__ int plan_warm(size_t p)
+{
+    int d;
+    if constexpr (NS == 4)
+        asm volatile("s_load_dword %0, %1, 0x0\n\ts_load_dword %0, %1, 0x40\n\ts_load_dword %0, %1, 0x80\n\ts_load_dword %0, %1, 0xc0" : "=&s"(d) : "s"(p) : "memory");
+    else
+        asm volatile("s_load_dword %0, %1, 0x0\n\ts_load_dword %0, %1, 0x40" : "=&s"(d) : "s"(p) : "memory");
+    return d;
+}
+
+template <int NG, bool FUSE, int NS, bool COMPACT /* `tab` holds compact descriptors, four ints per record (geometry_kernel's off4; desc_expand), not 128-int rows */,
+          bool PLAN /* the group loop's parameters come from multi_plan_kernel's plans (scalar loads), not from the head records */>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void accumulate_multi_kernel(
     const float *__restrict__ G, const int2 *__restrict__ span, int pitch,
     const GeoRec *__restrict__ recs, const int *__restrict__ cent_ofs, int isrc0, int nrec,
     const RecvDev *__restrict__ recv, float *__restrict__ syn, size_t syn_stride, int ntiles,
     const int *__restrict__ tab, const float *__restrict__ coefs, FuseParams fp, const int *__restrict__ pairflag, const int *__restrict__ mate,
-    const int *__restrict__ mate_wider /* NS = 2: the groups of four the wider launch has taken (or null) */)
+    const int *__restrict__ mate_wider /* NS = 2: the groups of four the wider launch has taken (or null) */,
+    const PlanSrc *__restrict__ plan, const int *__restrict__ plan_ofs /* PLAN: first plan of every source group (kiwi_common.hpp) */)
 {
     constexpr bool compact = COMPACT;
     static_assert(NS == 2 || NS == 4, "sources per workgroup");
+    static_assert(!PLAN || COMPACT, "plans hold compact descriptors");
     constexpr int TILE = 1024 / NS, LDS_TILE = TILE + kHalo, K = LDS_TILE / 64, WPS = 4 / NS;       // WPS: waves per source
     constexpr int SET = multi_set_stride<NG, NS>();
     __shared__ __attribute__((aligned(16))) float tiles[NS * SET];      // NS tile sets of NG rows of LDS_TILE floats
@@ -1678,18 +1799,45 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     auto tab_of = [&](int i) { return tab + (size_t)rbase[i] * (compact ? 4 : 128); };
     int c = 0;
     int cur[NS];
-#pragma unroll
-    for (int i = 0; i < NS; i++) cur[i] = rec_load(recs_of(i), 0, nc, lane);
     int ta = 0, tb = 0;                                   // (compact form: `ta` carries the four offsets until desc_expand at the group's top)
-    if constexpr (compact) ta = off4_load(tab_of(0), 0, lane);
-    else { ta = tab_of(0)[lane]; tb = tab_of(0)[64 + lane]; }
+    if constexpr (!PLAN) {
+#pragma unroll
+        for (int i = 0; i < NS; i++) cur[i] = rec_load(recs_of(i), 0, nc, lane);
+        if constexpr (compact) ta = off4_load(tab_of(0), 0, lane);
+        else { ta = tab_of(0)[lane]; tb = tab_of(0)[64 + lane]; }
+    }
     // halo: one lane per (4-sample chunk, component), chunk-major from the last thread down (see multi_build)
     const int hq = 255 - tid, hch = min(hq / NG, 15), hig = hq % NG, hph = TILE + 4 * hch;
+    // PLAN: this group's plan, a wave-uniform address in the constant address space (scalar loads); the next group's is kPlanStride nrec
+    // bytes on ([centroid group][receiver])
+    size_t pcur = 0;
+    if constexpr (PLAN) {
+        const size_t a = (size_t)plan + ((size_t)plan_ofs[blockIdx.x] + (size_t)r) * kPlanStride;
+        pcur = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
+    }
+    const int pstep = nrec * kPlanStride;
+    const int hoff = PLAN ? hig * pitch : 0;
+    auto plan4 = [&](int byte) { return *(plan_cptr)(pcur + (size_t)(unsigned)byte); };
     while (c < nc) {
         GeoRec g[NS];
         int smaxs[NS], smins[NS], npos = 0;
         bool shared = true, same_rows = true;
-        if constexpr (compact) desc_expand(ta, cur[0], lane, pitch, ta, tb);
+        int glen_p = 0;
+        DescPlan dp;
+        if constexpr (PLAN) {
+            // rows, offsets and tile origin of the first source (of all of them where the build is shared) and the group's header:
+            // three scalar loads from lines multi_plan_kernel wrote and the previous group's shadow() brought into the scalar cache
+            const v4i_t rw = plan4(0), of = plan4(16), tl = plan4(48);
+            g[0].row[0] = rw.x;
+            dp = DescPlan{ { 0, (rw.y - rw.x) * pitch, (rw.z - rw.x) * pitch, (rw.w - rw.x) * pitch }, { of.x, of.y, of.z, of.w }, pitch, hoff };
+            const unsigned head = (unsigned)tl.y;
+            glen_p = (int)((head >> 16) & 0x7fu);
+            shared = ((head >> 23) & 1u) != 0u;
+            npos = TILE + (int)(head >> 24);
+            smaxs[0] = tl.x;
+        }
+        if constexpr (compact && !PLAN) desc_expand(ta, cur[0], lane, pitch, ta, tb);
+        if constexpr (!PLAN) {
 #pragma unroll
         for (int i = 0; i < NS; i++) {
             // of the head record: blend weights, integer shift and group hint of every source; the four node rows of the first
@@ -1720,17 +1868,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                 for (int i = 0; i < NS; i++) smaxs[i] = smax_c;
             }
         }
-        const int glen = g[0].pad & 0xff;                // (same structure: equal for all)
+        }
+        const int glen = PLAN ? glen_p : (g[0].pad & 0xff);                // (same structure: equal for all)
         const int cend = c + glen;
         // this wave's source: what its apply needs (equal for all centroids of the group: same point, same receiver) -- fetched
         // in the shadow of the build's loads, like the blend weights
         int smax = smaxs[0];
+        if constexpr (PLAN) smax = plan4(64 * sh + 48).x;
+        else {
 #pragma unroll
-        for (int i = 1; i < NS; i++) if (sh == i) smax = smaxs[i];
-        int flags = 0, ishv = 0, warm_ = 0;
+            for (int i = 1; i < NS; i++) if (sh == i) smax = smaxs[i];
+        }
+        int flags = 0, ishv = 0, warm_ = 0, pwarm_ = 0;
         float gcl = 0.f, gsl = 0.f;
         const float *__restrict__ coef_grp = nullptr;
         auto shadow = [&]() {
+            if constexpr (PLAN) {
+                // the blend weights of every source and this wave's source's flags and rotation: scalar loads
+#pragma unroll
+                for (int i = 0; i < NS; i++) {
+                    const v4i_t w = plan4(64 * i + 32);
+                    g[i].w[0] = __int_as_float(w.x); g[i].w[1] = __int_as_float(w.y); g[i].w[2] = __int_as_float(w.z); g[i].w[3] = __int_as_float(w.w);
+                }
+                const v4i_t me = plan4(64 * sh + 48);
+                flags = me.y & 0xffff; gcl = __int_as_float(me.z); gsl = __int_as_float(me.w);
+                // the next group's plan on its way into the scalar cache (none behind the last group: nothing is read past the plans)
+                if (c + glen < nc) pwarm_ = plan_warm<NS>(pcur + (size_t)(unsigned)pstep);
+            } else {
 #pragma unroll
             for (int i = 0; i < NS; i++) { g[i].w[0] = REC_F(cur[i], 4); g[i].w[1] = REC_F(cur[i], 5); g[i].w[2] = REC_F(cur[i], 6); g[i].w[3] = REC_F(cur[i], 7); }
             int curme = cur[0];
@@ -1738,6 +1902,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             for (int i = 1; i < NS; i++) if (sh == i) curme = cur[i];
             flags = REC_I(curme, 18);
             gcl = REC_F(curme, 16); gsl = REC_F(curme, 17);
+            }
             if (lane < glen) ishv = rc[c + lane].ishift;
             // this group's coefficient lines (80 bytes per step, consecutive) on their way into the scalar cache
             const size_t crow = (base_me + c) * kCoefLine;
@@ -1747,33 +1912,47 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         };
         auto noshadow = []() {};
         // ---- build
-#define KIWI_MULTI_BUILD(TA, TB, I0, ONLY, NPOS, SHADOW) do { \
+#define KIWI_MULTI_BUILD(DESC, I0, ONLY, NPOS, SHADOW) do { \
             const int jb_ = t_tile0 - smaxs[I0] - 1;      /* LDS position p of a tile set holds its source's blended trace sample jb + p */ \
             const float *__restrict__ Gg = G + (size_t)g[I0].row[0] * (size_t)pitch; \
-            const bool lane_ok = lane >= 4 * NG || ((TA) + jb_ >= (TB) && (TA) + jb_ + LDS_TILE <= (TB) + pitch); \
-            const bool fast = __builtin_amdgcn_ballot_w64(lane_ok) == ~0ull; \
+            const bool fast = (DESC).fast(jb_, LDS_TILE, pitch, lane, NG); \
             const bool hact = hq < 16 * NG && hph < (NPOS); \
             const bool whalo = __builtin_amdgcn_ballot_w64(hact) != 0ull; \
-            if (fast) multi_build<NG, true, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, TA, TB, g, ONLY, hact, whalo, hig, hph, SHADOW); \
-            else      multi_build<NG, false, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, TA, TB, g, ONLY, hact, whalo, hig, hph, SHADOW); } while (0)
+            if (fast) multi_build<NG, true, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, SHADOW); \
+            else      multi_build<NG, false, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, SHADOW); } while (0)
         // A workgroup in its build phase is waiting for memory most of the time: its waves go first whenever they have an
         // instruction to issue (loads out early, the blend done as soon as the rows arrive), the workgroups that are applying
         // fill the rest of the issue slots.  Measured: cfg3 133.5 -> 127.2 ms per 4096 sources, cfg3-100pt 55.2 -> 51.3 (the
         // other way round -- apply first -- 137.8 / 57.5; priority 1, 2 and 3 alike).
         __builtin_amdgcn_s_setprio(1);
-        if (shared) KIWI_MULTI_BUILD(ta, tb, 0, -1, npos, shadow);
+        if constexpr (PLAN) {
+            if (shared) KIWI_MULTI_BUILD(dp, 0, -1, npos, shadow);
+            else {
+                KIWI_MULTI_BUILD(dp, 0, 0, npos, shadow);
+#pragma unroll
+                for (int i = 1; i < NS; i++) {           // (rows, offsets and tile origin of the others only here: not kept in registers)
+                    const v4i_t rw = plan4(64 * i), of = plan4(64 * i + 16);
+                    smaxs[i] = plan4(64 * i + 48).x;
+                    g[i].row[0] = rw.x;
+                    const DescPlan di{ { 0, (rw.y - rw.x) * pitch, (rw.z - rw.x) * pitch, (rw.w - rw.x) * pitch }, { of.x, of.y, of.z, of.w }, pitch, hoff };
+                    KIWI_MULTI_BUILD(di, i, i, npos, noshadow);
+                }
+            }
+            asm volatile("" :: "s"(pwarm_));             // (the warming loads' target register stays allocated until here)
+            pcur += (size_t)(unsigned)pstep;
+        } else {
+        if (shared) KIWI_MULTI_BUILD((DescLanes{ ta, tb }), 0, -1, npos, shadow);
         else {
-            KIWI_MULTI_BUILD(ta, tb, 0, 0, npos, shadow);
+            KIWI_MULTI_BUILD((DescLanes{ ta, tb }), 0, 0, npos, shadow);
 #pragma unroll
             for (int i = 1; i < NS; i++) {               // (descriptors of the others only here: not kept in registers)
                 int tai, tbi;
                 if constexpr (compact) desc_expand(off4_load(tab_of(i), c, lane), cur[i], lane, pitch, tai, tbi);
                 else { tai = tab_of(i)[(size_t)c * 128 + lane]; tbi = tab_of(i)[(size_t)c * 128 + 64 + lane]; }
                 g[i].row[0] = REC_I(cur[i], 0);
-                KIWI_MULTI_BUILD(tai, tbi, i, i, npos, noshadow);
+                KIWI_MULTI_BUILD((DescLanes{ tai, tbi }), i, i, npos, noshadow);
             }
         }
-#undef KIWI_MULTI_BUILD
         // head records and descriptors of the NEXT group: in flight while this group is applied
 #pragma unroll
         for (int i = 0; i < NS; i++) cur[i] = rec_load(recs_of(i), cend, nc, lane);
@@ -1781,6 +1960,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             if constexpr (compact) ta = off4_load(tab_of(0), cend, lane);
             else { ta = tab_of(0)[(size_t)cend * 128 + lane]; tb = tab_of(0)[(size_t)cend * 128 + 64 + lane]; }
         }
+        }
+#undef KIWI_MULTI_BUILD
         __syncthreads();
         __builtin_amdgcn_s_setprio(0);
         // ---- apply: this wave's source from its tile set.  (No tail rule and no partly added centroid here: multi_taken()

@@ -17,6 +17,8 @@ struct AccumArgs {
     const int *tab; const float *coefs; FuseParams fp;
     const int *pairflag, *synrow, *fam_ofs, *fam_list;
     int compact;                         // `tab` holds geometry_kernel's compact descriptors (four ints per record), not 128-int rows
+    const PlanSrc *plan = nullptr;       // accumulate_multi_kernel: the plans of THIS launch's source groups (multi_plan_kernel), or null: none
+    const int *plan_ofs = nullptr;       // ... and the index of every source group's first plan (one more entry than groups)
 };
 
 #define KIWI_ACCUM_LAUNCHERS                                                                                                      \
@@ -27,6 +29,8 @@ struct AccumArgs {
                         const int *mate4);                                                                                        \
     /* accumulate_multi_kernel<NG, FUSE, NS>: NS = 2 / 4 sources per workgroup */                                                 \
     void launch_multi(const AccumArgs &a, dim3 grid, int NS, int ntiles, const int *mate, const int *mate_wider);                \
+    /* multi_plan_kernel<NS>: the plans (a.plan_ofs, compact descriptors in a.tab) of the launch_multi that follows */            \
+    void launch_multi_plan(const AccumArgs &a, int NS, int ngroups, const int *mate, const int *mate_wider, PlanSrc *plan);      \
     /* accumulate_cell_kernel<NG, 256, 2, 0, FUSE> (tile shared by the workgroup) / accumulate_cellw_kernel (tile per wave) */    \
     void launch_cell(const AccumArgs &a, dim3 grid, int ntiles);                                                                  \
     void launch_cellw(const AccumArgs &a, dim3 grid, int ntiles);                                                                 \

@@ -508,7 +508,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Out &out)
         int n = 0;
         while (s + n < isrc0 + nsrc) {
             const size_t nc = (size_t)(c->cent_ofs[s + n + 1] - c->cent_ofs[s + n]);
-            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float) +
+            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s + n, (size_t)nrec) + c->syn_stride * sizeof(float) +
                                (size_t)nband * nmis * 2 * sizeof(float);
             if (n > 0 && (bytes + add > c->chunk_bytes_limit || n >= 65535)) break;
             if (c->fft_needed && n >= c->fft_cap) break;

@@ -114,6 +114,21 @@ struct ShakeRec {
 // the time steps of a sub-fault share cache lines and DRAM bursts (until round 3 each line sat alone in its record's 512-byte
 // descriptor row: 2.6 GB per cfg3 launch from HBM, and a third of geometry_kernel's writes).
 constexpr int kCoefLine = 20;      // floats per record in the coefficient array (ng = 8 uses the first 16)
+// Plan of accumulate_multi_kernel (compact descriptors only): what the kernel's group loop derives from the head records of its NS
+// sources at the top of a centroid group, already merged, written ONCE per evaluation by multi_plan_kernel (kiwi_accum.inc) for every
+// (group of NS sources, receiver, centroid group) multi_taken() admits, and read by the kernel through scalar loads.  One plan is
+// kPlanStride bytes (NS = 2 uses the first half), 16-byte aligned: a PlanSrc per source.  The plans of a source group are consecutive,
+// [centroid group][receiver]; plan_ofs[k] (host, run_chunk) is the index of the first plan of source group k.
+struct PlanSrc {
+    int   row[4];     // GeoRec::row of the group's head record
+    int   o[4];       // compact descriptor of the head record (geometry_kernel's off4): sample 0 inside the rows of node k
+    float w[4];       // GeoRec::w
+    int   smax;       // tile origin of this source's tile set: its own largest shift, or the common one of a shared build
+    int   head;       // GeoRec::flags & 0xffff | glen << 16 | shared << 23 | (npos - 1024 / NS) << 24   (glen, shared, npos: equal for all NS)
+    float cl, sl;     // GeoRec::cl, sl
+};
+static_assert(sizeof(PlanSrc) == 64, "PlanSrc layout");
+constexpr int kPlanStride = 256;   // bytes per plan
 template <int NG> __host__ __device__ constexpr int coef_wl(int a) { return 2 * a; }
 template <int NG> __host__ __device__ constexpr int coef_wr(int a) { return 2 * a + 1; }
 

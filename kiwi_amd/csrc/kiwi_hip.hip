@@ -216,11 +216,15 @@ struct kiwi_hip_ctx {
     std::vector<kiwi_hip_ctx *> mates;
     int cpu_share = 1;                // contexts that discretise at the same time: divides the discretiser's thread team
     std::vector<unsigned long long> struct_hash;   // per source: number of centroids and boundaries of its centroid groups (accumulate_multi_kernel's grouping)
+    std::vector<int> ngroups;                       // per source: number of centroid groups (non-zero entries of group_lens)
     std::vector<unsigned char> group_lens;          // per centroid: length of the centroid group that starts there, 0 inside a group (what struct_hash hashes)
     std::vector<int> first_shift;                  // per source: integer shift of its first centroid (groups of four: within 16 samples of each other,
                                                    // so that their groups can share a tile origin)
     std::vector<float> src_ends;                   // per source: position (north, east, depth) of its first and of its last centroid
     DevBuf<int> mate_d, mate4_d;
+    DevBuf<int> planofs_d;            // first plan of every group of four, then of every pair (kiwi_common.hpp PlanSrc), one more entry each
+    DevBuf<int4> plan_d;              // accumulate_multi_kernel's plans of a chunk: the groups of four, then the pairs
+    int multi_plan = 1;               // KIWI_HIP_MULTI_PLAN=0: accumulate_multi_kernel derives every group's parameters from the head records (A/B)
     int duo = 4;                      // accumulate_multi_kernel: up to this many consecutive sources of equal structure per workgroup
                                       // (4, 2, or 0 = off); env KIWI_HIP_DUO
     std::vector<char> single_group;
@@ -1024,6 +1028,14 @@ static int kiwi_quad_shift_span()
     return v;
 }
 
+// what source s adds to a chunk's workspace for accumulate_multi_kernel's plans at most: as one of a pair, half a plan per centroid
+// group and receiver (chunk sizing, KIWI_HIP_CHUNK_MB)
+size_t plan_bytes(const kiwi_hip_ctx *c, int s, size_t nrec)
+{
+    if (c->accum_mode != 0 || !c->duo || !c->multi_plan || !(c->db_simple && c->compact) || (size_t)s >= c->ngroups.size()) return 0;
+    return (size_t)c->ngroups[(size_t)s] * nrec * (kPlanStride / 2);
+}
+
 void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 {
     const int nrec = (int)c->recv.size();
@@ -1193,12 +1205,13 @@ void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
             // their origin times are within 16 samples of each other (their groups then share a tile origin: that of the largest
             // shift; further apart the four tile sets would be built one after the other -- two at a time then)
             bool duo = duo_maybe && !runs && !synrow && maxnc > 0;
-            bool any4 = false, any2 = false;
+            bool any4 = false, any2 = false, planned = false;
+            size_t plan_n4 = 0;                                          // plans of the groups of four
             if (duo) {
                 // (flags staged in pinned memory the context owns: the upload needs no stream synchronisation -- the host only waits,
                 // before it rewrites them for the next chunk, until the previous upload has been read)
                 const size_t n4 = (size_t)(nsrc + 3) / 4, n2 = (size_t)(nsrc + 1) / 2;
-                pin_ensure(c->mate_pin, c->mate_pin_n, n4 + n2);
+                pin_ensure(c->mate_pin, c->mate_pin_n, 2 * (n4 + n2) + 2);            // (flags, then the plan offsets: n4 + 1 and n2 + 1)
                 if (!c->mate_event) HIPCHECK(hipEventCreateWithFlags(&c->mate_event, hipEventDisableTiming));
                 else HIPCHECK(hipEventSynchronize(c->mate_event));
                 int *m4 = c->mate_pin, *m2 = c->mate_pin + n4;
@@ -1240,6 +1253,25 @@ void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
                     c->mate_d.ensure(n2, &c->dev_bytes);
                     HIPCHECK(hipMemcpyAsync(c->mate4_d.p, m4, n4 * sizeof(int), hipMemcpyHostToDevice, c->stream));
                     HIPCHECK(hipMemcpyAsync(c->mate_d.p, m2, n2 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+                    if (off4 && c->multi_plan) {
+                        // plans (multi_plan_kernel): a source group's are consecutive, one per (centroid group, receiver); the groups of
+                        // four first, the pairs behind them
+                        int *po = c->mate_pin + n4 + n2;
+                        size_t np = 0;
+                        auto ngroups = [&](int a) { return (size_t)c->ngroups[(size_t)a]; };
+                        for (size_t k = 0; k < n4; k++) { po[k] = (int)np; if (m4[k]) np += ngroups(isrc0 + 4 * (int)k) * (size_t)nrec; }
+                        po[n4] = (int)np;
+                        plan_n4 = np;
+                        for (size_t k = 0; k < n2; k++) { po[n4 + 1 + k] = (int)(np - plan_n4); if (m2[k]) np += ngroups(isrc0 + 2 * (int)k) * (size_t)nrec; }
+                        po[n4 + 1 + n2] = (int)(np - plan_n4);
+                        if (np * (kPlanStride / 16) < ((size_t)1 << 31)) {
+                            c->planofs_d.ensure(n4 + n2 + 2, &c->dev_bytes);
+                            c->plan_d.ensure((np + 1) * (kPlanStride / 16), &c->dev_bytes);
+                            HIPCHECK(hipMemcpyAsync(c->planofs_d.p, po, (n4 + n2 + 2) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+                            if (std::getenv("KIWI_HIP_POISON")) HIPCHECK(hipMemsetAsync(c->plan_d.p, 0x7f, (np + 1) * kPlanStride, c->stream));
+                            planned = true;
+                        }
+                    }
                     HIPCHECK(hipEventRecord(c->mate_event, c->stream));
                 }
             }
@@ -1270,8 +1302,16 @@ void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
             }
             // the (group of sources, receiver) combinations accumulate_multi_kernel takes; the grouped kernel behind it returns at once for those
             const int *m2p = any2 ? c->mate_d.p : (const int *)nullptr, *m4p = any4 ? c->mate4_d.p : (const int *)nullptr;
-            if (any4) { if (fusedar) fused::launch_multi(aa, qgrid, 4, ntiles_q, m4p, nullptr); else exact::launch_multi(aa, qgrid, 4, ntiles_q, m4p, nullptr); }
-            if (any2) { if (fusedar) fused::launch_multi(aa, dgrid, 2, ntiles_p, m2p, m4p); else exact::launch_multi(aa, dgrid, 2, ntiles_p, m2p, m4p); }
+            AccumArgs aa4 = aa, aa2 = aa;
+            if (planned) {
+                const size_t n4 = (size_t)(nsrc + 3) / 4;
+                aa4.plan = (const PlanSrc *)c->plan_d.p; aa4.plan_ofs = c->planofs_d.p;
+                aa2.plan = (const PlanSrc *)(c->plan_d.p + plan_n4 * (kPlanStride / 16)); aa2.plan_ofs = c->planofs_d.p + n4 + 1;
+                if (any4) { if (fusedar) fused::launch_multi_plan(aa4, 4, (int)qgrid.x, m4p, nullptr, (PlanSrc *)aa4.plan); else exact::launch_multi_plan(aa4, 4, (int)qgrid.x, m4p, nullptr, (PlanSrc *)aa4.plan); }
+                if (any2) { if (fusedar) fused::launch_multi_plan(aa2, 2, (int)dgrid.x, m2p, m4p, (PlanSrc *)aa2.plan); else exact::launch_multi_plan(aa2, 2, (int)dgrid.x, m2p, m4p, (PlanSrc *)aa2.plan); }
+            }
+            if (any4) { if (fusedar) fused::launch_multi(aa4, qgrid, 4, ntiles_q, m4p, nullptr); else exact::launch_multi(aa4, qgrid, 4, ntiles_q, m4p, nullptr); }
+            if (any2) { if (fusedar) fused::launch_multi(aa2, dgrid, 2, ntiles_p, m2p, m4p); else exact::launch_multi(aa2, dgrid, 2, ntiles_p, m2p, m4p); }
             const int pairsel = cell ? 1 : (duo ? 3 : 0);
             if (fusedar) fused::launch_grouped(aa, ggrid, T, ntiles, runs, pairsel, m2p, m4p);
             else         exact::launch_grouped(aa, ggrid, T, ntiles, runs, pairsel, m2p, m4p);
@@ -1444,7 +1484,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
             const size_t nc = (size_t)(c->cent_ofs[s + n + 1] - c->cent_ofs[s + n]);
             const size_t syn_bytes = c->fuse_now ? (size_t)c->nmis * 64 * sizeof(double)
                                                              : c->syn_stride * sizeof(float) * ((proc_which ? 2 : 1) + (c->floating ? 1 : 0));
-            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + syn_bytes;
+            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + syn_bytes + plan_bytes(c, s + n, (size_t)nrec);
             if (n > 0 && (bytes + add > c->chunk_bytes_limit || n >= 65535)) break;
             if (c->fft_needed && n >= c->fft_cap) break;
             bytes += add; n++;
@@ -1518,6 +1558,7 @@ int kiwi_hip_init(int device, kiwi_hip_ctx **out)
         if (const char *m = std::getenv("KIWI_HIP_ACCUM")) c->accum_mode = (std::strcmp(m, "direct") == 0) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_FUSE")) c->fuse_enabled = std::atoi(m);
         if (const char *m = std::getenv("KIWI_HIP_DUO")) { const int v = std::atoi(m); c->duo = v >= 4 ? 4 : (v >= 1 ? 2 : 0); }
+        if (const char *m = std::getenv("KIWI_HIP_MULTI_PLAN")) c->multi_plan = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_CELL")) c->cell_mode = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_DEDUPE")) c->dedupe_enabled = std::atoi(m);      // 0 off, 1 default, 2 also for point sources
         if (const char *m = std::getenv("KIWI_HIP_FUSED_FFT")) c->fused_fft = std::atoi(m) != 0;   // 0: amplitude spectra through hipFFT
@@ -2041,6 +2082,7 @@ int kiwi_hip_set_sources(kiwi_hip_ctx *c, int nsrc, const int *cent_ofs, const f
     c->geo_hash.assign((size_t)nsrc, 0ull);
     c->struct_hash.assign((size_t)nsrc, 0ull);
     c->group_lens.assign(ntot, 0);
+    c->ngroups.assign((size_t)nsrc, 0);
     c->first_shift.assign((size_t)nsrc, 0);
     c->src_ends.assign((size_t)nsrc * 6, 0.f);
     c->single_group.assign((size_t)nsrc, 0);
@@ -2082,6 +2124,7 @@ int kiwi_hip_set_sources(kiwi_hip_ctx *c, int nsrc, const int *cent_ofs, const f
                 }
                 hs ^= (unsigned)len; hs *= 1099511628211ull;
                 c->group_lens[(size_t)cent_ofs[s] + k] = (unsigned char)len;
+                c->ngroups[(size_t)s]++;
                 k += len;
             }
             c->geo_hash[s] = h;

@@ -417,7 +417,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             size_t add = 0;
             for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
                 const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float) * 2;
+                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float) * 2;
             }
             add += (size_t)nrec * (NN + (rb && rb->mode == 1 ? NN + 2 : 0)) * sizeof(double);
             if (cd) add += cand_bytes(*cd, nrec);

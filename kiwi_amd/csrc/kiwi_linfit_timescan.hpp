@@ -280,7 +280,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
             size_t add = 0;
             for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
                 const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + c->syn_stride * sizeof(float);
+                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float);
             }
             add += (size_t)nk * nrec * NN * sizeof(double);
             if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
