@@ -3,6 +3,7 @@ and to the product (kiwi_amd.Engine)."""
 import numpy as np
 
 import os
+import re
 
 from kiwi_amd import synthetic
 from oracle import ko
@@ -98,13 +99,14 @@ def arith():
     return os.environ.get("KIWI_HIP_ARITH", "exact")
 
 
-def misfit_close(a, b, norm=None, glob=False):
+def misfit_close(a, b, norm=None, glob=False, rtol=None):
     """Device misfits a against oracle misfits b.  exact: |a - b| <= 1e-6 |b| per value.  fused: a misfit is the norm of a
     DIFFERENCE of traces, its round-off scales with the traces (the norm factor), not with itself -- a trial next to the true
     source has a misfit far below its norm factor --: |a - b| <= 1e-6 max(|b|, norm factor) per slot, `norm` = the slots' norm
     factors (required: there is no other floor).  glob=True: a, b are GLOBAL misfits g = |m| / |n| (minimizer_engine.f90:936-942),
     normalised by construction -- the same rule with norm factor 1: from |dm_i| <= 1e-6 max(m_i, n_i) follows
-    |dg| <= 1e-6 sqrt(g^2 + 1)."""
+    |dg| <= 1e-6 sqrt(g^2 + 1).  rtol: another factor than MISFIT_RTOL in the same rule, for a caller that states why."""
+    rtol = MISFIT_RTOL if rtol is None else rtol
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     scale = np.maximum(np.abs(b), 1e-30)
@@ -114,7 +116,13 @@ def misfit_close(a, b, norm=None, glob=False):
         else:
             assert norm is not None, "fused contract: per-slot misfits are compared on the scale of their norm factors"
             scale = np.maximum(scale, np.abs(np.asarray(norm, np.float64)))
-    return bool(np.all(np.abs(a - b) <= MISFIT_RTOL * scale))
+    return bool(np.all(np.abs(a - b) <= rtol * scale))
+
+
+def multi_groups(stderr_text):
+    """[(sources of the chunk, groups of four, pairs)] of every chunk whose grouping for accumulate_multi_kernel the library reported
+    (KIWI_HIP_DEBUG=1: one line per chunk that was considered at all)"""
+    return [tuple(int(v) for v in t) for t in re.findall(r"chunk of (\d+) sources: (\d+) groups of four, (\d+) pairs", stderr_text)]
 
 
 def same_bits(a, b):

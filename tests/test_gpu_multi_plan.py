@@ -5,14 +5,12 @@ and global misfits, bit for bit under `exact`, within the contract's tolerances 
 The trial sources are centroid tables cut from discretised bilateral sources -- a few points with a few time steps each -- so that every
 case is a handful of centroid groups of known length, on a database of 16 x 5 nodes with 1100 samples (two 512-sample tiles, five
 256-sample tiles, the last one partial) and three receivers."""
-import re
-
 import numpy as np
 import pytest
 
 from kiwi_amd import synthetic
 from kiwi_amd.engine import discretize
-from tests.common import Scenario, arith, misfit_close, same_bits
+from tests.common import Scenario, arith, misfit_close, multi_groups, same_bits
 
 DT = 0.5                  # sample interval of the synthetic database
 STEPS = 5                 # time steps per point of the discretised bilateral source below
@@ -60,9 +58,9 @@ def _evaluate(sc, tables, moments, monkeypatch, capfd, plan, duo):
     syn = [p.get_synthetics(s, ir, k, 1)[1].copy() for s in range(len(tables)) for ir in range(1, sc.nrec + 1)
            for k in range(1, len(sc.comps[ir - 1]) + 1)]
     p.close()
-    taken = re.findall(r"chunk of (\d+) sources: (\d+) groups of four, (\d+) pairs", capfd.readouterr().err)
-    n4 = max((int(t[1]) for t in taken), default=0)
-    n2 = max((int(t[2]) for t in taken), default=0)
+    taken = multi_groups(capfd.readouterr().err)
+    n4 = max((t[1] for t in taken), default=0)
+    n2 = max((t[2] for t in taken), default=0)
     return syn, m, n, g, n4, n2
 
 
