@@ -617,6 +617,58 @@ int kiwi_hip_get_linear_fit_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
 /* how the candidate kernel walks its work: *candidates_per_workgroup (one per lane), *receivers_per_stage rows of sums per LDS
  * stage; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage);
+/* ---- the candidate evaluation at MANY ORIGIN TIMES from one synthesis of the basis
+ * (kiwi_amd/csrc/kiwi_linfit_candidates_timescan.hpp): the best double couple, depth and origin time from six syntheses per location.
+ * Nothing new is defined.  Groups, K, receiver_weight and anarchy are kiwi_hip_linear_fit's; the offsets k0 + j kstep, j < nk, and
+ * their limits are kiwi_hip_time_scan's; the sums of offset j are kiwi_hip_linear_fit_time_scan's (the same Gram-scan kernel, the
+ * same solve); the misfit of candidate c at offset j, its free_scale scale and its receiver_misfit are
+ * kiwi_hip_linear_fit_candidates' expressions on those sums, operation for operation.  candidates [ncand][K] is shared by all
+ * groups and offsets.
+ *   best_index  [ngroup][nk], best_misfit [ngroup][nk]   per offset, in the candidate call's total order: NaN passed over, the
+ *                          smaller value, the LOWEST candidate index
+ *   best_offset [ngroup]   the j of the smallest best_misfit[g][j] among the j with best_index[g][j] >= 0, the lowest j among equal
+ *                          values; -1 if there is none
+ *   best_scale  [ngroup][nk] or NULL (free_scale only): a = (u.b) / (u.G.u) of the winner on the folded sums of (g, j): the bits
+ *                          scale[g][j][best_index[g][j]] has; NaN where there is no winner
+ *   status      [ngroup]   0 evaluated; 1 no data; 2 a basis source failed to discretise (NaN, -1 indices, zeros per receiver); it does
+ *                          not depend on the offset, because R_r does not
+ *   cand_misfit [ngroup][ncand] or NULL: each candidate's smallest misfit over the offsets, j ascending, NaN passed over, the first
+ *                          j among equal values -- the mechanism cube with the origin time profiled out --; cand_offset
+ *                          [ngroup][ncand] or NULL: that j (NaN and -1 where every offset is NaN); cand_scale [ngroup][ncand] or NULL
+ *                          (free_scale only): the scale at that j
+ *   misfit, scale  [ngroup][nk][ncand] or NULL;  receiver_misfit  float [ngroup][nk][ncand][nrec] or NULL
+ *   receiver_norm  float [ngroup][nrec] or NULL: one row per group; with receiver_misfit read as nk x ncand "sources" they are what
+ *                          kiwi_hip_outer_misfits takes: the bootstrap over mechanism and origin time jointly
+ *   fit_coef [ngroup][nk][K], fit_misfit [ngroup][nk], fit_status [ngroup][nk], each or NULL: kiwi_hip_linear_fit_time_scan's coef,
+ *                          misfit and status
+ * Equalities: offset 0 with nk = 1 is kiwi_hip_linear_fit_candidates bit for bit; offset k is bit for bit
+ * kiwi_hip_linear_fit_candidates on a context whose references and tapers are moved by -k samples (under KIWI_ARITH_EXACT; under
+ * KIWI_ARITH_FUSED as stated for kiwi_hip_linear_fit_time_scan).  The answer does not depend on how candidates and receivers are
+ * tiled, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.  Afterwards the context is what
+ * kiwi_hip_linear_fit_time_scan leaves.  Refused with a message that starts with "linear_fit_candidates_time_scan:", nothing
+ * approximated: everything kiwi_hip_linear_fit_time_scan and kiwi_hip_linear_fit_candidates refuse; best_scale or cand_scale
+ * without free_scale; cand_offset without cand_misfit. */
+int kiwi_hip_linear_fit_candidates_time_scan(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                             const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                             int free_scale, int *best_offset, int *best_index, double *best_misfit, double *best_scale,
+                                             int *status, double *cand_misfit, int *cand_offset, double *cand_scale, double *misfit,
+                                             double *scale, float *receiver_misfit, float *receiver_norm, double *fit_coef,
+                                             double *fit_misfit, int *fit_status);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_candidates_time_scan_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                    int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                    const double *receiver_weight, int anarchy, int free_scale, int *best_offset,
+                                                    int *best_index, double *best_misfit, double *best_scale, int *status,
+                                                    double *cand_misfit, int *cand_offset, double *cand_scale, double *misfit,
+                                                    double *scale, float *receiver_misfit, float *receiver_norm, double *fit_coef,
+                                                    double *fit_misfit, int *fit_status);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram-scan kernel, ms[2] solve kernels,
+ * ms[3] candidate-scan kernels, ms[4] downloads */
+int kiwi_hip_get_linear_fit_candidates_time_scan_ms(kiwi_hip_ctx *ctx, float ms[5]);
+/* how the candidate-scan kernel walks its work: *candidates_per_workgroup (one per lane), *receivers_per_stage rows of sums per LDS
+ * stage; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -272,6 +272,7 @@ struct kiwi_hip_ctx {
     TimeScanState timescan_state;
     float timescan_ms[3] = { 0.f, 0.f, 0.f };         // evaluation, scan kernels, downloads of the last kiwi_hip_time_scan
     float linfit_timescan_ms[4] = { 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, downloads of the last kiwi_hip_linear_fit_time_scan
+    float linfit_cand_timescan_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, candidate-scan kernels, downloads of the last kiwi_hip_linear_fit_candidates_time_scan
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
@@ -1509,6 +1510,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_bands.hpp"
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
+#include "kiwi_linfit_candidates_timescan.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2865,10 +2867,23 @@ struct FitScanCall { int K; const double *weight; int anarchy; linfit_timescan::
 // (kiwi_hip_linear_fit_candidates_params the same with `cand` set: groups of K basis sources as for `fit`, a piece is evaluated by
 // linfit::run with the candidates behind its l2 kernels)
 struct CandCall { int K; const double *weight; int anarchy; linfit::Out out; linfit::Candidates cand; };
+// (kiwi_hip_linear_fit_candidates_time_scan_params the same with `candscan` set: groups of K basis sources as for `fit`, a piece is
+// evaluated by linfit_candidates_timescan::run)
+struct CandScanCall {
+    int K; const double *weight; int anarchy; linfit_timescan::Out out; linfit_candidates_timescan::Scan scan; timescan::Offsets of;
+    CandScanCall at(size_t g, size_t nrec) const
+    {
+        CandScanCall s = *this;
+        s.out = out.at(g, (size_t)K, (size_t)of.nk);
+        s.scan = scan.at(g, (size_t)of.nk, nrec);
+        return s;
+    }
+};
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
-                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr)
+                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
+                           const CandScanCall *candscan = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2880,8 +2895,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (scan) timescan::check_setup(c, scan->of.k0, scan->of.kstep, scan->of.nk);
     if (fitscan) linfit_timescan::check_setup(c, fitscan->K, fitscan->of, fitscan->out);
     if (cand) { linfit::check_candidates(cand->cand, cand->K); linfit::check_setup(c, cand->K, cand->out); }
+    if (candscan) linfit_candidates_timescan::check_setup(c, candscan->K, candscan->of, candscan->out, candscan->scan);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2912,16 +2928,19 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool canding = cand != nullptr;
             CandCall mine_cand{};
             if (canding) { mine_cand = *cand; mine_cand.out = cand->out.at(s0 / unit, unit, nrec_all); mine_cand.cand = cand->cand.at(s0 / unit, nrec_all); }
+            const bool candscanning = candscan != nullptr;
+            const CandScanCall mine_candscan = candscanning ? candscan->at((size_t)(s0 / unit), (size_t)nrec_all) : CandScanCall{};
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
-                                       fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr);
+                                       fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
+                                       candscanning ? &mine_candscan : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3056,6 +3075,11 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                 linfit::fill_failed(n / unit, unit, nrec_all, cand->out.at(s0 / unit, unit, nrec_all));
                 linfit::cand_fill_failed(n / unit, nrec_all, cand->cand.at(s0 / unit, nrec_all));
             }
+            if (candscan) {
+                const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);
+                linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)mine.of.nk, mine.out);
+                linfit_candidates_timescan::fill_failed((size_t)(n / unit), (size_t)mine.of.nk, (size_t)nrec_all, mine.scan);
+            }
             continue;
         }
         upload_batch(c, hb);
@@ -3068,6 +3092,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         else if (cand) {
             const linfit::Candidates mine = cand->cand.at(s0 / unit, nrec_all);
             linfit::run(c, 0, n / unit, unit, cand->weight, cand->anarchy, cand->out.at(s0 / unit, unit, nrec_all), nullptr, nullptr, &mine);
+        } else if (candscan) {
+            const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);
+            linfit_candidates_timescan::run(c, 0, n / unit, unit, mine.of, mine.weight, mine.anarchy, mine.out, mine.scan);
         } else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3364,6 +3391,86 @@ int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, i
     if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !receivers_per_stage) return 1;
     *candidates_per_workgroup = linfit::kCandThreads;
     *receivers_per_stage = linfit::kCandStage;
+    return 0;
+}
+
+// The candidate evaluation at many origin times from one synthesis of the basis (kiwi_linfit_candidates_timescan.hpp).  The free fit
+// per offset is made on the way; where the caller does not want it, it goes to arrays of this call
+struct CandScanFitArrays {
+    std::vector<double> coef, misfit;
+    std::vector<int> status;
+    linfit_timescan::Out out(int ngroup, int K, int nk, double *fit_coef, double *fit_misfit, int *fit_status)
+    {
+        const size_t n = std::max<size_t>((size_t)std::max(ngroup, 0) * (size_t)std::max(nk, 0), 1);       // (never null: the refusals name nk)
+        if (!fit_coef) coef.resize(n * K);
+        if (!fit_misfit) misfit.resize(n);
+        if (!fit_status) status.resize(n);
+        return linfit_timescan::Out{ fit_coef ? fit_coef : coef.data(), fit_misfit ? fit_misfit : misfit.data(),
+                                     fit_status ? fit_status : status.data(), nullptr, nullptr, nullptr };
+    }
+};
+
+static const char *const kCandScanBasis = "linear_fit_candidates_time_scan: K = ";
+
+int kiwi_hip_linear_fit_candidates_time_scan(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                             const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                             int free_scale, int *best_offset, int *best_index, double *best_misfit, double *best_scale,
+                                             int *status, double *cand_misfit, int *cand_offset, double *cand_scale, double *misfit,
+                                             double *scale, float *receiver_misfit, float *receiver_norm, double *fit_coef,
+                                             double *fit_misfit, int *fit_status)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->linfit_cand_timescan_ms) t = 0.f;
+    if (K < 1 || K > linfit::kMaxBasis)
+        throw std::runtime_error(kCandScanBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    const linfit_candidates_timescan::Scan sc{ candidates, ncand, outer_norm, free_scale, best_offset, best_index, best_misfit, best_scale,
+                                               status, cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm };
+    CandScanFitArrays fa;
+    linfit_candidates_timescan::run(c, isrc0, ngroup, K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy,
+                                    fa.out(ngroup, K, nk, fit_coef, fit_misfit, fit_status), sc);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_candidates_time_scan_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                    int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                    const double *receiver_weight, int anarchy, int free_scale, int *best_offset,
+                                                    int *best_index, double *best_misfit, double *best_scale, int *status,
+                                                    double *cand_misfit, int *cand_offset, double *cand_scale, double *misfit, double *scale,
+                                                    float *receiver_misfit, float *receiver_norm, double *fit_coef, double *fit_misfit,
+                                                    int *fit_status)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, kCandScanBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "linear_fit_candidates_time_scan: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->linfit_cand_timescan_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_timescan_ms) t = 0.f;
+    CandScanFitArrays fa;
+    const CandScanCall candscan{ K, receiver_weight, anarchy, fa.out(ngroup, K, nk, fit_coef, fit_misfit, fit_status),
+                                 linfit_candidates_timescan::Scan{ candidates, ncand, outer_norm, free_scale, best_offset, best_index,
+                                                                   best_misfit, best_scale, status, cand_misfit, cand_offset, cand_scale,
+                                                                   misfit, scale, receiver_misfit, receiver_norm },
+                                 timescan::Offsets{ k0, kstep, nk } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, &candscan);
+}
+
+int kiwi_hip_get_linear_fit_candidates_time_scan_ms(kiwi_hip_ctx *c, float ms[5])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 5; i++) ms[i] = c->linfit_cand_timescan_ms[i];
+    return 0;
+}
+
+int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !receivers_per_stage) return 1;
+    *candidates_per_workgroup = linfit_candidates_timescan::kCandThreads;
+    *receivers_per_stage = linfit_candidates_timescan::kCandStage;
     return 0;
 }
 

@@ -22,6 +22,9 @@ RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
 ScanFit = collections.namedtuple("ScanFit", "coef misfit status pivot_min best normal")
 CandidateScan = collections.namedtuple("CandidateScan", "best_index best_misfit status misfit scale receiver_misfit receiver_norm "
                                                         "fit_coef fit_misfit")
+CandidateTimeScan = collections.namedtuple("CandidateTimeScan", "best_offset best_index best_misfit best_scale status cand_misfit cand_offset "
+                                                                "cand_scale misfit scale receiver_misfit receiver_norm fit_coef fit_misfit "
+                                                                "fit_status")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -970,6 +973,89 @@ class Engine:
         downloads)."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_candidates_ms(self.h, _fp(ms)), "get_linear_fit_candidates_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)
+    def linear_fit_candidates_time_scan_shape(self, K):
+        """(candidates per workgroup, receivers per LDS stage) of the candidate-scan kernel for K basis sources."""
+        c, s = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_linear_fit_candidates_time_scan_shape(int(K), _ip(c), _ip(s)):
+            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(s[0])
+
+    def _candidate_scan_arrays(self, ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit, receiver_misfit):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != int(K):
+            raise KiwiHipError("linear_fit_candidates_time_scan: candidates must be [ncand, K = %d]" % int(K))
+        ng, K, nj, nc, nrec = int(ngroup), int(K), max(int(nk), 0), len(x), len(self.components)
+        free = bool(free_scale)
+        out = CandidateTimeScan(np.zeros(ng, np.int32), np.zeros((ng, nj), np.int32), np.zeros((ng, nj)),
+                                np.zeros((ng, nj)) if free else None, np.zeros(ng, np.int32),
+                                np.zeros((ng, nc)) if marginal else None, np.zeros((ng, nc), np.int32) if marginal else None,
+                                np.zeros((ng, nc)) if marginal and free else None,
+                                np.zeros((ng, nj, nc)) if misfit else None, np.zeros((ng, nj, nc)) if misfit and free else None,
+                                np.zeros((ng, nj, nc, nrec), np.float32) if receiver_misfit else None,
+                                np.zeros((ng, nrec), np.float32) if receiver_misfit else None,
+                                np.zeros((ng, nj, K)), np.zeros((ng, nj)), np.zeros((ng, nj), np.int32))
+        ipn = lambda a: None if a is None else _ip(a)                                  # noqa: E731
+        fpn = lambda a: None if a is None else _fp(a)                                  # noqa: E731
+        tail = (nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_offset), _ip(out.best_index), dp(out.best_misfit), dp(out.best_scale), _ip(out.status),      # noqa: E731
+                        dp(out.cand_misfit), ipn(out.cand_offset), dp(out.cand_scale), dp(out.misfit), dp(out.scale),
+                        fpn(out.receiver_misfit), fpn(out.receiver_norm), dp(out.fit_coef), dp(out.fit_misfit), _ip(out.fit_status))
+        return tail, out, outs
+
+    def linear_fit_candidates_time_scan(self, isrc0, ngroup, K, candidates, k0=0, kstep=1, nk=1, outer_norm="l1norm", receiver_weights=None,
+                                        anarchy=False, free_scale=False, marginal=True, misfit=False, receiver_misfit=False):
+        """`linear_fit_candidates` at the origin-time offsets (k0 + j kstep) dt, j < nk, from ONE synthesis of the basis sources
+        (kiwi_hip_linear_fit_candidates_time_scan): `linear_fit_time_scan`'s sums per offset, `linear_fit_candidates`' evaluation
+        on them.  Returns a `CandidateTimeScan`: best_offset[ngroup] (-1: none), best_index[ngroup, nk] (-1: none),
+        best_misfit[ngroup, nk], best_scale[ngroup, nk] (free_scale), status[ngroup]; cand_misfit, cand_offset[ngroup, ncand]
+        (marginal=True: every candidate's smallest misfit over the offsets and where) and cand_scale (free_scale);
+        misfit[ngroup, nk, ncand] (misfit=True) and scale (free_scale); receiver_misfit[ngroup, nk, ncand, nrec] and
+        receiver_norm[ngroup, nrec] float32 (receiver_misfit=True); fit_coef[ngroup, nk, K], fit_misfit and fit_status[ngroup, nk]:
+        `linear_fit_time_scan` of the same groups.  Arrays not asked for are None."""
+        tail, out, outs = self._candidate_scan_arrays(ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit,
+                                                      receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *tail,
+                                                                 1 if anarchy else 0, 1 if free_scale else 0, *outs()),
+                 "linear_fit_candidates_time_scan")
+        return out
+
+    def linear_fit_candidates_time_scan_params(self, sourcetype, params, K, candidates, k0=0, kstep=1, nk=1, outer_norm="l1norm",
+                                               receiver_weights=None, anarchy=False, free_scale=False, marginal=True, misfit=False,
+                                               receiver_misfit=False, piece=0):
+        """`linear_fit_candidates_time_scan` for a parameter list of any length, cut into pieces and over the devices at group
+        boundaries as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        tail, out, outs = self._candidate_scan_arrays(ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit,
+                                                      receiver_misfit)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_candidates_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep),
+                                                                            int(nk), *tail, 1 if anarchy else 0, 1 if free_scale else 0,
+                                                                            *outs()), "linear_fit_candidates_time_scan")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_candidates_time_scan_ms(self):
+        """HIP-event durations [ms] of the last `linear_fit_candidates_time_scan`: (evaluation, Gram-scan kernel, solve kernels,
+        candidate-scan kernels, downloads)."""
+        ms = np.zeros(5, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_time_scan_ms(self.h, _fp(ms)), "get_linear_fit_candidates_time_scan_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ robust linear fit (kiwi_hip_linear_fit_robust)

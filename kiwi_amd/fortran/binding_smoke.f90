@@ -34,6 +34,10 @@ program binding_smoke
     if (kiwi_hip_linear_fit_candidates_shape( 6_c_int, per_group, per_stage ) /= 0) stop 7
     if (per_group < 64 .or. per_stage < 1) stop 8
 
+    ! the candidate-scan kernel of the time scan has a shape of its own
+    if (kiwi_hip_linear_fit_candidates_time_scan_shape( 6_c_int, per_group, per_stage ) /= 0) stop 9
+    if (per_group < 64 .or. per_stage < 1) stop 10
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

@@ -605,6 +605,60 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, receivers_per_stage
         end function
 
+        ! the candidate evaluation at nk origin-time offsets k0 + j kstep from one synthesis of the basis sources
+        integer(c_int) function kiwi_hip_linear_fit_candidates_time_scan( ctx, isrc0, ngroup, k, k0, kstep, nk, ncand, candidates, &
+                outer_norm, receiver_weight, anarchy, free_scale, best_offset, best_index, best_misfit, best_scale, status, &
+                cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm, fit_coef, fit_misfit, &
+                fit_status ) bind(C, name='kiwi_hip_linear_fit_candidates_time_scan')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, k0, kstep, nk, ncand, outer_norm, anarchy, free_scale
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_offset(*) ! (ngroup): 0-based offset index, -1 if none
+            integer(c_int), intent(out) :: best_index(*)  ! (nk, ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (nk, ngroup)
+            type(c_ptr), value :: best_scale              ! c_loc of real(c_double) (nk, ngroup), or c_null_ptr; free_scale only
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: cand_misfit, cand_scale ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: cand_offset             ! c_loc of integer(c_int) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: misfit, scale           ! c_loc of real(c_double) (ncand, nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: receiver_misfit         ! c_loc of real(c_float) (nrec, ncand, nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: receiver_norm           ! c_loc of real(c_float) (nrec, ngroup), or c_null_ptr
+            type(c_ptr), value :: fit_coef, fit_misfit    ! c_loc of real(c_double) (k, nk, ngroup) and (nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: fit_status              ! c_loc of integer(c_int) (nk, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_time_scan_params( ctx, sourcetype, ngroup, k, params, piece, k0, kstep, &
+                nk, ncand, candidates, outer_norm, receiver_weight, anarchy, free_scale, best_offset, best_index, best_misfit, &
+                best_scale, status, cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm, fit_coef, &
+                fit_misfit, fit_status ) bind(C, name='kiwi_hip_linear_fit_candidates_time_scan_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, k0, kstep, nk, ncand, outer_norm, anarchy, free_scale
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_offset(*), best_index(*), status(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: best_scale, cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm, &
+                                  fit_coef, fit_misfit, fit_status       ! as in kiwi_hip_linear_fit_candidates_time_scan
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_candidates_time_scan_ms( ctx, ms ) &
+                bind(C, name='kiwi_hip_get_linear_fit_candidates_time_scan_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(5)                 ! evaluation, Gram-scan kernel, solve kernels, candidate-scan kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_time_scan_shape( k, candidates_per_workgroup, receivers_per_stage ) &
+                bind(C, name='kiwi_hip_linear_fit_candidates_time_scan_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, receivers_per_stage
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -194,6 +194,54 @@ class MisfitGrid:
         self.ibest = int(np.nanargmin(self.fit_misfits)) if np.any(np.isfinite(self.fit_misfits)) else 0
         self.best_source = self.sources[self.ibest]
 
+    def compute_dc_time_scan(self, engine, strikes, dips, rakes, moment=None, outer_norm="l1norm", dt=None, cube=False):
+        """The best double couple over strikes x dips x rakes at every node of a grid with a `time` axis, from six syntheses per
+        node of the grid WITHOUT that axis (`mtfit.scan_double_couples_time_scan`, kiwi_hip_linear_fit_candidates_time_scan).  The
+        grid is as `compute_mt_time_scan` asks: exactly one `time` axis that `split_time_axis` accepts, no tensor axes, every node
+        switched on, source type `moment_tensor` or `mt_eikonal`; the engine's method is l2norm, `outer_norm` combines the
+        receivers; moment=None finds every mechanism's best moment (outer l2norm only).  Fills, in grid order, `dc_sdr` [n, 3],
+        `dc_moments`, `dc_misfits`, `dc_index` (the mechanism's row in the grid of mechanisms, -1: none), `dc_status`, the tensor
+        columns of `sources` (the best double couple of the node), `ibest`, `best_source`, `misfits_by_s` and `syntheses_saved`
+        (against one synthesis per mechanism and node); cube=True also `dc_cube` [nodes without time, ns, nd, nr] and
+        `dc_cube_offset`: every mechanism's smallest misfit over the time axis and where."""
+        from . import mtfit
+        c0 = mtfit.TENSOR_COLUMN.get(SOURCE_TYPES.get(self.sourcetype, self.sourcetype))
+        if c0 is None or any(p in mtfit.COMPONENTS for p in self.sourceparams):
+            raise KiwiHipError("linear_mt: the source type must be moment_tensor or mt_eikonal and the grid must not run over tensor components")
+        axes = [i for i, (p, _) in enumerate(self.param_values) if p == "time"]
+        if len(axes) != 1:
+            raise ValueError("time_scan: the grid needs exactly one `time` axis")
+        ax = axes[0]
+        split = split_time_axis(self.param_values[ax][1], engine.dt if dt is None else dt)
+        if split is None:
+            raise ValueError("time_scan: the time axis is not evenly spaced by a whole number of samples")
+        k0, kstep, nk = split
+        dims = [len(v) for _, v in self.param_values]
+        if int(np.prod(dims)) != len(self.sources):
+            raise ValueError("time_scan: source constraints have switched grid nodes off; the scan needs the full grid")
+        idx = np.arange(len(self.sources)).reshape(dims)
+        first = np.take(idx, 0, axis=ax).ravel()                       # nodes at the axis's first value, grid order
+        where = np.moveaxis(idx, ax, -1).reshape(len(first), nk)        # [node without time][offset] -> grid index
+        res = mtfit.scan_double_couples_time_scan(engine, self.sourcetype, self.sources[first], strikes, dips, rakes, k0, kstep, nk,
+                                                  moment=moment, outer_norm=outer_norm, cube=cube)
+        n = len(self.sources)
+        self.dc_sdr, self.dc_moments, self.dc_misfits = np.full((n, 3), np.nan), np.full(n, np.nan), np.full(n, np.nan)
+        self.dc_index, self.dc_status = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+        self.dc_sdr[where] = np.stack([res["strikes"], res["dips_"], res["rakes_"]], 2)
+        self.dc_moments[where], self.dc_misfits[where], self.dc_index[where] = res["moments"], res["misfits"], res["indices"]
+        self.dc_status[where] = res["status"][:, None]
+        if cube:
+            self.dc_cube, self.dc_cube_offset = res["cube"], res["cube_offset"]
+        has = self.dc_index >= 0
+        tensors, _ = mtfit.double_couple_candidates(strikes, dips, rakes)
+        self.sources[has, c0:c0 + 6] = (tensors[self.dc_index[has]] * self.dc_moments[has, None]).astype(np.float32)
+        nmech = len(tensors)
+        self.syntheses_saved = nmech * n - 6 * len(first)
+        self.misfits_by_s = self.dc_misfits
+        self.ibest = int(np.nanargmin(self.dc_misfits)) if np.any(np.isfinite(self.dc_misfits)) else 0
+        self.best_source = self.sources[self.ibest]
+        self.dc_scan = res
+
     def compute(self, engine, dist=None, device=0, linear_mt=False, outer_norm="l2norm", niter=8, eps=1e-3, time_scan=False,
                 dt=None):
         """Trace misfits for every grid node (and the reference source), `engine` = kiwi_amd.Engine set up for

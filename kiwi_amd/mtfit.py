@@ -182,3 +182,44 @@ def scan_double_couples(engine, sourcetype, params, strikes, dips, rakes, moment
         if free:
             out["moments"] = (scan.scale * float(unit)).reshape(len(p), len(s), len(d), len(r))
     return out
+
+
+def scan_double_couples_time_scan(engine, sourcetype, params, strikes, dips, rakes, k0, kstep, nk, moment=None, outer_norm="l1norm",
+                                  unit=1e18, receiver_weights=None, anarchy=False, piece=0, cube=False, receiver_misfit=False):
+    """`scan_double_couples` at the origin-time offsets (k0 + j kstep) dt, j < nk, of every row of params[N, nparams], from the SIX
+    syntheses per row of a single time (`Engine.linear_fit_candidates_time_scan_params`): the best double couple AND origin time of
+    every row.  moment as in `scan_double_couples` (None: the best scalar moment of every mechanism and offset, outer l2norm only).
+    Returns a dict: strike, dip, rake, moment, misfit [N] of the best (mechanism, offset) (NaN where there is none), index [N] the
+    mechanism's row in the grid and offset [N] the offset index (-1: none), status [N]; per offset strikes, dips_, rakes_, moments,
+    misfits, indices [N, nk]: the best mechanism of every offset; tensor [N, nk, 6] in N m, tensor_misfit and tensor_status
+    [N, nk]: the free tensor of `fit_moment_tensors_time_scan` per offset; scan: the `CandidateTimeScan`.  cube=True adds cube
+    [N, ns, nd, nr]: every mechanism's smallest misfit over the offsets -- the mechanism cube with the origin time profiled out --,
+    cube_offset, the same shape: the offset index of that minimum, and cube_moments where moment is None."""
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    free = moment is None
+    if free and outer_norm != "l2norm":
+        raise KiwiHipError("scan_double_couples_time_scan: moment=None (the best moment per mechanism) needs outer_norm l2norm; give a moment")
+    s, d, r = list(strikes), list(dips), list(rakes)
+    cand, sdr = double_couple_candidates(s, d, r, 1.0 if free else float(moment) / float(unit))
+    scan = engine.linear_fit_candidates_time_scan_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, k0, kstep, nk,
+                                                         outer_norm=outer_norm, receiver_weights=receiver_weights, anarchy=anarchy,
+                                                         free_scale=free, marginal=cube, receiver_misfit=receiver_misfit, piece=piece)
+    has = scan.best_index >= 0                                                  # [N, nk]
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, :, None], sdr[at], np.nan)                           # [N, nk, 3]
+    moms = np.where(has, scan.best_scale * float(unit) if free else float(moment), np.nan)
+    rows = np.arange(len(p))
+    found = scan.best_offset >= 0
+    j = np.where(found, scan.best_offset, 0)
+    one = lambda a, none: np.where(found, a[rows, j], none)                     # noqa: E731
+    out = dict(strike=one(pick[:, :, 0], np.nan), dip=one(pick[:, :, 1], np.nan), rake=one(pick[:, :, 2], np.nan), moment=one(moms, np.nan),
+               misfit=one(scan.best_misfit, np.nan), index=one(scan.best_index, -1), offset=scan.best_offset, status=scan.status,
+               strikes=pick[:, :, 0], dips_=pick[:, :, 1], rakes_=pick[:, :, 2], moments=moms, misfits=scan.best_misfit,
+               indices=scan.best_index, tensor=scan.fit_coef * float(unit), tensor_misfit=scan.fit_misfit, tensor_status=scan.fit_status,
+               scan=scan)
+    if cube:
+        shape = (len(p), len(s), len(d), len(r))
+        out["cube"], out["cube_offset"] = scan.cand_misfit.reshape(shape), scan.cand_offset.reshape(shape)
+        if free:
+            out["cube_moments"] = (scan.cand_scale * float(unit)).reshape(shape)
+    return out
