@@ -16,7 +16,8 @@ memory model that matters here:
   (product exact in fp64, sum rounded once to fp64 and then to fp32: double rounding is possible in principle and irrelevant here -- the
   reference model of the test uses the same expression).
 
-Operands %0 .. %12 of the inline-assembly statement are bound to registers outside the routine's fixed ranges (v[200:211], s[90:95])."""
+Operands %0 .. %12 of the inline-assembly statement are bound to registers outside the routine's fixed ranges (v[200:211], s[90:95]);
+the apply_regular_asm_* and apply_plan_asm_* routines take other operands (OPERANDS_REGULAR, OPERANDS_PLAN: `operands` of Machine.run)."""
 import re
 
 import numpy as np
@@ -31,7 +32,7 @@ class EmuError(AssertionError):
 def routines(text):
     """{name: [instruction, ...]} of every routine in the generated file"""
     out = {}
-    for m in re.finditer(r"void (apply_group_asm_\w+)\(.*?asm volatile\(\n(.*?)\n\s*: \"\+v\"", text, re.S):
+    for m in re.finditer(r"void (apply_(?:group|regular|plan)_asm_\w+)\(.*?asm volatile\(\n(.*?)\n\s*: \"\+v\"", text, re.S):
         ins = []
         for line in m.group(2).split("\n"):
             line = line.strip()
@@ -49,9 +50,18 @@ OPERANDS = {"%0": "v[200:201]", "%1": "v[202:203]", "%2": "v[204:205]", "%3": "v
             "%6": "v212", "%7": "v213", "%8": "s90", "%9": "s91", "%10": "s[92:93]", "%11": "s94", "%12": "s95"}
 
 
-def _bind(ins):
-    for k in sorted(OPERANDS, key=len, reverse=True):       # %10 .. %12 before %1
-        ins = ins.replace(k, OPERANDS[k])
+# apply_regular_asm_*: %6 abase, %7 e0, %8 n, %9 coef, %10 cl, %11 sl
+OPERANDS_REGULAR = {"%0": "v[200:201]", "%1": "v[202:203]", "%2": "v[204:205]", "%3": "v[206:207]", "%4": "v[208:209]", "%5": "v[210:211]",
+                    "%6": "v212", "%7": "s90", "%8": "s91", "%9": "s[92:93]", "%10": "s94", "%11": "s95"}
+
+
+# apply_plan_asm_*: apply_group_asm_*'s, then %13 the plan's header word
+OPERANDS_PLAN = dict(OPERANDS, **{"%13": "s96"})
+
+
+def _bind(ins, operands=OPERANDS):
+    for k in sorted(operands, key=len, reverse=True):       # %10 .. %12 before %1
+        ins = ins.replace(k, operands[k])
     return ins
 
 
@@ -111,8 +121,8 @@ class Machine:
         raise EmuError("packed operand: " + ins)
 
     # ---- execution
-    def run(self, ins_list, max_steps=200000):
-        ins_list = [_bind(i) for i in ins_list]
+    def run(self, ins_list, max_steps=200000, operands=OPERANDS):
+        ins_list = [_bind(i, operands) for i in ins_list]
         labels = {i[:-1]: n for n, i in enumerate(ins_list) if i.endswith(":")}
         pc, steps = 0, 0
         while pc < len(ins_list):
@@ -155,7 +165,7 @@ class Machine:
                 a = int(re.match(r"s\[(\d+)", args[1]).group(1))
                 self.s[d], self.s[d + 1] = self.rs(a, ins), self.rs(a + 1, ins)
                 continue
-            if op in ("s_add_u32", "s_addc_u32", "s_sub_i32", "s_lshl_b32"):
+            if op in ("s_add_u32", "s_addc_u32", "s_sub_i32", "s_sub_u32", "s_lshl_b32"):
                 a, b = int(self.src32(args[1], ins)[0]), int(self.src32(args[2], ins)[0])
                 if op == "s_add_u32":
                     r = a + b
@@ -165,9 +175,22 @@ class Machine:
                     self.scc = 1 if r > 0xffffffff else 0
                 elif op == "s_sub_i32":
                     r = a - b
+                elif op == "s_sub_u32":
+                    r = a - b
+                    self.scc = 1 if a < b else 0          # (the borrow)
                 else:
                     r = a << (b & 31)
                 self.s[int(args[0][1:])] = r & 0xffffffff
+                continue
+            if op == "s_bitcmp0_b32":
+                self.scc = int(((int(self.src32(args[0], ins)[0]) >> (int(self.src32(args[1], ins)[0]) & 31)) & 1) == 0)
+                continue
+            if op == "s_bfe_u32":                          # (offset in bits 0 .. 4 of the second source, width in bits 16 .. 22)
+                a, b = int(self.src32(args[1], ins)[0]), int(self.src32(args[2], ins)[0])
+                w = (b >> 16) & 0x7f
+                r = (a >> (b & 31)) & ((1 << w) - 1)
+                self.s[int(args[0][1:])] = r
+                self.scc = int(r != 0)
                 continue
             if op in ("s_cmp_ge_u32", "s_cmp_lg_u32", "s_cmp_eq_u32"):
                 a, b = int(self.src32(args[0], ins)[0]), int(self.src32(args[1], ins)[0])
@@ -177,7 +200,9 @@ class Machine:
                 n = 16 if op.endswith("16") else 4
                 d = int(re.match(r"s\[(\d+)", args[0]).group(1))
                 p = int(re.match(r"s\[(\d+)", args[1]).group(1))
-                addr = (int(self.rs(p + 1, ins)) << 32 | int(self.rs(p, ins))) + int(args[2], 0)
+                addr = int(self.rs(p + 1, ins)) << 32 | int(self.rs(p, ins))
+                om = re.fullmatch(r"s(\d+)(?:\s+offset:(\w+))?", args[2])      # offset in a register (+ an immediate), or an immediate
+                addr += int(self.rs(int(om.group(1)), ins)) + int(om.group(2) or "0", 0) if om else int(args[2], 0)
                 if addr % 4 or addr // 4 + n > len(self.coef):
                     raise EmuError("scalar load outside of the coefficient lines: " + ins)
                 for i in range(n):

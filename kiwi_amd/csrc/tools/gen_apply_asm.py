@@ -24,6 +24,11 @@ Registers (kernel budget: 168 VGPRs at three waves per SIMD):
   s[36:55], s[56:75] coefficient lines of the step at hand and of the next one, swapping roles every step   s[76:77] (cl, sl)
   s80 k  s81, s82 4 x integer shift of this step / the next (swapping)  s83 tmp  s84 4 d  s[86:87] coefficient pointer
   v44 address of position smax  v45 4 x shifts (lane k: step k)  v46, v47 addresses of the next reads
+
+Two more families (python tools/gen_apply_asm.py regular | plan; not committed: the Makefile writes the plan family into
+build/kiwi_apply_plan_asm.inc, the tests call the generator): apply_regular_asm_* serves the groups whose shifts grow by one per step (routine_regular()), and
+apply_plan_asm_*, what accumulate_multi_kernel calls where it has plans, holds that text and the general routine's in one statement
+(routine_plan()).
 """
 import os
 import sys
@@ -165,6 +170,10 @@ def arithmetic(ng, rot, fused, H, L, acc, K=None, behind=False, C=None):
 
 def routine(ng, K, rot, fused):
     name = "apply_group_asm_%d_k%d_%s_%s" % (ng, K, "rot" if rot else "plain", "fused" if fused else "exact")
+    return wrap_general(name, lines_general(ng, K, rot, fused))
+
+
+def lines_general(ng, K, rot, fused):
     acc = ["%0", "%1", "%2", "%3", "%4", "%5"]
     # operands: %6 abase (v), %7 ishv (v), %8 smax (s), %9 n (s), %10 coef (s, 64 bit), %11 cl (s), %12 sl (s)
     L = []
@@ -230,29 +239,133 @@ def routine(ng, K, rot, fused):
             if "nocoef" in VARIANT and i > steps and x.startswith("s_load"): return False
             return True
         L = [x for i, x in enumerate(L) if keep(i, x)]
+    return L
+
+
+def wrap_general(name, L, head=False):
+    """the routine's C++ function: routine()'s operands, and behind them (head) the plan's header word in a scalar register"""
     text = "\\n\\t\"\n        \"".join(L)
     clob_v = ", ".join('"v%d"' % i for i in range(28, 128))
     clob_s = ", ".join('"s%d"' % i for i in list(range(CA, CB + 20)) + [CLSL, CLSL + 1] + list(range(SK, SCP + 2)))
     out = []
     out.append("__device__ __forceinline__ void %s(f2v &ar1a, f2v &ar1b, f2v &ar2a, f2v &ar2b, f2v &dza, f2v &dzb, unsigned abase, int ishv,\n"
-               "        int smax, int n, const float *coef, float cl, float sl)" % name)
+               "        int smax, int n, const float *coef, float cl, float sl%s)" % (name, ", int head" if head else ""))
     out.append("{")
     out.append('    asm volatile(\n        "%s\\n\\t"' % text)
     out.append('        : "+v"(ar1a), "+v"(ar1b), "+v"(ar2a), "+v"(ar2b), "+v"(dza), "+v"(dzb)')
-    out.append('        : "v"(abase), "v"(ishv), "s"(smax), "s"(n), "s"(coef), "s"(cl), "s"(sl)')
+    out.append('        : "v"(abase), "v"(ishv), "s"(smax), "s"(n), "s"(coef), "s"(cl), "s"(sl)%s' % (', "s"(head)' if head else ""))
     out.append('        : "memory", "scc", "vcc", %s,\n          %s);' % (clob_s, clob_v))
     out.append("}")
     return "\n".join(out)
 
 
+def routine_regular(ng, K, rot, fused):
+    """The apply of a REGULAR group: every centroid's integer shift is its predecessor's + 1 (multi_plan_kernel decides it once per
+    evaluation, PlanSrc::head).  What routine() establishes again at every step -- the next shift out of a vector register, its
+    difference to this one's, whether that is one sample -- is known, so the step's bookkeeping is a count-down whose borrow is the
+    exit branch, one add on the coefficient offset (the scalar loads take it from a register: no 64-bit pointer add) and one add on
+    the read address.  The step bodies are arithmetic()'s, the ones routine() takes for a regular successor and for a last step:
+    per accumulator the same operations in the same order.
+    Registers as routine()'s, except: s80 steps left behind this one, s85 byte offset of the next coefficient line, no v44 / v45 and
+    no s81 / s82 / s84."""
+    name = "apply_regular_asm_%d_k%d_%s_%s" % (ng, K, "rot" if rot else "plain", "fused" if fused else "exact")
+    # operands: %6 abase (v), %7 e0 (s), %8 n (s), %9 coef (s, 64 bit), %10 cl (s), %11 sl (s)
+    L = lines_regular(ng, K, rot, fused, {"abase": "%6", "e0": "%7", "n": "%8", "coef": "%9", "cl": "%10", "sl": "%11"}, ".Lkiwi_rend_%=", False)
+    L.append(".Lkiwi_rend_%=:")
+    return wrap_regular(name, L)
+
+
+def lines_regular(ng, K, rot, fused, op, end, jump_end):
+    """op: the statement's operands by name (e0, or head: the plan's header word, which holds it); end: the label behind the routine,
+    jump_end: it does not follow the text"""
+    acc = ["%0", "%1", "%2", "%3", "%4", "%5"]
+    L = []
+    a = L.append
+    a("s_mov_b32 s%d, %s" % (CLSL, op["cl"]))
+    a("s_mov_b32 s%d, %s" % (CLSL + 1, op["sl"]))
+    a("s_mov_b64 %s, %s" % (sp(SCP), op["coef"]))
+    a("s_load_dwordx16 s[%d:%d], %s, 0x0" % (CA, CA + 15, sp(SCP)))
+    if ng == 10:
+        a("s_load_dwordx4 s[%d:%d], %s, 0x40" % (CA + 16, CA + 19, sp(SCP)))
+    a("s_sub_u32 s%d, %s, 1" % (SK, op["n"]))          # s80: steps behind the one at hand
+    a("s_mov_b32 s%d, 0" % SK1)                        # s85: byte offset of the coefficient line last loaded
+    if "head" in op:
+        a("s_bfe_u32 s%d, %s, 0x70004" % (ST, op["head"]))        # e0: bits 4 .. 10 of the plan's header word (PlanSrc::head)
+        a("s_lshl_b32 s%d, s%d, 2" % (ST, ST))
+    else:
+        a("s_lshl_b32 s%d, %s, 2" % (ST, op["e0"]))
+    a("v_add_u32 v%d, s%d, %s" % (VN, ST, op["abase"]))           # v46: LDS address of position e0 of the lane's first sample: b[j-1] of step 0
+    a("v_add_u32 v%d, 4, v%d" % (VN4, VN))
+    L += reads(0, ng, K, VN4)            # bank 0 = b[j]
+    L += reads(1, ng, K, VN)             # bank 1 = b[j-1]
+    tail = []                            # the last step: out of line
+    for r in range(2):
+        H, Lb = r, 1 - r
+        Cc, Cn = (CA, CB) if r == 0 else (CB, CA)
+        a(".Lkiwi_rstep%d_%%=:" % r)
+        a("s_waitcnt lgkmcnt(0)")
+        a("s_sub_u32 s%d, s%d, 1" % (SK, SK))          # (the borrow: this is the last step)
+        a("s_cbranch_scc1 .Lkiwi_rlast%d_%%=" % r)
+        a("s_add_u32 s%d, s%d, %d" % (SK1, SK1, 80))
+        a("s_load_dwordx16 s[%d:%d], %s, s%d" % (Cn, Cn + 15, sp(SCP), SK1))
+        if ng == 10:
+            a("s_load_dwordx4 s[%d:%d], %s, s%d offset:0x40" % (Cn + 16, Cn + 19, sp(SCP), SK1))
+        a("v_add_u32 v%d, -4, v%d" % (VN, VN))         # the successor's shift is one more: its b[j-1] one position back
+        L += arithmetic(ng, rot, fused, H, Lb, acc, K, True, C=Cc)
+        if r == 1:
+            a("s_branch .Lkiwi_rstep0_%=")
+        tail.append(".Lkiwi_rlast%d_%%=:" % r)
+        tail += arithmetic(ng, rot, fused, H, Lb, acc, C=Cc)
+        if r == 0 or jump_end:
+            tail.append("s_branch %s" % end)
+    L += tail
+    return L
+
+
+def wrap_regular(name, L):
+    text = "\\n\\t\"\n        \"".join(L)
+    clob_v = ", ".join('"v%d"' % i for i in list(range(28, 44)) + [VN, VN4] + list(range(48, 128)))
+    clob_s = ", ".join('"s%d"' % i for i in list(range(CA, CB + 20)) + [CLSL, CLSL + 1, SK, ST, SK1, SCP, SCP + 1])
+    out = []
+    out.append("__device__ __forceinline__ void %s(f2v &ar1a, f2v &ar1b, f2v &ar2a, f2v &ar2b, f2v &dza, f2v &dzb, unsigned abase, int e0,\n"
+               "        int n, const float *coef, float cl, float sl)" % name)
+    out.append("{")
+    out.append('    asm volatile(\n        "%s\\n\\t"' % text)
+    out.append('        : "+v"(ar1a), "+v"(ar1b), "+v"(ar2a), "+v"(ar2b), "+v"(dza), "+v"(dzb)')
+    out.append('        : "v"(abase), "s"(e0), "s"(n), "s"(coef), "s"(cl), "s"(sl)')
+    out.append('        : "memory", "scc", "vcc", %s,\n          %s);' % (clob_s, clob_v))
+    out.append("}")
+    return "\n".join(out)
+
+
+def routine_plan(ng, K, rot, fused):
+    """What accumulate_multi_kernel calls where it has plans: routine()'s text and routine_regular()'s in ONE statement, the choice
+    between them a scalar bit test of the plan's header word (PlanSrc::head, bit 11: regular; bits 4 .. 10: e0) at its top.  (Two
+    statements on the two sides of a C++ branch: the compiler either branches with a mask over the wave -- ten instructions per group
+    -- or, for a scalar condition, copies the six accumulators in front of every statement and back behind it.)  Operands:
+    routine()'s, then %13 the header word (s)."""
+    name = "apply_plan_asm_%d_k%d_%s_%s" % (ng, K, "rot" if rot else "plain", "fused" if fused else "exact")
+    L = ["s_bitcmp0_b32 %%13, %d" % 11, "s_cbranch_scc1 .Lkiwi_general_%="]
+    L += lines_regular(ng, K, rot, fused, {"abase": "%6", "head": "%13", "n": "%9", "coef": "%10", "cl": "%11", "sl": "%12"}, ".Lkiwi_end_%=", True)
+    L.append(".Lkiwi_general_%=:")
+    L += lines_general(ng, K, rot, fused)          # (ends in its label .Lkiwi_end)
+    return wrap_general(name, L, head=True)
+
+
 if __name__ == "__main__":
-    print("// ---- (generated text: tools/gen_apply_asm.py) the apply of one centroid group as a hand-allocated assembly routine")
+    # no argument: kiwi_apply_asm.inc, the general routines.  `regular` / `plan`: the routines of accumulate_multi_kernel's plans (K = 17 is
+    # the grouped kernel's: no plan) -- `plan` is what the Makefile writes into build/kiwi_apply_plan_asm.inc
+    family = sys.argv[1] if len(sys.argv) > 1 else "general"
+    assert family in ("general", "regular", "plan")
+    what = {"general": "the apply of one centroid group", "regular": "the apply of one REGULAR centroid group (shifts one apart: routine_regular)",
+            "plan": "the apply of one centroid group, regular or not by the plan's header word (routine_plan)"}[family]
+    print("// ---- (generated text: tools/gen_apply_asm.py%s) %s as a hand-allocated assembly routine" % ("" if family == "general" else " " + family, what))
     print("// KIWI_ARITH selects the exact (v_pk_mul_f32 + v_pk_add_f32) or the fused (v_pk_fma_f32) text")
     for fused in (False, True):
         print("#if KIWI_ARITH == %d" % (1 if fused else 0))
         for ng in (10, 8):
-            for K in (5, 9, 17):
+            for K in (5, 9, 17) if family == "general" else (5, 9):
                 for rot in (True, False):
-                    print(routine(ng, K, rot, fused))
+                    print({"general": routine, "regular": routine_regular, "plan": routine_plan}[family](ng, K, rot, fused))
         print("#endif")
     print("// ---- (end of generated text)")

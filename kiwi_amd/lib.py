@@ -28,7 +28,7 @@ def build(force=False):
     """Compile kiwi_amd/csrc for gfx950 into kiwi_amd/libkiwi_hip.so (hipcc cross-compiles without a GPU)."""
     if force and os.path.exists(LIB_PATH):
         os.remove(LIB_PATH)
-    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc")])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(HERE, "csrc"), "PYTHON=" + sys.executable])      # (the generated apply routines)
     return LIB_PATH
 
 
