@@ -669,6 +669,55 @@ int kiwi_hip_get_linear_fit_candidates_time_scan_ms(kiwi_hip_ctx *ctx, float ms[
 /* how the candidate-scan kernel walks its work: *candidates_per_workgroup (one per lane), *receivers_per_stage rows of sums per LDS
  * stage; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage);
+/* ---- the candidate evaluation with PER-RECEIVER TIME SHIFTS (kiwi_amd/csrc/kiwi_linfit_candidates_floating.hpp): the context's
+ * misfit method must be floating_l2norm (receiver.f90:439-510): every receiver slides its reference data under the fixed taper by the
+ * whole samples of its own range (kiwi_hip_set_floating_shiftrange: fl_lo .. fl_lo + fl_ns - 1), and per candidate the shift with the
+ * smallest sum of squared component misfits wins -- the remedy for a velocity model that mis-times single stations, for a whole
+ * mechanism grid from the six syntheses of a location.  For a GIVEN x the minimum over the shifts is exact; nothing is fitted.
+ * Groups, K, receiver_weight, anarchy and candidates [ncand][K] are kiwi_hip_linear_fit_candidates'.  Per receiver r:
+ *   G_r                    kiwi_hip_linear_fit's sums of the tapered kept synthetics (the taper stays with the synthetic: they do not
+ *                          depend on the shift)
+ *   b_r[q][i], R_r[q]      for shift index q (shift fl_lo + q): dt sum_t s_i[t] a_q[t] and dt sum_t a_q[t]^2 with a_q the reference moved
+ *                          by that shift, times the taper (fp32, as the floating evaluation forms it); fp64 sums in the order of G_r's.
+ *                          They are the bits kiwi_hip_linear_fit gives on a context whose references were moved by that shift with
+ *                          kiwi_hip_shift_ref_seismogram; at shift 0 the bits of the unshifted context
+ *   val_q = max((R_r[q] - 2 x.b_r[q]) + x.G_r.x, 0) in kiwi_hip_linear_fit_candidates' order; m_r = sqrt(min_q val_q), the FIRST
+ *                          minimum with q ascending; shift_r = fl_lo + argmin; n_r = (sum_q sqrt(R_r[q])) / fl_ns, q ascending: the
+ *                          receiver-level form of receiver.f90:501.  A receiver is skipped where w_r == 0 or n_r is not positive
+ *   outer_norm 1 (l1norm)  v_r = w_r (anarchy: w_r / n_r); misfit = (sum v_r m_r) / (sum v_r n_r), receivers ascending
+ *   outer_norm 2 (l2norm)  misfit = sqrt((sum v_r^2 m_r^2) / (sum v_r^2 n_r^2)), m_r^2 the clamped val; the minimum sits inside the
+ *                          sum, so there is no fold-then-evaluate form
+ *   best_index, best_misfit [ngroup]   in kiwi_hip_linear_fit_candidates' total order;  status [ngroup]: 0 evaluated; 1 no receiver
+ *                          counts: NaN, -1; 2 a basis source of the group failed to discretise: NaN, -1
+ *   best_shift  int [ngroup][nrec]     the winner's shifts in samples; 0 for receivers that are disabled or skipped, and without a winner
+ *   misfit      [ngroup][ncand] or NULL;  cand_shift  short [ngroup][ncand][nrec] or NULL (needs misfit): every candidate's shifts
+ *   receiver_misfit  float [ngroup][ncand][nrec] or NULL: m_r;  receiver_norm  float [ngroup][nrec] or NULL: n_r; zeros as for
+ *                          kiwi_hip_linear_fit_candidates.  They are the pair kiwi_hip_outer_misfits takes: the bootstrap over receivers
+ * There is no free fit (it is not defined under shifts) and no free_scale.  All ranges (0, 0) and outer_norm 1: bit for bit
+ * kiwi_hip_linear_fit_candidates under l2norm.  The answer does not depend on tiling, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the
+ * number of devices.  Afterwards the context is what kiwi_hip_eval of the basis sources under floating_l2norm leaves.  Refused with a
+ * message that starts with "linear_fit_candidates_floating:", nothing approximated: a method other than floating_l2norm
+ * (floating_l1norm is not quadratic in the coefficients); what kiwi_hip_linear_fit refuses otherwise; what
+ * kiwi_hip_linear_fit_candidates refuses of ncand, candidates and outer_norm; free_scale other than 0; cand_shift without misfit (or
+ * with a range beyond 16 bits).  n_r and the l1norm fold are receiver-level where make_global_misfits works per slot. */
+int kiwi_hip_linear_fit_candidates_floating(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                            int outer_norm, const double *receiver_weight, int anarchy, int free_scale, int *best_index,
+                                            double *best_misfit, int *status, int *best_shift, double *misfit, short *cand_shift,
+                                            float *receiver_misfit, float *receiver_norm);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_linear_fit_candidates_floating_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                   int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                   int anarchy, int free_scale, int *best_index, double *best_misfit, int *status,
+                                                   int *best_shift, double *misfit, short *cand_shift, float *receiver_misfit,
+                                                   float *receiver_norm);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram and cross-correlation kernels,
+ * ms[2] candidate kernels, ms[3] downloads */
+int kiwi_hip_get_linear_fit_candidates_floating_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the kernels walk their work: *candidates_per_workgroup (one per lane), *shifts_per_pass of the cross-correlation kernel (their
+ * accumulators are registers), *shifts_per_stage rows of sums per LDS stage of the candidate kernel; answers without a device.
+ * Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_workgroup, int *shifts_per_pass, int *shifts_per_stage);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

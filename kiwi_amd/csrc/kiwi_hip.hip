@@ -274,6 +274,7 @@ struct kiwi_hip_ctx {
     TimeScanState timescan_state;
     float timescan_ms[3] = { 0.f, 0.f, 0.f };         // evaluation, scan kernels, downloads of the last kiwi_hip_time_scan
     float linfit_timescan_ms[4] = { 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, downloads of the last kiwi_hip_linear_fit_time_scan
+    float linfit_cand_floating_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, Gram + xcorr kernels, candidate kernels, downloads of the last kiwi_hip_linear_fit_candidates_floating
     float linfit_cand_timescan_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, candidate-scan kernels, downloads of the last kiwi_hip_linear_fit_candidates_time_scan
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
@@ -1522,6 +1523,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_robust.hpp"
 #include "kiwi_linfit_wide.hpp"
 #include "kiwi_linfit_candidates.hpp"
+#include "kiwi_linfit_candidates_floating.hpp"
 #include "kiwi_bands.hpp"
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
@@ -2896,10 +2898,14 @@ struct CandScanCall {
     }
 };
 
+// (kiwi_hip_linear_fit_candidates_floating_params the same with `candfloat` set: groups of K basis sources as for `fit`, a piece is
+// evaluated by linfit_candidates_floating::run)
+struct CandFloatCall { int K; const double *weight; int anarchy; linfit_candidates_floating::Floating fl; };
+
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
-                           const CandScanCall *candscan = nullptr)
+                           const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2912,8 +2918,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (fitscan) linfit_timescan::check_setup(c, fitscan->K, fitscan->of, fitscan->out);
     if (cand) { linfit::check_candidates(cand->cand, cand->K); linfit::check_setup(c, cand->K, cand->out); }
     if (candscan) linfit_candidates_timescan::check_setup(c, candscan->K, candscan->of, candscan->out, candscan->scan);
+    if (candfloat) linfit_candidates_floating::check_setup(c, candfloat->K, candfloat->fl);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2946,17 +2953,20 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (canding) { mine_cand = *cand; mine_cand.out = cand->out.at(s0 / unit, unit, nrec_all); mine_cand.cand = cand->cand.at(s0 / unit, nrec_all); }
             const bool candscanning = candscan != nullptr;
             const CandScanCall mine_candscan = candscanning ? candscan->at((size_t)(s0 / unit), (size_t)nrec_all) : CandScanCall{};
+            const bool candfloating = candfloat != nullptr;
+            CandFloatCall mine_candfloat{};
+            if (candfloating) { mine_candfloat = *candfloat; mine_candfloat.fl = candfloat->fl.at(s0 / unit, nrec_all); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
-                                       candscanning ? &mine_candscan : nullptr);
+                                       candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3096,6 +3106,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                 linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)mine.of.nk, mine.out);
                 linfit_candidates_timescan::fill_failed((size_t)(n / unit), (size_t)mine.of.nk, (size_t)nrec_all, mine.scan);
             }
+            if (candfloat) linfit_candidates_floating::fill_failed(n / unit, nrec_all, candfloat->fl.at(s0 / unit, nrec_all));
             continue;
         }
         upload_batch(c, hb);
@@ -3111,7 +3122,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         } else if (candscan) {
             const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);
             linfit_candidates_timescan::run(c, 0, n / unit, unit, mine.of, mine.weight, mine.anarchy, mine.out, mine.scan);
-        } else eval_impl(c, 0, n, c->keep_which);
+        } else if (candfloat)
+            linfit_candidates_floating::run(c, 0, n / unit, unit, candfloat->weight, candfloat->anarchy, candfloat->fl.at(s0 / unit, nrec_all));
+        else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
         if (trace) {
@@ -3407,6 +3420,67 @@ int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, i
     if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !receivers_per_stage) return 1;
     *candidates_per_workgroup = linfit::kCandThreads;
     *receivers_per_stage = linfit::kCandStage;
+    return 0;
+}
+
+// The candidate evaluation under floating_l2norm: per receiver and candidate the best whole-sample shift of the reference
+// (kiwi_linfit_candidates_floating.hpp)
+static const char *const kCandFloatFreeScale =
+    "linear_fit_candidates_floating: free_scale is not offered (the best scale of a direction changes the shifts that win, so it has no "
+    "closed form under shifts); pass 0";
+
+int kiwi_hip_linear_fit_candidates_floating(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                            int outer_norm, const double *receiver_weight, int anarchy, int free_scale, int *best_index,
+                                            double *best_misfit, int *status, int *best_shift, double *misfit, short *cand_shift,
+                                            float *receiver_misfit, float *receiver_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->linfit_cand_floating_ms) t = 0.f;
+    if (free_scale != 0) throw std::runtime_error(kCandFloatFreeScale);
+    const linfit_candidates_floating::Floating fl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
+                                                   cand_shift, receiver_misfit, receiver_norm };
+    linfit_candidates_floating::run(c, isrc0, ngroup, K, receiver_weight, anarchy, fl);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_candidates_floating_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                   int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                   int anarchy, int free_scale, int *best_index, double *best_misfit, int *status,
+                                                   int *best_shift, double *misfit, short *cand_shift, float *receiver_misfit,
+                                                   float *receiver_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (free_scale != 0) return fail(c, kCandFloatFreeScale);
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, "linear_fit_candidates_floating: K = " + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "linear_fit_candidates_floating: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->linfit_cand_floating_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_floating_ms) t = 0.f;
+    const CandFloatCall candfloat{ K, receiver_weight, anarchy,
+                                   linfit_candidates_floating::Floating{ candidates, ncand, outer_norm, best_index, best_misfit, status,
+                                                                         best_shift, misfit, cand_shift, receiver_misfit, receiver_norm } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, &candfloat);
+}
+
+int kiwi_hip_get_linear_fit_candidates_floating_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->linfit_cand_floating_ms[i];
+    return 0;
+}
+
+int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_workgroup, int *shifts_per_pass, int *shifts_per_stage)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !shifts_per_pass || !shifts_per_stage) return 1;
+    *candidates_per_workgroup = linfit_candidates_floating::kFloatCandThreads;
+    *shifts_per_pass = linfit_candidates_floating::kFloatShiftsPerPass;
+    *shifts_per_stage = linfit_candidates_floating::kFloatShiftStage;
     return 0;
 }
 

@@ -336,8 +336,9 @@ static void cand_chunk(kiwi_hip_ctx *c, int K, int g0, int ng, const double *w_d
                        const Candidates &cd, CandBufs &b, hipEvent_t after_kernels);
 static void cand_fill_failed(int ngroup, int nrec, const Candidates &cd);
 
-// what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.
-static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr, const Wide *wd = nullptr)
+// what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.  floating_l2: the caller evaluates GIVEN
+// coefficient vectors under floating_l2norm (kiwi_linfit_candidates_floating.hpp) and fits nothing: that method, and only it, passes
+static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb = nullptr, const Wide *wd = nullptr, bool floating_l2 = false)
 {
     const int kmax = wd ? kWideMaxBasis : kMaxBasis;
     if (K < 1 || K > kmax)
@@ -349,9 +350,10 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Out &out, const Robust *rb
                 if (!std::isfinite(wd->penalty[p])) throw std::runtime_error("linear_fit_wide: penalty entry " + std::to_string(p) + " is not finite");
     }
     if (!out.coef || !out.misfit || !out.status) throw std::runtime_error("linear_fit: null coef, misfit or status array");
-    if (c->method == KIWI_FLOATING_L2NORM || c->method == KIWI_FLOATING_L1NORM)
+    const bool floating_ok = floating_l2 && c->method == KIWI_FLOATING_L2NORM;
+    if ((c->method == KIWI_FLOATING_L2NORM || c->method == KIWI_FLOATING_L1NORM) && !floating_ok)
         throw std::runtime_error("linear_fit: floating shift ranges make the misfit a minimum over shifts, which is not quadratic in the coefficients; set l2norm");
-    if (c->method != KIWI_L2NORM && !(rb && rb->mode == 1 && c->method == KIWI_L1NORM))
+    if (c->method != KIWI_L2NORM && !(rb && rb->mode == 1 && c->method == KIWI_L1NORM) && !floating_ok)
         throw std::runtime_error("linear_fit: the misfit method must be l2norm (the only inner norm that is quadratic in the coefficients)");
     prepare(c);
     if (c->synth_only) throw std::runtime_error("linear_fit: every enabled receiver component needs a reference seismogram");

@@ -22,6 +22,8 @@ RobustFit = collections.namedtuple("RobustFit", "coef misfit status trace")
 ScanFit = collections.namedtuple("ScanFit", "coef misfit status pivot_min best normal")
 CandidateScan = collections.namedtuple("CandidateScan", "best_index best_misfit status misfit scale receiver_misfit receiver_norm "
                                                         "fit_coef fit_misfit")
+CandidateFloatingScan = collections.namedtuple("CandidateFloatingScan", "best_index best_misfit status best_shift misfit cand_shift "
+                                                                        "receiver_misfit receiver_norm")
 CandidateTimeScan = collections.namedtuple("CandidateTimeScan", "best_offset best_index best_misfit best_scale status cand_misfit cand_offset "
                                                                 "cand_scale misfit scale receiver_misfit receiver_norm fit_coef fit_misfit "
                                                                 "fit_status")
@@ -973,6 +975,91 @@ class Engine:
         downloads)."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_candidates_ms(self.h, _fp(ms)), "get_linear_fit_candidates_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ candidates with per-receiver shifts (kiwi_hip_linear_fit_candidates_floating)
+    def linear_fit_candidates_floating_shape(self, K):
+        """(candidates per workgroup, shifts per pass of the cross-correlation kernel, shifts per LDS stage of the candidate
+        kernel) for K basis sources."""
+        c, j, s = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_linear_fit_candidates_floating_shape(int(K), _ip(c), _ip(j), _ip(s)):
+            raise KiwiHipError("linear_fit_candidates_floating: K = %d basis sources per group; 1 to %d are supported"
+                               % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(j[0]), int(s[0])
+
+    def _candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift, receiver_misfit):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        K, ng = int(K), int(ngroup)
+        if not 1 <= K <= self.linear_fit_max_basis():
+            raise KiwiHipError("linear_fit_candidates_floating: K = %d basis sources per group; 1 to %d are supported"
+                               % (K, self.linear_fit_max_basis()))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != K:
+            raise KiwiHipError("linear_fit_candidates_floating: candidates must be [ncand, K = %d]" % K)
+        nc, nrec = len(x), len(self.components)
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        out = CandidateFloatingScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nrec), np.int32),
+                                    np.zeros((ng, nc)) if misfit else None, np.zeros((ng, nc, nrec), np.int16) if cand_shift else None,
+                                    np.zeros((ng, nc, nrec), np.float32) if receiver_misfit else None,
+                                    np.zeros((ng, nrec), np.float32) if receiver_misfit else None)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        tail = (nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), _ip(out.best_shift), dp(out.misfit),      # noqa: E731
+                        None if out.cand_shift is None else out.cand_shift.ctypes.data_as(C.POINTER(C.c_short)),
+                        None if out.receiver_misfit is None else _fp(out.receiver_misfit),
+                        None if out.receiver_norm is None else _fp(out.receiver_norm))
+        return tail, out, outs, (x, w)
+
+    def linear_fit_candidates_floating(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                                       free_scale=False, misfit=True, cand_shift=False, receiver_misfit=False):
+        """`linear_fit_candidates` under floating_l2norm (kiwi_hip_linear_fit_candidates_floating): every receiver slides its
+        reference by the whole samples of its own range (`set_floating_shiftrange`) and, per candidate, the shift with the
+        smallest squared misfit wins.  Nothing is fitted, and free_scale is refused.  Returns a `CandidateFloatingScan`:
+        best_index[ngroup] (-1: none), best_misfit[ngroup], status[ngroup] (0 evaluated, 1 no receiver counts, 2 a basis source
+        failed to discretise), best_shift[ngroup, nrec] (the winner's shifts in SAMPLES, 0 for receivers that do not count),
+        misfit[ngroup, ncand] (misfit=True), cand_shift[ngroup, ncand, nrec] int16 (cand_shift=True; needs misfit),
+        receiver_misfit[ngroup, ncand, nrec] and receiver_norm[ngroup, nrec] float32 (receiver_misfit=True: what
+        `outer_misfits` takes with one slot per receiver)."""
+        tail, out, outs, keep = self._candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift,
+                                                                receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
+                                                                1 if free_scale else 0, *outs()), "linear_fit_candidates_floating")
+        return out
+
+    def linear_fit_candidates_floating_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None,
+                                              anarchy=False, free_scale=False, misfit=True, cand_shift=False, receiver_misfit=False,
+                                              piece=0):
+        """`linear_fit_candidates_floating` for a parameter list of any length (kiwi_hip_linear_fit_candidates_floating_params),
+        cut into pieces and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        tail, out, outs, keep = self._candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift,
+                                                                receiver_misfit)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
+                                                                           1 if anarchy else 0, 1 if free_scale else 0, *outs()),
+                     "linear_fit_candidates_floating")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_candidates_floating_ms(self):
+        """HIP-event durations [ms] of the last `linear_fit_candidates_floating`: (evaluation, Gram and cross-correlation kernels,
+        candidate kernels, downloads)."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_ms(self.h, _fp(ms)), "get_linear_fit_candidates_floating_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)

@@ -38,6 +38,10 @@ program binding_smoke
     if (kiwi_hip_linear_fit_candidates_time_scan_shape( 6_c_int, per_group, per_stage ) /= 0) stop 9
     if (per_group < 64 .or. per_stage < 1) stop 10
 
+    ! and the kernels of the candidate evaluation with per-receiver shifts: shifts per pass and per LDS stage as well
+    if (kiwi_hip_linear_fit_candidates_floating_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 11
+    if (per_group < 64 .or. per_pass < 1 .or. per_stage < 1) stop 12
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

@@ -223,3 +223,34 @@ def scan_double_couples_time_scan(engine, sourcetype, params, strikes, dips, rak
         if free:
             out["cube_moments"] = (scan.cand_scale * float(unit)).reshape(shape)
     return out
+
+
+def scan_double_couples_floating(engine, sourcetype, params, strikes, dips, rakes, moment, outer_norm="l1norm", unit=1e18,
+                                 receiver_weights=None, anarchy=False, piece=0, cube=False, receiver_misfit=False):
+    """`scan_double_couples` with per-receiver time shifts (`Engine.linear_fit_candidates_floating_params`): the engine's misfit
+    method is floating_l2norm and every receiver has its own range of whole-sample shifts (`set_floating_shiftrange`); per
+    mechanism every receiver takes the shift under which it fits best, still from the SIX syntheses of a row.  All mechanisms
+    have the scalar moment `moment` [N m]; moment=None (the best moment per mechanism) is refused: the shifts that win depend on
+    the scale, so it has no closed form.  Returns a dict: strike, dip, rake, moment, misfit [N] of the best mechanism (NaN where
+    there is none), index [N] its row in the grid (-1: none), status [N] (0 evaluated, 1 no receiver counts, 2 the row failed to
+    discretise), shifts [N, nrec]: the best mechanism's shift of every receiver in SECONDS (0 for receivers that do not count),
+    scan: the `CandidateFloatingScan`; cube=True adds cube [N, ns, nd, nr], every mechanism's misfit, and cube_shifts
+    [N, ns, nd, nr, nrec] in samples (int16)."""
+    if moment is None:
+        raise KiwiHipError("scan_double_couples_floating: moment=None (the best moment per mechanism) is not defined under "
+                           "per-receiver shifts; give a moment")
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    s, d, r = list(strikes), list(dips), list(rakes)
+    cand, sdr = double_couple_candidates(s, d, r, float(moment) / float(unit))
+    scan = engine.linear_fit_candidates_floating_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, outer_norm=outer_norm,
+                                                        receiver_weights=receiver_weights, anarchy=anarchy, misfit=cube,
+                                                        cand_shift=cube, receiver_misfit=receiver_misfit, piece=piece)
+    has = scan.best_index >= 0
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, None], sdr[at], np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=np.where(has, float(moment), np.nan), misfit=scan.best_misfit,
+               index=scan.best_index, status=scan.status, shifts=scan.best_shift * float(engine.dt), scan=scan)
+    if cube:
+        out["cube"] = scan.misfit.reshape(len(p), len(s), len(d), len(r))
+        out["cube_shifts"] = scan.cand_shift.reshape(len(p), len(s), len(d), len(r), -1)
+    return out
