@@ -718,6 +718,55 @@ int kiwi_hip_get_linear_fit_candidates_floating_ms(kiwi_hip_ctx *ctx, float ms[4
  * accumulators are registers), *shifts_per_stage rows of sums per LDS stage of the candidate kernel; answers without a device.
  * Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_workgroup, int *shifts_per_pass, int *shifts_per_stage);
+/* The misfits of many GIVEN coefficient vectors per group under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp): the
+ * mechanism grid of a location from its six syntheses where the users of the reference search first, ampspec_l2norm (3) or
+ * ampspec_l1norm (4) inside a pass band.  The amplitude spectrum is not quadratic in the coefficients, but the complex spectrum is
+ * linear in them: X(f) = sum_a x_a S_a(f), S_a the spectra of the K basis sources' tapered traces, so the transforms are paid once
+ * per location and a candidate costs K complex multiply-adds and a root per kept bin.  Groups, K, receiver_weight, anarchy and
+ * candidates [ncand][K] are kiwi_hip_linear_fit_candidates'; the kernels use (float) x.  Per slot (enabled receiver component):
+ *   bins klo .. khi        the smallest range that holds every bin with a non-zero filter weight (0 .. ntrans / 2 without a filter);
+ *                          a skipped bin adds exactly nothing (its reference amplitude is |Xref| x 0; a non-zero one is refused)
+ *   per bin, ascending     re = xf_0 S_0.re; re = re + xf_a S_a.re, im the same, every product and sum rounded in fp32;
+ *                          b = |re + i im| with a correctly rounded root, times the filter weight where the receiver has a filter;
+ *                          d = ref_amp - b (synthetics factor as the comparator applies it); one fp64 accumulator: d^2 | |d|
+ *   slot misfit            (float) sqrt(df acc) | (float) (df acc), df = 1.f / ((float) ntrans dt); the slot norm factor is the basis
+ *                          sources' own (that of the group's first source)
+ *   outer fold             make_global_misfits per SLOT with outer_norm 1 (l1norm) or 2 (l2norm), receiver weights and anarchy: the
+ *                          expression sequence of kiwi_hip_outer_misfits for one draw of weights 1 -- nothing is receiver-level
+ *   free_scale 1           (ampspec_l2norm with outer l2norm only) the candidate is a direction: per slot P = sum a b, Q = sum b b,
+ *                          A = sum a a in fp64; s = (sum_r rw_r^2 sum_k df_k P_k) / (sum_r rw_r^2 sum_k df_k Q_k);
+ *                          misfit = sqrt(max((A - 2 s P) + s s Q, 0) / D), A the same weighted sum, D the fold's denominator
+ *   best_index, best_misfit [ngroup]   NaN passed over, then the value, then the lowest index; -1, NaN if none
+ *   status [ngroup]        0 evaluated; 1 no receiver counts; 2 a basis source of the group failed to discretise
+ *   misfit, scale          [ngroup][ncand] or NULL (scale needs free_scale)
+ *   slot_misfit  float [ngroup][ncand][nmis], slot_norm  float [ngroup][nmis], both or neither: the pair kiwi_hip_outer_misfits takes
+ *   spectra      float [ngroup][nmis][spectra_bins][K][2] or NULL: the kept bins of every slot from index 0 (re, im; no filter weight);
+ *   spectra_range  int [ngroup][nmis][3]: klo, khi, ntrans;  spectra_ref  float [ngroup][nmis][spectra_bins][2]: reference amplitude
+ *                          and filter weight of the kept bins.  spectra_bins from kiwi_hip_spectral_candidates_shape
+ * The answer does not depend on tiling, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.  Afterwards the context
+ * is what kiwi_hip_eval of the basis sources leaves.  Refused with a message that starts with "spectral_candidates:", nothing
+ * approximated: a method other than 3 or 4; an enabled receiver without a misfit taper or without references; K outside 1 .. 8; a
+ * range outside the batch; ncand < 1; a candidate that is not finite; a bad outer_norm or free_scale; free_scale outside method 3
+ * with outer l2norm, or together with slot_misfit; scale without free_scale; KIWI_HIP_FUSED_FFT=0; a slot whose transform length lies
+ * outside 64 .. 32768; basis sources of a group whose transform lengths differ. */
+int kiwi_hip_spectral_candidates(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                 const double *receiver_weight, int anarchy, int free_scale, int *best_index, double *best_misfit,
+                                 int *status, double *misfit, double *scale, float *slot_misfit, float *slot_norm, int spectra_bins,
+                                 float *spectra, int *spectra_range, float *spectra_ref);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_spectral_candidates_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece, int ncand,
+                                        const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                        int free_scale, int *best_index, double *best_misfit, int *status, double *misfit, double *scale,
+                                        float *slot_misfit, float *slot_norm, int spectra_bins, float *spectra, int *spectra_range,
+                                        float *spectra_ref);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the spectra kernel alone, ms[2] candidate
+ * kernels, ms[3] downloads.  The host's table of kept bins per chunk and its upload lie between ms[0] and ms[1], in neither */
+int kiwi_hip_get_spectral_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the kernels walk their work: *candidates_per_workgroup (one per lane) and *bins_per_stage of spectra per LDS stage of the
+ * candidate kernel; ctx may be NULL, the call then answers without a device (*spectra_bins 0).  With a context *spectra_bins is the
+ * row length of its spectra arrays (spectra_bins may be NULL).  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_spectral_candidates_shape(kiwi_hip_ctx *ctx, int K, int *candidates_per_workgroup, int *bins_per_stage, int *spectra_bins);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -276,6 +276,14 @@ struct kiwi_hip_ctx {
     float linfit_timescan_ms[4] = { 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, downloads of the last kiwi_hip_linear_fit_time_scan
     float linfit_cand_floating_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, Gram + xcorr kernels, candidate kernels, downloads of the last kiwi_hip_linear_fit_candidates_floating
     float linfit_cand_timescan_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };   // evaluation, Gram-scan kernel, solve kernels, candidate-scan kernels, downloads of the last kiwi_hip_linear_fit_candidates_time_scan
+    float speccand_ms[4] = { 0.f, 0.f, 0.f, 0.f };    // evaluation, spectra kernel, candidate kernels, downloads of the last kiwi_hip_spectral_candidates
+    struct SpecCandBufs {                             // device buffers of kiwi_hip_spectral_candidates, grown only (slots, info: records as ints)
+        DevBuf<double> w, misfit, scale, tile_v, best_misfit;
+        DevBuf<float> x, smis;
+        DevBuf<float2> spec;
+        DevBuf<int> tile_i, best_index, status, slots, info;
+    } speccand_bufs;
+    bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
@@ -1528,6 +1536,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
 #include "kiwi_linfit_candidates_timescan.hpp"
+#include "kiwi_spectral_candidates.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2901,11 +2910,15 @@ struct CandScanCall {
 // (kiwi_hip_linear_fit_candidates_floating_params the same with `candfloat` set: groups of K basis sources as for `fit`, a piece is
 // evaluated by linfit_candidates_floating::run)
 struct CandFloatCall { int K; const double *weight; int anarchy; linfit_candidates_floating::Floating fl; };
+// (kiwi_hip_spectral_candidates_params the same with `speccand` set: groups of K basis sources as for `fit`, a piece is evaluated by
+// spectral_candidates::run)
+struct SpecCandCall { int K; const double *weight; int anarchy; spectral_candidates::Call call; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
-                           const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr)
+                           const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
+                           const SpecCandCall *speccand = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2919,8 +2932,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (cand) { linfit::check_candidates(cand->cand, cand->K); linfit::check_setup(c, cand->K, cand->out); }
     if (candscan) linfit_candidates_timescan::check_setup(c, candscan->K, candscan->of, candscan->out, candscan->scan);
     if (candfloat) linfit_candidates_floating::check_setup(c, candfloat->K, candfloat->fl);
+    if (speccand) spectral_candidates::check_setup(c, speccand->K, speccand->call);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2956,17 +2970,21 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool candfloating = candfloat != nullptr;
             CandFloatCall mine_candfloat{};
             if (candfloating) { mine_candfloat = *candfloat; mine_candfloat.fl = candfloat->fl.at(s0 / unit, nrec_all); }
+            const bool speccanding = speccand != nullptr;
+            SpecCandCall mine_speccand{};
+            if (speccanding) { mine_speccand = *speccand; mine_speccand.call = speccand->call.at(s0 / unit, (int)nmis, unit); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
-                                       candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr);
+                                       candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
+                                       speccanding ? &mine_speccand : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3107,6 +3125,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                 linfit_candidates_timescan::fill_failed((size_t)(n / unit), (size_t)mine.of.nk, (size_t)nrec_all, mine.scan);
             }
             if (candfloat) linfit_candidates_floating::fill_failed(n / unit, nrec_all, candfloat->fl.at(s0 / unit, nrec_all));
+            if (speccand) spectral_candidates::fill_failed(n / unit, (int)nmis, unit, speccand->call.at(s0 / unit, (int)nmis, unit));
             continue;
         }
         upload_batch(c, hb);
@@ -3124,6 +3143,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             linfit_candidates_timescan::run(c, 0, n / unit, unit, mine.of, mine.weight, mine.anarchy, mine.out, mine.scan);
         } else if (candfloat)
             linfit_candidates_floating::run(c, 0, n / unit, unit, candfloat->weight, candfloat->anarchy, candfloat->fl.at(s0 / unit, nrec_all));
+        else if (speccand)
+            spectral_candidates::run(c, 0, n / unit, unit, speccand->weight, speccand->anarchy, speccand->call.at(s0 / unit, (int)nmis, unit));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3482,6 +3503,65 @@ int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_wor
     *shifts_per_pass = linfit_candidates_floating::kFloatShiftsPerPass;
     *shifts_per_stage = linfit_candidates_floating::kFloatShiftStage;
     return 0;
+}
+
+// The candidate evaluation under the amplitude-spectrum norms from the spectra of the basis sources (kiwi_spectral_candidates.hpp)
+int kiwi_hip_spectral_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                 const double *receiver_weight, int anarchy, int free_scale, int *best_index, double *best_misfit,
+                                 int *status, double *misfit, double *scale, float *slot_misfit, float *slot_norm, int spectra_bins,
+                                 float *spectra, int *spectra_range, float *spectra_ref)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->speccand_ms) t = 0.f;
+    const spectral_candidates::Call cl{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale,
+                                        slot_misfit, slot_norm, spectra_bins, spectra, spectra_range, spectra_ref };
+    spectral_candidates::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_spectral_candidates_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int ncand,
+                                        const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                        int free_scale, int *best_index, double *best_misfit, int *status, double *misfit, double *scale,
+                                        float *slot_misfit, float *slot_norm, int spectra_bins, float *spectra, int *spectra_range,
+                                        float *spectra_ref)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > spectral_candidates::kMaxBasis)
+        return fail(c, "spectral_candidates: K = " + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(spectral_candidates::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "spectral_candidates: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->speccand_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->speccand_ms) t = 0.f;
+    const SpecCandCall speccand{ K, receiver_weight, anarchy,
+                                 spectral_candidates::Call{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit,
+                                                            scale, slot_misfit, slot_norm, spectra_bins, spectra, spectra_range, spectra_ref } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, &speccand);
+}
+
+int kiwi_hip_get_spectral_candidates_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->speccand_ms[i];
+    return 0;
+}
+
+// (c may be null: the two kernel shapes need no device; with a context, spectra_bins is the row length of its spectra arrays)
+int kiwi_hip_spectral_candidates_shape(kiwi_hip_ctx *c, int K, int *candidates_per_workgroup, int *bins_per_stage, int *spectra_bins)
+{
+    if (K < 1 || K > spectral_candidates::kMaxBasis || !candidates_per_workgroup || !bins_per_stage) return c ? fail(c, "spectral_candidates: K outside 1 to 8 or a null argument") : 1;
+    *candidates_per_workgroup = spectral_candidates::kThreads;
+    *bins_per_stage = spectral_candidates::kStage;
+    if (spectra_bins) *spectra_bins = 0;
+    if (!c || !spectra_bins) return 0;
+    GUARD_BEGIN_DEV(c)
+    *spectra_bins = spectral_candidates::spectra_bins(c);
+    return 0;
+    GUARD_END(c)
 }
 
 // The candidate evaluation at many origin times from one synthesis of the basis (kiwi_linfit_candidates_timescan.hpp).  The free fit

@@ -27,6 +27,8 @@ CandidateFloatingScan = collections.namedtuple("CandidateFloatingScan", "best_in
 CandidateTimeScan = collections.namedtuple("CandidateTimeScan", "best_offset best_index best_misfit best_scale status cand_misfit cand_offset "
                                                                 "cand_scale misfit scale receiver_misfit receiver_norm fit_coef fit_misfit "
                                                                 "fit_status")
+SpectralCandidateScan = collections.namedtuple("SpectralCandidateScan", "best_index best_misfit status misfit scale slot_misfit slot_norm "
+                                                                        "spectra spectra_range spectra_ref")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -1060,6 +1062,98 @@ class Engine:
         candidate kernels, downloads)."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_ms(self.h, _fp(ms)), "get_linear_fit_candidates_floating_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ candidates under the amplitude-spectrum norms (kiwi_hip_spectral_candidates)
+    def spectral_candidates_shape(self, K, context=True):
+        """(candidates per workgroup, bins of spectra per LDS stage, spectra_bins) of `spectral_candidates` for K basis sources;
+        spectra_bins is the row length of this engine's `spectra` arrays for the sources it holds -- the longest transform any of
+        their slots needs, halved, plus one -- (0 with context=False, which needs no device)."""
+        c, b, n = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_spectral_candidates_shape(self.h if context else None, int(K), _ip(c), _ip(b), _ip(n)):
+            raise KiwiHipError("spectral_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(b[0]), int(n[0])
+
+    def _spectral_candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, slot_misfit, spectra,
+                                   spectra_bins=None):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        K, ng = int(K), int(ngroup)
+        if not 1 <= K <= self.linear_fit_max_basis():
+            raise KiwiHipError("spectral_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != K:
+            raise KiwiHipError("spectral_candidates: candidates must be [ncand, K = %d]" % K)
+        nc, nrec = len(x), len(self.components)
+        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        nb = (self.spectral_candidates_shape(K)[2] if spectra_bins is None else int(spectra_bins)) if spectra else 0
+        out = SpectralCandidateScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nc)) if misfit else None,
+                                    np.zeros((ng, nc)) if free_scale and misfit else None,
+                                    np.zeros((ng, nc, nmis), np.float32) if slot_misfit else None,
+                                    np.zeros((ng, nmis), np.float32) if slot_misfit else None,
+                                    np.zeros((ng, nmis, nb, K, 2), np.float32) if spectra else None,
+                                    np.zeros((ng, nmis, 3), np.int32) if spectra else None,
+                                    np.zeros((ng, nmis, nb, 2), np.float32) if spectra else None)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
+        tail = (nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.misfit), dp(out.scale), fp(out.slot_misfit),      # noqa: E731
+                        fp(out.slot_norm), nb, fp(out.spectra), None if out.spectra_range is None else _ip(out.spectra_range),
+                        fp(out.spectra_ref))
+        return tail, out, outs, (x, w)
+
+    def spectral_candidates(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                            free_scale=False, misfit=True, slot_misfit=False, spectra=False, spectra_bins=None):
+        """The misfits of given coefficient vectors under ampspec_l2norm / ampspec_l1norm (kiwi_hip_spectral_candidates): sources
+        [isrc0, isrc0 + ngroup K) are groups of K basis sources whose complex spectra are combined per candidate; the amplitude of
+        the combination is compared with the reference's inside the pass band.  Returns a `SpectralCandidateScan`:
+        best_index[ngroup] (-1: none), best_misfit[ngroup], status[ngroup] (0 evaluated, 1 no receiver counts, 2 a basis source
+        failed to discretise), misfit[ngroup, ncand] (misfit=True) and scale[ngroup, ncand] (free_scale: ampspec_l2norm with the
+        outer l2norm only), slot_misfit[ngroup, ncand, nmis] and slot_norm[ngroup, nmis] float32 (slot_misfit=True: what
+        `outer_misfits_slots` takes), spectra[ngroup, nmis, spectra_bins, K, 2], spectra_range[ngroup, nmis, 3] (klo, khi,
+        ntrans) and spectra_ref[ngroup, nmis, spectra_bins, 2] (reference amplitude, filter weight) with spectra=True
+        (spectra_bins: `spectral_candidates_shape`'s unless given)."""
+        tail, out, outs, keep = self._spectral_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit,
+                                                                slot_misfit, spectra, spectra_bins)
+        self._ck(self.L.kiwi_hip_spectral_candidates(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
+                                                     1 if free_scale else 0, *outs()), "spectral_candidates")
+        return out
+
+    def spectral_candidates_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                                   free_scale=False, misfit=True, slot_misfit=False, spectra=False, spectra_bins=None, piece=0):
+        """`spectral_candidates` for a parameter list of any length (kiwi_hip_spectral_candidates_params), cut into pieces and
+        over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list.  spectra=True without
+        spectra_bins: the first group is uploaded to size the rows; a later group that needs longer ones is refused by name."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("spectral_candidates: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("spectral_candidates: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        if spectra and spectra_bins is None:
+            self.set_source_params(sourcetype, p[:K])
+        tail, out, outs, keep = self._spectral_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit,
+                                                                slot_misfit, spectra, spectra_bins)
+        try:
+            self._ck(self.L.kiwi_hip_spectral_candidates_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail, 1 if anarchy else 0,
+                                                                1 if free_scale else 0, *outs()), "spectral_candidates")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def spectral_candidates_ms(self):
+        """HIP-event durations [ms] of the last `spectral_candidates`: (evaluation, the spectra kernel alone, candidate kernels,
+        downloads); the host's table of kept bins and its upload lie between the first two, in neither."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_spectral_candidates_ms(self.h, _fp(ms)), "get_spectral_candidates_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)

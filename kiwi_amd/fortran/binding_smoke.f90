@@ -42,6 +42,10 @@ program binding_smoke
     if (kiwi_hip_linear_fit_candidates_floating_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 11
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 1) stop 12
 
+    ! the candidate kernel of the amplitude-spectrum norms: candidates per workgroup and bins of spectra per LDS stage
+    if (kiwi_hip_spectral_candidates_shape( c_null_ptr, 6_c_int, per_group, per_stage, per_pass ) /= 0) stop 13
+    if (per_group < 64 .or. per_stage < 1 .or. per_pass /= 0) stop 14
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

@@ -706,6 +706,54 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, shifts_per_pass, shifts_per_stage
         end function
 
+        ! the candidate evaluation under the amplitude-spectrum norms from the spectra of the basis sources
+        integer(c_int) function kiwi_hip_spectral_candidates( ctx, isrc0, ngroup, k, ncand, candidates, outer_norm, receiver_weight, &
+                anarchy, free_scale, best_index, best_misfit, status, misfit, scale, slot_misfit, slot_norm, spectra_bins, spectra, &
+                spectra_range, spectra_ref ) bind(C, name='kiwi_hip_spectral_candidates')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, ncand, outer_norm, anarchy, free_scale, spectra_bins      ! isrc0 0-based
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_index(*)  ! (ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: misfit, scale           ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_misfit             ! c_loc of real(c_float) (nmis, ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_norm               ! c_loc of real(c_float) (nmis, ngroup), or c_null_ptr
+            type(c_ptr), value :: spectra                 ! c_loc of real(c_float) (2, k, spectra_bins, nmis, ngroup), or c_null_ptr
+            type(c_ptr), value :: spectra_range           ! c_loc of integer(c_int) (3, nmis, ngroup), or c_null_ptr
+            type(c_ptr), value :: spectra_ref             ! c_loc of real(c_float) (2, spectra_bins, nmis, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_spectral_candidates_params( ctx, sourcetype, ngroup, k, params, piece, ncand, candidates, &
+                outer_norm, receiver_weight, anarchy, free_scale, best_index, best_misfit, status, misfit, scale, slot_misfit, &
+                slot_norm, spectra_bins, spectra, spectra_range, spectra_ref ) bind(C, name='kiwi_hip_spectral_candidates_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, ncand, outer_norm, anarchy, free_scale, spectra_bins
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_index(*), status(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: misfit, scale, slot_misfit, slot_norm, spectra, spectra_range, spectra_ref      ! as in kiwi_hip_spectral_candidates
+        end function
+
+        integer(c_int) function kiwi_hip_get_spectral_candidates_ms( ctx, ms ) bind(C, name='kiwi_hip_get_spectral_candidates_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, spectra kernel, candidate kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_spectral_candidates_shape( ctx, k, candidates_per_workgroup, bins_per_stage, spectra_bins ) &
+                bind(C, name='kiwi_hip_spectral_candidates_shape')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx                           ! c_null_ptr: answers without a device
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, bins_per_stage, spectra_bins
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -254,3 +254,37 @@ def scan_double_couples_floating(engine, sourcetype, params, strikes, dips, rake
         out["cube"] = scan.misfit.reshape(len(p), len(s), len(d), len(r))
         out["cube_shifts"] = scan.cand_shift.reshape(len(p), len(s), len(d), len(r), -1)
     return out
+
+
+def scan_double_couples_spectral(engine, sourcetype, params, strikes, dips, rakes, moment=None, outer_norm="l1norm", unit=1e18,
+                                 receiver_weights=None, anarchy=False, piece=0, cube=False, slot_misfit=False):
+    """`scan_double_couples` under the amplitude-spectrum norms (`Engine.spectral_candidates_params`): the engine's misfit method
+    is ampspec_l2norm or ampspec_l1norm, and every mechanism of the grid is a combination of the complex spectra of the SIX
+    syntheses of a row, compared in amplitude inside the receivers' pass bands.  moment=None: the best scalar moment of every
+    mechanism is found on the way (ampspec_l2norm with outer l2norm only); otherwise all mechanisms have that moment [N m].
+    Amplitude spectra leave the polarity open: a mechanism and its opposite (rake + 180) have the same misfit, the lower grid
+    index is returned.  Returns a dict: strike, dip, rake, moment, misfit [N] of the best mechanism (NaN where there is none),
+    index [N] its row in the grid (-1: none), status [N] (0 evaluated, 1 no receiver counts, 2 the row failed to discretise),
+    scan: the `SpectralCandidateScan`; cube=True adds cube [N, ns, nd, nr], every mechanism's misfit (and moments, the same
+    shape, where moment is None)."""
+    p = np.atleast_2d(np.asarray(params, np.float32))
+    free = moment is None
+    if free and outer_norm != "l2norm":
+        raise KiwiHipError("scan_double_couples_spectral: moment=None (the best moment per mechanism) needs outer_norm l2norm; give a moment")
+    s, d, r = list(strikes), list(dips), list(rakes)
+    cand, sdr = double_couple_candidates(s, d, r, 1.0 if free else float(moment) / float(unit))
+    scan = engine.spectral_candidates_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, outer_norm=outer_norm,
+                                             receiver_weights=receiver_weights, anarchy=anarchy, free_scale=free, misfit=cube or free,
+                                             slot_misfit=slot_misfit, piece=piece)
+    has = scan.best_index >= 0
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, None], sdr[at], np.nan)
+    rows = np.arange(len(p))
+    mom = np.where(has, scan.scale[rows, at] * float(unit) if free else float(moment), np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=mom, misfit=scan.best_misfit, index=scan.best_index,
+               status=scan.status, scan=scan)
+    if cube:
+        out["cube"] = scan.misfit.reshape(len(p), len(s), len(d), len(r))
+        if free:
+            out["moments"] = (scan.scale * float(unit)).reshape(len(p), len(s), len(d), len(r))
+    return out

@@ -2,10 +2,10 @@
 """Register / LDS / spill table of the accumulate kernels, per kernel family and arithmetic contract, and of the outer-misfit
 kernels (kiwi_outer.hpp), the misfit-band kernels (kiwi_bands.hpp), the time-scan kernels (kiwi_timescan.hpp), the kernels of the
 linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation (kiwi_linfit_candidates.hpp) and of the candidate
-evaluation's time scan (kiwi_linfit_candidates_timescan.hpp) and with per-receiver shifts (kiwi_linfit_candidates_floating.hpp), from
-the compiler's own
+evaluation's time scan (kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp) and
+under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), from the compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands|timescan|linfit_timescan|linfit_candidates|linfit_candidates_timescan|linfit_candidates_floating]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands|timescan|linfit_timescan|linfit_candidates|linfit_candidates_timescan|linfit_candidates_floating|spectral_candidates]"""
 import json
 import os
 import re
@@ -19,7 +19,7 @@ FAMILIES = {1: "direct", 2: "grouped", 3: "multi", 4: "cell"}
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::") for o in out]
+    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::").replace("void spectral_candidates::", "spectral_candidates::") for o in out]
 
 
 KEYS = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"),
@@ -39,7 +39,8 @@ def collect_outer():
             for prefix, fam in (("_ZN5outer", "outer"), ("_ZN5bands", "bands"), ("_ZN8timescan", "timescan"),
                                 ("_ZN15linfit_timescan", "linfit_timescan"), ("_ZN6linfit", "linfit_candidates"),
                                 ("_ZN26linfit_candidates_timescan", "linfit_candidates_timescan"),
-                                ("_ZN26linfit_candidates_floating", "linfit_candidates_floating")):
+                                ("_ZN26linfit_candidates_floating", "linfit_candidates_floating"),
+                                ("_ZN19spectral_candidates", "spectral_candidates")):
                 if m.group(1).startswith(prefix) and (fam != "linfit_candidates" or "linfit_candidates_" in m.group(1)):
                     cur = {"family": fam, "arith": "exact", "mangled": m.group(1)}
                     rows.append(cur)
