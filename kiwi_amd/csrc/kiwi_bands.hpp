@@ -469,9 +469,7 @@ static void make_variants(kiwi_hip_ctx *c, const std::vector<std::pair<int, int>
 static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Out &out)
 {
     check_setup(c);
-    if (isrc0 < 0 || nsrc < 0 || (long long)isrc0 + nsrc > (long long)c->nsrc)
-        throw std::runtime_error("band_misfits: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + nsrc) +
-                                 " are not inside the uploaded batch of " + std::to_string(c->nsrc));
+    check_group_range("band_misfits", c, isrc0, nsrc, 1);
     if (nsrc == 0) return;
     BandState &st = c->band_state;
     if (!st.valid || st.prepare_gen != c->prepare_gen) reset_cache(c);
@@ -497,23 +495,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Out &out)
         st.attr = true;
     }
 
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 4; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<4> ev(c);
     std::vector<int> ntr_h;
     int s = isrc0;
     while (s < isrc0 + nsrc) {
-        // greedy chunk bounded by workspace bytes (eval_impl)
-        size_t bytes = 0;
-        int n = 0;
-        while (s + n < isrc0 + nsrc) {
-            const size_t nc = (size_t)(c->cent_ofs[s + n + 1] - c->cent_ofs[s + n]);
-            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s + n, (size_t)nrec) + c->syn_stride * sizeof(float) +
-                               (size_t)nband * nmis * 2 * sizeof(float);
-            if (n > 0 && (bytes + add > c->chunk_bytes_limit || n >= 65535)) break;
-            if (c->fft_needed && n >= c->fft_cap) break;
-            bytes += add; n++;
-        }
+        // a chunk of sources (groups of one) with their misfits and norms per band
+        const int n = next_group_chunk(c, isrc0, s - isrc0, nsrc, 1, 1, (size_t)nband * nmis * 2 * sizeof(float),
+                                       c->fft_needed ? c->fft_cap : kNoSourceCap);
         HIPCHECK(hipEventRecord(ev[0], c->stream));
         run_chunk(c, s, n, 0);
         HIPCHECK(hipEventRecord(ev[1], c->stream));
@@ -568,17 +556,10 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Out &out)
         if (o.global) HIPCHECK(hipMemcpyAsync(o.global, st.glob_d.p, (size_t)n * nband * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[3], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 3; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->bands_ms[i] += t;
-        }
+        for (int i = 0; i < 3; i++) ev.add_elapsed(c->bands_ms, i, i, i + 1);
         s += n;
     }
-    // what an evaluation of the range leaves behind (eval_impl): the context's own method and filters were evaluated on the way
-    c->last_isrc0 = isrc0; c->last_nsrc = nsrc; c->last_proc_which = 0;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + nsrc, 1);
+    leave_evaluated(c, isrc0, nsrc, 0);                    // the context's own method and filters were evaluated on the way
 }
 
 } // namespace bands

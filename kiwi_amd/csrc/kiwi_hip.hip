@@ -1486,9 +1486,14 @@ void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
     c->events.push_back({ e1, e2, 1 });
     c->events.push_back({ e2, e3, 2 });
     c->last_chunk0 = isrc0; c->last_chunkn = nsrc;
-    if (proc_which) { c->proc_chunk0 = isrc0; c->proc_chunkn = nsrc; c->proc_which_held = proc_which; }
-    else c->proc_which_held = c->proc_which_held;   // proc_d untouched
+    if (proc_which) { c->proc_chunk0 = isrc0; c->proc_chunkn = nsrc; c->proc_which_held = proc_which; }     // else: proc_d untouched
 }
+
+} // namespace
+
+#include "kiwi_group_run.hpp"
+
+namespace {
 
 int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 {
@@ -1506,10 +1511,9 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
         size_t bytes = 0;
         int n = 0;
         while (s + n < isrc0 + nsrc) {
-            const size_t nc = (size_t)(c->cent_ofs[s + n + 1] - c->cent_ofs[s + n]);
             const size_t syn_bytes = c->fuse_now ? (size_t)c->nmis * 64 * sizeof(double)
                                                              : c->syn_stride * sizeof(float) * ((proc_which ? 2 : 1) + (c->floating ? 1 : 0));
-            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + syn_bytes + plan_bytes(c, s + n, (size_t)nrec);
+            const size_t add = source_workspace_bytes(c, s + n, (size_t)nrec) + syn_bytes;
             if (n > 0 && (bytes + add > c->chunk_bytes_limit || n >= 65535)) break;
             if (c->fft_needed && n >= c->fft_cap) break;
             bytes += add; n++;
@@ -1517,9 +1521,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
         run_chunk(c, s, n, proc_which);
         s += n;
     }
-    c->last_isrc0 = isrc0; c->last_nsrc = nsrc; c->last_proc_which = proc_which;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + nsrc, 1);
+    leave_evaluated(c, isrc0, nsrc, proc_which);
     return 0;
 }
 
@@ -3117,7 +3119,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                                                       fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
             if (cand) {
                 linfit::fill_failed(n / unit, unit, nrec_all, cand->out.at(s0 / unit, unit, nrec_all));
-                linfit::cand_fill_failed(n / unit, nrec_all, cand->cand.at(s0 / unit, nrec_all));
+                linfit_candidates_timescan::fill_failed((size_t)(n / unit), 1, (size_t)nrec_all, linfit_candidates_timescan::plain(cand->cand.at(s0 / unit, nrec_all)));
             }
             if (candscan) {
                 const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);

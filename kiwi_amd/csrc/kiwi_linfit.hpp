@@ -235,16 +235,7 @@ static void launch_gram(kiwi_hip_ctx *c, int ng, const FftPair *pairs, double *n
 // the Gram kernel alone (the wide fit's for K <= 8: kiwi_linfit_wide.hpp)
 static void launch_gram_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, double *nbr)
 {
-    switch (K) {
-    case 1: launch_gram<1>(c, ng, pairs, nbr); break;
-    case 2: launch_gram<2>(c, ng, pairs, nbr); break;
-    case 3: launch_gram<3>(c, ng, pairs, nbr); break;
-    case 4: launch_gram<4>(c, ng, pairs, nbr); break;
-    case 5: launch_gram<5>(c, ng, pairs, nbr); break;
-    case 6: launch_gram<6>(c, ng, pairs, nbr); break;
-    case 7: launch_gram<7>(c, ng, pairs, nbr); break;
-    default: launch_gram<8>(c, ng, pairs, nbr); break;
-    }
+    by_basis(K, [&](auto k) { launch_gram<k.value>(c, ng, pairs, nbr); });
 }
 
 template <int K>
@@ -261,16 +252,7 @@ static void launch(kiwi_hip_ctx *c, int ng, const FftPair *pairs, const double *
 static void launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, double *nbr, double *coef,
                        double *misfit, int *status, double *pivot, double *normal)
 {
-    switch (K) {
-    case 1: launch<1>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 2: launch<2>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 3: launch<3>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 4: launch<4>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 5: launch<5>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 6: launch<6>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    case 7: launch<7>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    default: launch<8>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); break;
-    }
+    by_basis(K, [&](auto k) { launch<k.value>(c, ng, pairs, w_d, anarchy, nbr, coef, misfit, status, pivot, normal); });
 }
 
 // host arrays of the caller, each for the groups of ONE call of run(); any of pivot_min, normal, by_receiver, trace may be null
@@ -324,17 +306,65 @@ struct Candidates {
         return c;
     }
 };
-// device buffers of the candidate kernels, kept over the chunks of one run
-struct CandBufs {
-    DevBuf<double> x, misfit, scale, tile_v, best_misfit;
-    DevBuf<float> rmis, rnorm;
-    DevBuf<int> tile_i, best_index, status;
-};
 static void check_candidates(const Candidates &cd, int K);
-static size_t cand_bytes(const Candidates &cd, int nrec);
-static void cand_chunk(kiwi_hip_ctx *c, int K, int g0, int ng, const double *w_d, int anarchy, const double *nbr, const double *normal,
-                       const Candidates &cd, CandBufs &b, hipEvent_t after_kernels);
-static void cand_fill_failed(int ngroup, int nrec, const Candidates &cd);
+
+} // namespace linfit
+
+// The one implementation of the candidate evaluation (kiwi_linfit_candidates_timescan.hpp) evaluates the candidates at nk origin
+// times per group; run() below hands it the plain call as nk = 1 without the arrays that only a scan has.
+namespace linfit_candidates_timescan {
+
+// host arrays of the caller for the groups of ONE call of run(): best_offset, status [group]; best_index, best_misfit, best_scale
+// [group][nk]; cand_misfit, cand_offset, cand_scale [group][ncand]; misfit, scale [group][nk][ncand]; receiver_misfit
+// [group][nk][ncand][nrec]; receiver_norm [group][nrec].  x [ncand][K] is shared by all groups and offsets.  best_scale and
+// everything after it may be null; best_offset is null in the plain call and only there
+struct Scan {
+    const double *x; int ncand, outer_norm, free_scale;
+    int *best_offset, *best_index; double *best_misfit, *best_scale; int *status;
+    double *cand_misfit; int *cand_offset; double *cand_scale;
+    double *misfit, *scale;
+    float *receiver_misfit, *receiver_norm;
+    Scan at(size_t g, size_t nk, size_t nrec) const
+    {
+        Scan s = *this;
+        const size_t nc = (size_t)ncand;
+        s.status += g; s.best_index += g * nk; s.best_misfit += g * nk;
+        if (best_offset) s.best_offset += g;
+        if (best_scale) s.best_scale += g * nk;
+        if (cand_misfit) s.cand_misfit += g * nc;
+        if (cand_offset) s.cand_offset += g * nc;
+        if (cand_scale) s.cand_scale += g * nc;
+        if (misfit) s.misfit += g * nk * nc;
+        if (scale) s.scale += g * nk * nc;
+        if (receiver_misfit) s.receiver_misfit += g * nk * nc * nrec;
+        if (receiver_norm) s.receiver_norm += g * nrec;
+        return s;
+    }
+    bool scaled() const { return free_scale && (scale || receiver_misfit); }        // the scales are kept on the device
+};
+
+// the plain call's arrays as those of a scan of one offset: the layouts coincide at nk = 1
+static Scan plain(const linfit::Candidates &cd)
+{
+    return Scan{ cd.x, cd.ncand, cd.outer_norm, cd.free_scale, nullptr, cd.best_index, cd.best_misfit, nullptr, cd.status,
+                 nullptr, nullptr, nullptr, cd.misfit, cd.scale, cd.receiver_misfit, cd.receiver_norm };
+}
+
+// device buffers of the candidate kernels, kept over the chunks of one run
+struct Bufs {
+    DevBuf<double> x, misfit, scale, tile_v, best_misfit, best_scale, cand_misfit, cand_scale;
+    DevBuf<float> rmis, rnorm;
+    DevBuf<int> tile_i, best_index, best_offset, status, cand_offset;
+};
+
+static size_t bytes_per_group(const Scan &sc, int nrec, int nk);
+static void chunk(kiwi_hip_ctx *c, int K, int g0, int ng, int nk, const double *w_d, int anarchy, const double *nbr, const double *normal,
+                  const Scan &sc, Bufs &b, hipEvent_t after_kernels);
+static void fill_failed(size_t ngroup, size_t nk, size_t nrec, const Scan &sc);
+
+} // namespace linfit_candidates_timescan
+
+namespace linfit {
 
 // what the fit cannot do is refused, nothing approximated.  Leaves the context prepared.  floating_l2: the caller evaluates GIVEN
 // coefficient vectors under floating_l2norm (kiwi_linfit_candidates_floating.hpp) and fits nothing: that method, and only it, passes
@@ -369,9 +399,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
 {
     if (cd) check_candidates(*cd, K);
     check_setup(c, K, out, rb, wd);
-    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
-        throw std::runtime_error("linear_fit: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
-                                 " are not inside the uploaded batch of " + std::to_string(c->nsrc));
+    check_group_range("linear_fit", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), NN = nn_of(K);
     // With a misfit filter the kept traces come from the library transforms; the filtered references are made by the transform
@@ -390,14 +418,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     c->fuse_now = can_fuse(c, proc_which, isrc0, ngroup * K);
     if (c->fft_needed && c->fft_cap < K) throw std::runtime_error("linear_fit: the transform workspace (KIWI_HIP_CHUNK_MB) does not hold one group");
 
-    std::vector<double> w((size_t)nrec, 0.0);
-    for (int r = 0; r < nrec; r++)
-        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    const std::vector<double> w = receiver_weights(c, receiver_weight);
     DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d, wbr_d, trace_d;
     const size_t trace_len = rb ? (size_t)(rb->niter + 1) * 2 : 0;
     DevBuf<int> st_d, npos_d, nsol_d;
     DevBuf<double> penalty_d;
-    CandBufs cand;
+    const linfit_candidates_timescan::Scan scan = cd ? linfit_candidates_timescan::plain(*cd) : linfit_candidates_timescan::Scan{};
+    linfit_candidates_timescan::Bufs cand;
     w_d.alloc((size_t)nrec, &c->dev_bytes);
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (wd && wd->penalty) {
@@ -406,27 +433,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     }
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[6];                                      // (ev[5]: between the Gram and the solve kernels of the wide fit)
-    for (int i = 0; i < 6; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 6; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<6> ev(c);                           // (ev[5]: between the Gram and the solve kernels of the wide fit)
     std::vector<double> piv_h;
+    // per group: the sums by receiver, the reweighted sums of a robust fit of mode 1 beside them, the candidate outputs
+    const size_t per_group = (size_t)nrec * (NN + (rb && rb->mode == 1 ? NN + 2 : 0)) * sizeof(double) + (cd ? linfit_candidates_timescan::bytes_per_group(scan, nrec, 1) : 0);
     int g0 = 0;
     while (g0 < ngroup) {
-        // whole groups, bounded by workspace bytes the way eval_impl bounds its chunks
-        size_t bytes = 0;
-        int ng = 0;
-        while (g0 + ng < ngroup) {
-            size_t add = 0;
-            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
-                const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float) * 2;
-            }
-            add += (size_t)nrec * (NN + (rb && rb->mode == 1 ? NN + 2 : 0)) * sizeof(double);
-            if (cd) add += cand_bytes(*cd, nrec);
-            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
-            if (c->fft_needed && (ng + 1) * K > c->fft_cap) break;
-            bytes += add; ng++;
-        }
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 2, per_group, c->fft_needed ? c->fft_cap : kNoSourceCap);
         const int s0 = isrc0 + g0 * K;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
         run_chunk(c, s0, ng * K, proc_which);
@@ -450,7 +463,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             robust_launch_any(c, K, ng, c->fft_needed ? c->pairs_d.p : (const FftPair *)nullptr, w_d.p, anarchy ? 1 : 0, nbr_d.p, *rb, wbr_d.p,
                               coef_d.p, mis_d.p, st_d.p, trace_d.p);
         }
-        if (cd) cand_chunk(c, K, g0, ng, w_d.p, anarchy ? 1 : 0, nbr_d.p, normal_d.p, *cd, cand, ev[3]);    // (its downloads are queued behind ev[3])
+        if (cd)                                                // (the downloads of the candidates' results are queued behind ev[3])
+            linfit_candidates_timescan::chunk(c, K, g0, ng, 1, w_d.p, anarchy ? 1 : 0, nbr_d.p, normal_d.p, scan, cand, ev[3]);
         else HIPCHECK(hipEventRecord(ev[3], c->stream));
         piv_h.resize((size_t)ng);
         HIPCHECK(hipMemcpyAsync(out.coef + (size_t)g0 * K, coef_d.p, (size_t)ng * K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -469,38 +483,25 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             HIPCHECK(hipMemcpyAsync(out.trace + (size_t)g0 * trace_len, trace_d.p, (size_t)ng * trace_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[4], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 4; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->linfit_ms[i] += t;
-        }
+        for (int i = 0; i < 4; i++) ev.add_elapsed(c->linfit_ms, i, i, i + 1);
         if (wd) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[1], ev[5]));
-            c->linfit_wide_ms[0] += t;
-            HIPCHECK(hipEventElapsedTime(&t, ev[5], ev[2]));
-            c->linfit_wide_ms[1] += t;
+            ev.add_elapsed(c->linfit_wide_ms, 0, 1, 5);
+            ev.add_elapsed(c->linfit_wide_ms, 1, 5, 2);
         }
         g0 += ng;
     }
-    // what an evaluation of the range leaves behind (eval_impl)
-    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = proc_which;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
+    leave_evaluated(c, isrc0, ngroup * K, proc_which);
     // a basis source that failed to discretise: no fit for its group
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    for (int g = 0; g < ngroup; g++) {
-        bool bad = false;
-        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
-        if (!bad) continue;
+    for_each_failed_group(c, isrc0, ngroup, K, [&](int g) {
         out.status[g] = 2;
         out.misfit[g] = nan;
         for (int i = 0; i < K; i++) out.coef[(size_t)g * K + i] = nan;
         if (out.trace) std::fill(out.trace + (size_t)g * out.trace_rows * 2, out.trace + (size_t)(g + 1) * out.trace_rows * 2, nan);
         if (out.npositive) out.npositive[g] = 0;
         if (out.nsolves) out.nsolves[g] = 0;
-        if (cd) cand_fill_failed(1, nrec, cd->at(g, nrec));
-    }
+        if (cd) linfit_candidates_timescan::fill_failed(1, 1, (size_t)nrec, scan.at((size_t)g, 1, (size_t)nrec));
+    });
 }
 
 // groups whose basis sources could not be discretised at all (nothing was uploaded for them): status 2, NaN, zero sums

@@ -26,7 +26,7 @@
 //                 outer l1norm   L = L + v_r m_r;            D = D + v_r n_r;              misfit = L / D
 //                 outer l2norm   L = L + (v_r v_r) min val;  D = D + (v_r v_r) (n_r n_r);  misfit = sqrt(L / D)
 //               (NaN where no receiver counts).  Under l2norm the minimum sits inside the sum: there is no fold-then-evaluate form.
-//   fold        one wavefront per group: the tiles' bests folded in linfit_candidates_fold_kernel's order; a lane per receiver
+//   fold        one wavefront per group: the tiles' bests folded in linfit_candidates_scan_fold_kernel's order; a lane per receiver
 //               recomputes the winner's argmin with the same expressions (best_shift); status and receiver_norm = (float) n_r.
 // The order of "best" is kiwi_linfit_candidates.hpp's total order.  No atomics.
 // Status of a group: 0 evaluated; 1 no receiver counts: NaN, best_index -1; 2 a basis source failed to discretise (host).
@@ -290,19 +290,6 @@ struct Floating {
     }
 };
 
-// a refusal of one of the calls this one is made of, under this call's name
-template <class F>
-static void refusing(F &&f)
-{
-    try { f(); }
-    catch (const std::runtime_error &e) {
-        std::string m = e.what();
-        const size_t colon = m.find(": ");
-        if (colon != std::string::npos && m.find(' ') > colon) m = m.substr(colon + 2);       // (the other call's name in front)
-        throw std::runtime_error("linear_fit_candidates_floating: " + m);
-    }
-}
-
 // what this call cannot do is refused before anything runs, nothing approximated.  Leaves the context prepared
 static void check_setup(kiwi_hip_ctx *c, int K, const Floating &fl)
 {
@@ -310,7 +297,7 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Floating &fl)
         throw std::runtime_error("linear_fit_candidates_floating: K = " + std::to_string(K) + " basis sources per group; 1 to " +
                                  std::to_string(kMaxBasis) + " are supported");
     if (!fl.best_shift) throw std::runtime_error("linear_fit_candidates_floating: null best_shift array");
-    refusing([&] {
+    refusing("linear_fit_candidates_floating", [&] {
         linfit::check_candidates(linfit::Candidates{ fl.x, fl.ncand, fl.outer_norm, 0, fl.best_index, fl.best_misfit, fl.status, nullptr,
                                                      nullptr, nullptr, nullptr }, K);
     });
@@ -323,7 +310,7 @@ static void check_setup(kiwi_hip_ctx *c, int K, const Floating &fl)
                                  "kiwi_hip_linear_fit_candidates answers under l2norm; floating_l1norm is not quadratic in the coefficients)");
     double d = 0.0;
     int s = 0;
-    refusing([&] { linfit::check_setup(c, K, linfit::Out{ &d, &d, &s }, nullptr, nullptr, true); });
+    refusing("linear_fit_candidates_floating", [&] { linfit::check_setup(c, K, linfit::Out{ &d, &d, &s }, nullptr, nullptr, true); });
     if (fl.cand_shift)
         for (const auto &r : c->recv)
             if (r.enabled && r.ncomp > 0 && (r.float_lo < -32768 || r.float_hi > 32767))
@@ -379,18 +366,6 @@ static void launch_cand(kiwi_hip_ctx *c, int ng, int anarchy, const Floating &fl
     HIPCHECK(hipGetLastError());
 }
 
-#define KIWI_FLOAT_BY_K(fn, ...)                                                                                                       \
-    switch (K) {                                                                                                                       \
-    case 1: fn<1>(__VA_ARGS__); break;                                                                                                 \
-    case 2: fn<2>(__VA_ARGS__); break;                                                                                                 \
-    case 3: fn<3>(__VA_ARGS__); break;                                                                                                 \
-    case 4: fn<4>(__VA_ARGS__); break;                                                                                                 \
-    case 5: fn<5>(__VA_ARGS__); break;                                                                                                 \
-    case 6: fn<6>(__VA_ARGS__); break;                                                                                                 \
-    case 7: fn<7>(__VA_ARGS__); break;                                                                                                 \
-    default: fn<8>(__VA_ARGS__); break;                                                                                                \
-    }
-
 // groups that have no evaluation (a basis source failed to discretise): status 2, NaN, best_index -1, zeros per receiver
 static void fill_failed(int ngroup, int nrec, const Floating &fl)
 {
@@ -410,10 +385,7 @@ static void fill_failed(int ngroup, int nrec, const Floating &fl)
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Floating &fl)
 {
     check_setup(c, K, fl);
-    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
-        throw std::runtime_error("linear_fit_candidates_floating: sources " + std::to_string(isrc0) + " .. " +
-                                 std::to_string((long long)isrc0 + (long long)ngroup * K) + " are not inside the uploaded batch of " +
-                                 std::to_string(c->nsrc));
+    check_group_range("linear_fit_candidates_floating", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), NN = nn_of(K), M = K + 1, max_ns = c->max_ns;
     c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
@@ -421,9 +393,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     const int proc_which = 2;                                 // (the context refuses a misfit filter under a floating norm)
     c->fuse_now = can_fuse(c, proc_which, isrc0, ngroup * K);
 
-    std::vector<double> w((size_t)nrec, 0.0);
-    for (int r = 0; r < nrec; r++)
-        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    const std::vector<double> w = receiver_weights(c, receiver_weight);
     Bufs b;
     b.w.alloc((size_t)nrec, &c->dev_bytes);
     b.x.alloc((size_t)fl.ncand * K, &c->dev_bytes);
@@ -431,26 +401,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     HIPCHECK(hipMemcpyAsync(b.x.p, fl.x, (size_t)fl.ncand * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 5; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<5> ev(c);
     const size_t ntile = (size_t)(fl.ncand + kFloatCandThreads - 1) / kFloatCandThreads;
+    // per group: the sums by receiver, the sums per shift and the outputs
+    const size_t per_group = (size_t)nrec * NN * sizeof(double) + float_bytes(fl, K, nrec, max_ns);
     int g0 = 0;
     while (g0 < ngroup) {
-        // whole groups, bounded by workspace bytes the way linfit::run bounds its chunks
-        size_t bytes = 0;
-        int ng = 0;
-        while (g0 + ng < ngroup) {
-            size_t add = 0;
-            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
-                const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) +
-                       c->syn_stride * sizeof(float) * 3;
-            }
-            add += (size_t)nrec * NN * sizeof(double) + float_bytes(fl, K, nrec, max_ns);
-            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
-            bytes += add; ng++;
-        }
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 3, per_group, kNoSourceCap);
         const int s0 = isrc0 + g0 * K;
         const size_t ngr = (size_t)ng * nrec, nc = (size_t)ng * fl.ncand;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
@@ -462,7 +419,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         HIPCHECK(hipMemsetAsync(b.nbr.p, 0, ngr * NN * sizeof(double), c->stream));
         HIPCHECK(hipMemsetAsync(b.xc.p, 0, ngr * max_ns * M * sizeof(double), c->stream));
         linfit::launch_gram_any(c, K, ng, nullptr, b.nbr.p);
-        KIWI_FLOAT_BY_K(launch_xcorr, c, ng, b)
+        by_basis(K, [&](auto k) { launch_xcorr<k.value>(c, ng, b); });
         HIPCHECK(hipEventRecord(ev[2], c->stream));
         b.tile_v.ensure((size_t)ng * ntile, &c->dev_bytes); b.tile_i.ensure((size_t)ng * ntile, &c->dev_bytes);
         b.best_index.ensure((size_t)ng, &c->dev_bytes); b.best_misfit.ensure((size_t)ng, &c->dev_bytes); b.status.ensure((size_t)ng, &c->dev_bytes);
@@ -471,7 +428,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         if (fl.cand_shift) b.cshift.ensure(nc * nrec, &c->dev_bytes);
         if (fl.receiver_misfit) b.rmis.ensure(nc * nrec, &c->dev_bytes);
         if (fl.receiver_norm) b.rnorm.ensure(ngr, &c->dev_bytes);
-        KIWI_FLOAT_BY_K(launch_cand, c, ng, anarchy ? 1 : 0, fl, b)
+        by_basis(K, [&](auto k) { launch_cand<k.value>(c, ng, anarchy ? 1 : 0, fl, b); });
         HIPCHECK(hipEventRecord(ev[3], c->stream));
         const Floating o = fl.at(g0, nrec);
         HIPCHECK(hipMemcpyAsync(o.best_index, b.best_index.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -484,24 +441,11 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         if (fl.receiver_norm) HIPCHECK(hipMemcpyAsync(o.receiver_norm, b.rnorm.p, ngr * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[4], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 4; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->linfit_cand_floating_ms[i] += t;
-        }
+        for (int i = 0; i < 4; i++) ev.add_elapsed(c->linfit_cand_floating_ms, i, i, i + 1);
         g0 += ng;
     }
-    // what an evaluation of the range leaves behind (eval_impl)
-    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = proc_which;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
-    for (int g = 0; g < ngroup; g++) {
-        bool bad = false;
-        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
-        if (bad) fill_failed(1, nrec, fl.at(g, nrec));
-    }
+    leave_evaluated(c, isrc0, ngroup * K, proc_which);
+    for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { fill_failed(1, nrec, fl.at(g, nrec)); });
 }
-
-#undef KIWI_FLOAT_BY_K
 
 } // namespace linfit_candidates_floating

@@ -1,67 +1,64 @@
-// kiwi_linfit_candidates_timescan.hpp -- the misfits of many GIVEN coefficient vectors per group at MANY origin times from ONE
-// synthesis of the basis (kiwi_hip_linear_fit_candidates_time_scan): kiwi_linfit_timescan.hpp's sums per offset with
-// kiwi_linfit_candidates.hpp's evaluation on them.  Nothing new is computed: per chunk of whole groups
-//   linfit_scan_gram_kernel<K, J>, linfit_solve_kernel<K>   unchanged: nbr[(g nk + j)][receiver][NN] and normal[(g nk + j)][NN]
-//   linfit_candidates_scan_kernel<K>   one workgroup of kCandThreads lanes per (group, tile of kCandThreads candidates); a lane owns
+// kiwi_linfit_candidates_timescan.hpp -- misfits of many GIVEN coefficient vectors per group from the normal equations the linear
+// fit keeps on the device: the synthetics are linear in the coefficients, so a candidate x (a trial double couple as a combination
+// of the six elementary tensors, kiwi_amd/mtfit.py) needs no synthesis of its own.  One implementation serves two calls:
+// kiwi_hip_linear_fit_candidates_time_scan evaluates the candidates at MANY origin times from ONE synthesis of the basis
+// (kiwi_linfit_timescan.hpp's sums per offset), kiwi_hip_linear_fit_candidates is the case of one offset, nk = 1, on the sums of
+// kiwi_linfit.hpp (linfit::run hands it over; the layouts below coincide there).  Included by kiwi_hip.hip after the other linfit
+// headers, under the same -ffp-contract=off: every fp64 operation below is rounded on its own, and
+// tests/linfit_candidates_restatement.py and tests/linfit_candidates_timescan_restatement.py restate each in the same order (the GPU
+// tests ask for bit identity).  Notation as in kiwi_linfit.hpp and kiwi_linfit_robust.hpp: N_r = (G_r, b_r, R_r) the sums of
+// receiver r from the Gram kernel, N = (G, b, R) their fold by linfit_solve_kernel (weights, anarchy), w_r = receiver_weight[r] (0
+// for a disabled receiver).  Per chunk of whole groups
+//   linfit_gram_kernel<K> or linfit_scan_gram_kernel<K, J>, linfit_solve_kernel<K>   unchanged: nbr[(g nk + j)][receiver][NN] and
+//       normal[(g nk + j)][NN]
+//   linfit_candidates_scan_kernel<K>, linfit_candidates_kernel<K>   two entries of ONE body (`candidates_body`), the second with
+//       nk = 1 known to the compiler for the plain call.  One workgroup of kCandThreads lanes per (group, tile of kCandThreads
+//       candidates); a lane owns
 //       ONE candidate with its x in registers, loaded once, and walks the nk offsets itself.  Per offset the rows of (g, j) are
-//       staged in LDS (passes 0 and 2: kCandStage receivers at a time from nbr; pass 1: the one folded row from normal) and read as
-//       a broadcast, receivers ascending, into the lane's own accumulators: linfit_candidates_kernel's passes operation for operation
-//       (`quad`, the clamp, the roots), so offset j has the bits that kernel gives on the rows of (g, j).  The lane keeps its running
-//       (minimum over j, argmin j, scale there) -- NaN passed over, the smaller value, the first j among equal values -- and writes
-//       cand_misfit, cand_offset, cand_scale once at the end.  Per offset the workgroup folds its best in linfit_candidates_kernel's
-//       order into tile_v, tile_i[g][j][tile].
+//       staged in LDS (passes 0 and 2: kCandStage receivers at a time from nbr; pass 1: the one folded row from normal); every lane
+//       reads the same address at the same time (a broadcast), receivers ascending, into the candidate's own accumulators: the
+//       result does not depend on the tiling.  Per row q = (G, b, R) and vector x, `quad`:
+//           xb = 0; xb = xb + x_i b_i;  row_i = 0; row_i = row_i + G_ij x_j (j ascending);  xgx = 0; xgx = xgx + x_i row_i
+//       -- the sums linfit_solve_kernel and robust_receiver_kernel form --, then val = (R - 2 xb) + xgx, clamped at 0.
+//         pass 0    outer l1norm, rows N_r.  A receiver with w_r == 0 or not R_r > 0 is skipped.  m = sqrt(val); n = sqrt(R_r);
+//                   v = anarchy ? w_r / n : w_r;  L = L + v m;  D = D + v n;  misfit = L / D (NaN where no receiver counts);
+//                   receiver_misfit[g][j][c][r] = (float) m.  This is iterate 0 of robust_receiver_kernel at a fixed x.
+//         pass 1    outer l2norm, the folded row N as the only "receiver": misfit = sqrt(val / R), NaN unless R > 0.
+//                   free_scale: the candidate is a direction u; quad(N, u) gives u.b and u.G.u; a = (u.b) / (u.G.u), NaN (and a
+//                   NaN misfit) unless u.G.u > 0; x_i = a u_i; then as above.  scale[g][j][c] = a.
+//         pass 2    outer l2norm, receiver_misfit only: rows N_r, x (free_scale: x_i = scale[g][j][c] u_i, the product of pass 1)
+//                   and (float) m per counted receiver as in pass 0; NaN for a candidate whose scale is NaN.
+//       The lane keeps its running (minimum over j, argmin j, scale there) -- NaN passed over, the smaller value, the first j among
+//       equal values -- and writes cand_misfit, cand_offset, cand_scale once at the end.  Per offset every lane has its (misfit,
+//       index); wavefront and workgroup fold them in the order below into tile_v, tile_i[g][j][tile].
 //   linfit_candidates_scan_fold_kernel<K>   one wavefront per group: per offset the tiles' bests folded in the same order,
 //       best_scale = (u.b) / (u.G.u) of the winner by `quad` on the folded row of (g, j) -- the bits scale[g][j][best_index] has --,
-//       then the offsets walked for best_offset (the smaller best_misfit, then the lowest j); status and receiver_norm from the
-//       rows of offset 0 (R_r does not depend on the offset).
-// The order of "best" is total, so no answer depends on tile shape, chunking or pieces.  No atomics.  Included by kiwi_hip.hip after
-// the other linfit headers, under the same -ffp-contract=off; tests/linfit_candidates_timescan_restatement.py restates the folds.
+//       then the offsets walked for best_offset (the smaller best_misfit, then the lowest j); status and receiver_norm[g][r] =
+//       (float) sqrt(R_r) of the receivers that count (0 otherwise) from the rows of offset 0 (R_r does not depend on the offset).
+// The order of "best" is total -- a NaN misfit never wins, then the smaller value, then the LOWER candidate index --, so no answer
+// depends on tile shape, chunking or pieces.  No atomics.
+// Status of a group: 0 evaluated; 1 no data (l2norm: R not positive; l1norm: no receiver counts): NaN, best_index -1; 2 a basis
+// source failed to discretise (set on the host).  A group and offset whose candidates are all NaN has best_index -1.
 
 namespace linfit_candidates_timescan {
 
 using linfit::kCandStage;
 using linfit::kCandThreads;
 
-// host arrays of the caller for the groups of ONE call of run(): best_offset, status [group]; best_index, best_misfit, best_scale
-// [group][nk]; cand_misfit, cand_offset, cand_scale [group][ncand]; misfit, scale [group][nk][ncand]; receiver_misfit
-// [group][nk][ncand][nrec]; receiver_norm [group][nrec].  x [ncand][K] is shared by all groups and offsets.  best_scale and
-// everything after it may be null
-struct Scan {
-    const double *x; int ncand, outer_norm, free_scale;
-    int *best_offset, *best_index; double *best_misfit, *best_scale; int *status;
-    double *cand_misfit; int *cand_offset; double *cand_scale;
-    double *misfit, *scale;
-    float *receiver_misfit, *receiver_norm;
-    Scan at(size_t g, size_t nk, size_t nrec) const
-    {
-        Scan s = *this;
-        const size_t nc = (size_t)ncand;
-        s.best_offset += g; s.status += g; s.best_index += g * nk; s.best_misfit += g * nk;
-        if (best_scale) s.best_scale += g * nk;
-        if (cand_misfit) s.cand_misfit += g * nc;
-        if (cand_offset) s.cand_offset += g * nc;
-        if (cand_scale) s.cand_scale += g * nc;
-        if (misfit) s.misfit += g * nk * nc;
-        if (scale) s.scale += g * nk * nc;
-        if (receiver_misfit) s.receiver_misfit += g * nk * nc * nrec;
-        if (receiver_norm) s.receiver_norm += g * nrec;
-        return s;
-    }
-    bool scaled() const { return free_scale && (scale || receiver_misfit); }        // the scales are kept on the device
-};
+// (Scan, the caller's host arrays, and Bufs, the device buffers kept over the chunks of one run: kiwi_linfit.hpp, whose run() needs them)
 
 // nbr: [group][nk][nrec][NN], normal: [group][nk][NN], w: [nrec] (pass 1: not read).  x: [ncand][K].  misfit, scale:
 // [group][nk][ncand] or null.  rmis: [group][nk][ncand][nrec] or null, zeroed before the launch.  cand_misfit, cand_offset,
 // cand_scale: [group][ncand] or null.  tile_v, tile_i: [group][nk][gridDim.x] (pass 2: not written).  blockIdx.x = tile of
-// candidates, blockIdx.y = group.  The passes are linfit_candidates_kernel's
-template <int K>
-__global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(const double *__restrict__ nbr, const double *__restrict__ normal,
-                                                                              int nrec, int nk, const double *__restrict__ w, int anarchy,
-                                                                              int pass, int free_scale, const double *__restrict__ x, int ncand,
-                                                                              double *__restrict__ misfit, double *__restrict__ scale,
-                                                                              float *__restrict__ rmis, double *__restrict__ cand_misfit,
-                                                                              int *__restrict__ cand_offset, double *__restrict__ cand_scale,
-                                                                              double *__restrict__ tile_v, int *__restrict__ tile_i)
+// candidates, blockIdx.y = group.  kScan = false: the one offset of the plain call -- nk = 1, no cand_* array -- known to the
+// compiler: without the walk over the offsets a lane needs fewer registers (K = 6: 114 against 140, 4 waves per SIMD against 3)
+template <int K, bool kScan>
+__device__ __forceinline__ void candidates_body(const double *__restrict__ nbr, const double *__restrict__ normal, int nrec, int nk,
+                                                const double *__restrict__ w, int anarchy, int pass, int free_scale,
+                                                const double *__restrict__ x, int ncand, double *__restrict__ misfit,
+                                                double *__restrict__ scale, float *__restrict__ rmis, double *__restrict__ cand_misfit,
+                                                int *__restrict__ cand_offset, double *__restrict__ cand_scale, double *__restrict__ tile_v,
+                                                int *__restrict__ tile_i)
 {
     constexpr int NN = K * (K + 1) / 2 + K + 1;
     __shared__ double sq[kCandStage * NN];
@@ -78,8 +75,8 @@ __global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(co
     for (int i = 0; i < K; i++) xu[i] = live ? x[(size_t)cand * K + i] : 0.0;
     double cm = nan, cs = nan;                              // the candidate's smallest misfit over the offsets, the scale there
     int co = -1;                                            // and its offset
-    for (int j = 0; j < nk; j++) {
-        const size_t gj = (size_t)g * nk + j;
+    for (int j = 0; j < (kScan ? nk : 1); j++) {
+        const size_t gj = kScan ? (size_t)g * nk + j : (size_t)g;
         const size_t slot = gj * ncand + (live ? cand : 0);
         const double *__restrict__ rows = pass == 1 ? normal + gj * NN : nbr + gj * nrec * NN;
         double xc[K];
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(co
         bool counted = false;
         for (int r0 = 0; r0 < nrows; r0 += kCandStage) {
             const int nr = nrows - r0 < kCandStage ? nrows - r0 : kCandStage;
-            __syncthreads();                                // (the rows of the stage before, the bests of the offset before)
+            if (kScan || r0 > 0) __syncthreads();           // (the rows of the stage before, the bests of the offset before)
             const double *__restrict__ src = rows + (size_t)r0 * NN;
             for (int p = tid; p < nr * NN; p += kCandThreads) sq[p] = src[p];
             if (tid < nr) sw[tid] = pass == 1 ? 1.0 : w[r0 + tid];
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(co
             if (misfit) misfit[slot] = mf;
             if (scale) scale[slot] = a;
         }
-        if (mf == mf && (co < 0 || mf < cm)) { cm = mf; co = j; cs = a; }
+        if (kScan && mf == mf && (co < 0 || mf < cm)) { cm = mf; co = j; cs = a; }
         double bv = mf;
         int bi = (live && mf == mf) ? cand : -1;
         linfit::wave_best(bv, bi);
@@ -149,15 +146,40 @@ __global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(co
             tile_i[gj * gridDim.x + blockIdx.x] = bi;
         }
     }
-    if (pass == 2 || !live) return;
+    if (!kScan || pass == 2 || !live) return;
     const size_t at = (size_t)g * ncand + cand;
     if (cand_misfit) cand_misfit[at] = cm;
     if (cand_offset) cand_offset[at] = co;
     if (cand_scale) cand_scale[at] = cs;
 }
 
+template <int K>
+__global__ __launch_bounds__(kCandThreads) void linfit_candidates_scan_kernel(const double *__restrict__ nbr, const double *__restrict__ normal,
+                                                                              int nrec, int nk, const double *__restrict__ w, int anarchy,
+                                                                              int pass, int free_scale, const double *__restrict__ x, int ncand,
+                                                                              double *__restrict__ misfit, double *__restrict__ scale,
+                                                                              float *__restrict__ rmis, double *__restrict__ cand_misfit,
+                                                                              int *__restrict__ cand_offset, double *__restrict__ cand_scale,
+                                                                              double *__restrict__ tile_v, int *__restrict__ tile_i)
+{
+    candidates_body<K, true>(nbr, normal, nrec, nk, w, anarchy, pass, free_scale, x, ncand, misfit, scale, rmis, cand_misfit, cand_offset,
+                             cand_scale, tile_v, tile_i);
+}
+
+template <int K>
+__global__ __launch_bounds__(kCandThreads) void linfit_candidates_kernel(const double *__restrict__ nbr, const double *__restrict__ normal,
+                                                                         int nrec, const double *__restrict__ w, int anarchy, int pass,
+                                                                         int free_scale, const double *__restrict__ x, int ncand,
+                                                                         double *__restrict__ misfit, double *__restrict__ scale,
+                                                                         float *__restrict__ rmis, double *__restrict__ tile_v,
+                                                                         int *__restrict__ tile_i)
+{
+    candidates_body<K, false>(nbr, normal, nrec, 1, w, anarchy, pass, free_scale, x, ncand, misfit, scale, rmis, nullptr, nullptr, nullptr,
+                              tile_v, tile_i);
+}
+
 // tile_v, tile_i: [group][nk][ntile].  nbr, normal, w as above.  best_index, best_misfit, best_scale (or null): [group][nk];
-// best_offset, status: [group]; rnorm: [group][nrec] or null.  blockIdx.x = group
+// best_offset (or null), status: [group]; rnorm: [group][nrec] or null.  blockIdx.x = group
 template <int K>
 __global__ __launch_bounds__(64) void linfit_candidates_scan_fold_kernel(const double *__restrict__ tile_v, const int *__restrict__ tile_i,
                                                                          int ntile, const double *__restrict__ nbr,
@@ -203,35 +225,15 @@ __global__ __launch_bounds__(64) void linfit_candidates_scan_fold_kernel(const d
     }
     const int any = __any(counts);
     if (lane == 0) {
-        best_offset[g] = oj;
+        if (best_offset) best_offset[g] = oj;
         status[g] = (outer == 2 ? normal[(size_t)g * nk * NN + NN - 1] > 0.0 : any != 0) ? 0 : 1;
-    }
-}
-
-// device buffers of the candidate scan, kept over the chunks of one run
-struct Bufs {
-    DevBuf<double> x, misfit, scale, tile_v, best_misfit, best_scale, cand_misfit, cand_scale;
-    DevBuf<float> rmis, rnorm;
-    DevBuf<int> tile_i, best_index, best_offset, status, cand_offset;
-};
-
-// a refusal of one of the calls this one is made of, under this call's name
-template <class F>
-static void refusing(F &&f)
-{
-    try { f(); }
-    catch (const std::runtime_error &e) {
-        std::string m = e.what();
-        const size_t colon = m.find(": ");
-        if (colon != std::string::npos && m.find(' ') > colon) m = m.substr(colon + 2);       // (the other call's name in front)
-        throw std::runtime_error("linear_fit_candidates_time_scan: " + m);
     }
 }
 
 // what the call cannot do is refused before anything runs: everything the linear fit's time scan and the candidate evaluation refuse
 static void check_setup(kiwi_hip_ctx *c, int K, const timescan::Offsets &of, const linfit_timescan::Out &fit, const Scan &sc)
 {
-    refusing([&] {
+    refusing("linear_fit_candidates_time_scan", [&] {
         if (!sc.best_offset) throw std::runtime_error("null best_offset array");
         linfit::check_candidates(linfit::Candidates{ sc.x, sc.ncand, sc.outer_norm, sc.free_scale, sc.best_index, sc.best_misfit, sc.status,
                                                      nullptr, sc.scale, nullptr, nullptr }, K);
@@ -241,14 +243,17 @@ static void check_setup(kiwi_hip_ctx *c, int K, const timescan::Offsets &of, con
     });
 }
 
-// device bytes of one group's candidate outputs (the chunk is bounded by them too)
+// device bytes of one group's candidate outputs as the chunks count them (they are bounded by them too): per offset the tiles' bests
+// and the per-candidate arrays that were asked for; a scan counts its bests per offset, its per-candidate minima and receiver_norm
+// on top, asked for or not, the plain call (no best_offset) none of them.  Chunk boundaries follow from these figures
 static size_t bytes_per_group(const Scan &sc, int nrec, int nk)
 {
     const size_t ntile = (size_t)(sc.ncand + kCandThreads - 1) / kCandThreads, nc = (size_t)sc.ncand;
-    return (size_t)nk * (ntile * (sizeof(double) + sizeof(int)) + 2 * sizeof(double) + sizeof(int) +
-                         nc * ((sc.misfit ? sizeof(double) : 0) + (sc.scaled() ? sizeof(double) : 0) +
-                               (sc.receiver_misfit ? (size_t)nrec * sizeof(float) : 0))) +
-           nc * (2 * sizeof(double) + sizeof(int)) + (size_t)nrec * sizeof(float);
+    const size_t per_offset = ntile * (sizeof(double) + sizeof(int)) +
+                              nc * ((sc.misfit ? sizeof(double) : 0) + (sc.scaled() ? sizeof(double) : 0) +
+                                    (sc.receiver_misfit ? (size_t)nrec * sizeof(float) : 0));
+    if (!sc.best_offset) return (size_t)nk * per_offset;
+    return (size_t)nk * (per_offset + 2 * sizeof(double) + sizeof(int)) + nc * (2 * sizeof(double) + sizeof(int)) + (size_t)nrec * sizeof(float);
 }
 
 // behind the Gram-scan and solve kernels of one chunk: nbr and normal as they left them on the stream
@@ -262,23 +267,25 @@ static void launch(kiwi_hip_ctx *c, int ng, int nk, const double *w_d, int anarc
     double *cm = sc.cand_misfit ? b.cand_misfit.p : nullptr, *cs = sc.cand_scale ? b.cand_scale.p : nullptr;
     int *co = sc.cand_offset ? b.cand_offset.p : nullptr;
     if (rm) HIPCHECK(hipMemsetAsync(rm, 0, (size_t)ng * nk * sc.ncand * nrec * sizeof(float), c->stream));
+    // one pass of the candidate kernel; the plain call (no best_offset, nk = 1) through the entry without the walk over the offsets
+    auto pass = [&](int which, int free_scale, double *misfit, double *scale, float *rmis, double *cand_misfit, int *cand_offset,
+                    double *cand_scale, double *tile_v, int *tile_i) {
+        if (sc.best_offset)
+            hipLaunchKernelGGL(linfit_candidates_scan_kernel<K>, grid, dim3(kCandThreads), 0, c->stream, nbr, normal, nrec, nk, w_d, anarchy,
+                               which, free_scale, b.x.p, sc.ncand, misfit, scale, rmis, cand_misfit, cand_offset, cand_scale, tile_v, tile_i);
+        else
+            hipLaunchKernelGGL(linfit_candidates_kernel<K>, grid, dim3(kCandThreads), 0, c->stream, nbr, normal, nrec, w_d, anarchy, which,
+                               free_scale, b.x.p, sc.ncand, misfit, scale, rmis, tile_v, tile_i);
+        HIPCHECK(hipGetLastError());
+    };
     if (sc.outer_norm == 1) {
-        hipLaunchKernelGGL(linfit_candidates_scan_kernel<K>, grid, dim3(kCandThreads), 0, c->stream, nbr, normal, nrec, nk, w_d, anarchy, 0, 0,
-                           b.x.p, sc.ncand, mis, (double *)nullptr, rm, cm, co, (double *)nullptr, b.tile_v.p, b.tile_i.p);
-        HIPCHECK(hipGetLastError());
+        pass(0, 0, mis, nullptr, rm, cm, co, nullptr, b.tile_v.p, b.tile_i.p);
     } else {
-        hipLaunchKernelGGL(linfit_candidates_scan_kernel<K>, grid, dim3(kCandThreads), 0, c->stream, nbr, normal, nrec, nk, w_d, anarchy, 1,
-                           sc.free_scale, b.x.p, sc.ncand, mis, scl, (float *)nullptr, cm, co, cs, b.tile_v.p, b.tile_i.p);
-        HIPCHECK(hipGetLastError());
-        if (rm) {
-            hipLaunchKernelGGL(linfit_candidates_scan_kernel<K>, grid, dim3(kCandThreads), 0, c->stream, nbr, normal, nrec, nk, w_d, anarchy, 2,
-                               sc.free_scale, b.x.p, sc.ncand, (double *)nullptr, scl, rm, (double *)nullptr, (int *)nullptr,
-                               (double *)nullptr, (double *)nullptr, (int *)nullptr);
-            HIPCHECK(hipGetLastError());
-        }
+        pass(1, sc.free_scale, mis, scl, nullptr, cm, co, cs, b.tile_v.p, b.tile_i.p);
+        if (rm) pass(2, sc.free_scale, nullptr, scl, rm, nullptr, nullptr, nullptr, nullptr, nullptr);
     }
     hipLaunchKernelGGL(linfit_candidates_scan_fold_kernel<K>, dim3((unsigned)ng), dim3(64), 0, c->stream, b.tile_v.p, b.tile_i.p, ntile, nbr,
-                       normal, w_d, nrec, nk, sc.outer_norm, b.x.p, b.best_offset.p, b.best_index.p, b.best_misfit.p,
+                       normal, w_d, nrec, nk, sc.outer_norm, b.x.p, sc.best_offset ? b.best_offset.p : (int *)nullptr, b.best_index.p, b.best_misfit.p,
                        sc.best_scale ? b.best_scale.p : (double *)nullptr, b.status.p, sc.receiver_norm ? b.rnorm.p : (float *)nullptr);
     HIPCHECK(hipGetLastError());
 }
@@ -295,7 +302,8 @@ static void chunk(kiwi_hip_ctx *c, int K, int g0, int ng, int nk, const double *
     }
     b.tile_v.ensure(nj * ntile, &c->dev_bytes); b.tile_i.ensure(nj * ntile, &c->dev_bytes);
     b.best_index.ensure(nj, &c->dev_bytes); b.best_misfit.ensure(nj, &c->dev_bytes);
-    b.best_offset.ensure((size_t)ng, &c->dev_bytes); b.status.ensure((size_t)ng, &c->dev_bytes);
+    b.status.ensure((size_t)ng, &c->dev_bytes);
+    if (sc.best_offset) b.best_offset.ensure((size_t)ng, &c->dev_bytes);
     if (sc.best_scale) b.best_scale.ensure(nj, &c->dev_bytes);
     if (sc.cand_misfit) b.cand_misfit.ensure(nc, &c->dev_bytes);
     if (sc.cand_offset) b.cand_offset.ensure(nc, &c->dev_bytes);
@@ -304,16 +312,7 @@ static void chunk(kiwi_hip_ctx *c, int K, int g0, int ng, int nk, const double *
     if (sc.scaled()) b.scale.ensure(njc, &c->dev_bytes);
     if (sc.receiver_misfit) b.rmis.ensure(njc * nrec, &c->dev_bytes);
     if (sc.receiver_norm) b.rnorm.ensure((size_t)ng * nrec, &c->dev_bytes);
-    switch (K) {
-    case 1: launch<1>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 2: launch<2>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 3: launch<3>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 4: launch<4>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 5: launch<5>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 6: launch<6>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    case 7: launch<7>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    default: launch<8>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); break;
-    }
+    by_basis(K, [&](auto k) { launch<k.value>(c, ng, nk, w_d, anarchy, nbr, normal, sc, b); });
     HIPCHECK(hipEventRecord(after_kernels, c->stream));
     const Scan o = sc.at((size_t)g0, (size_t)nk, nrec);
     auto down = [&](void *dst, const void *src, size_t bytes) { if (dst) HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); };
@@ -331,13 +330,13 @@ static void chunk(kiwi_hip_ctx *c, int K, int g0, int ng, int nk, const double *
     down(o.receiver_norm, b.rnorm.p, (size_t)ng * nrec * sizeof(float));
 }
 
-// groups that have no fit (a basis source failed to discretise): status 2, NaN, -1 indices, zeros per receiver (cand_fill_failed)
+// groups that have no fit (a basis source failed to discretise): status 2, NaN, -1 indices, zeros per receiver
 static void fill_failed(size_t ngroup, size_t nk, size_t nrec, const Scan &sc)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const size_t nj = ngroup * nk, nc = ngroup * (size_t)sc.ncand, njc = nj * (size_t)sc.ncand;
     std::fill(sc.status, sc.status + ngroup, 2);
-    std::fill(sc.best_offset, sc.best_offset + ngroup, -1);
+    if (sc.best_offset) std::fill(sc.best_offset, sc.best_offset + ngroup, -1);
     std::fill(sc.best_index, sc.best_index + nj, -1);
     std::fill(sc.best_misfit, sc.best_misfit + nj, nan);
     if (sc.best_scale) std::fill(sc.best_scale, sc.best_scale + nj, nan);
@@ -356,31 +355,16 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
                 const linfit_timescan::Out &fit, const Scan &sc)
 {
     check_setup(c, K, of, fit, sc);
-    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
-        throw std::runtime_error("linear_fit_candidates_time_scan: sources " + std::to_string(isrc0) + " .. " +
-                                 std::to_string((long long)isrc0 + (long long)ngroup * K) + " are not inside the uploaded batch of " +
-                                 std::to_string(c->nsrc));
+    check_group_range("linear_fit_candidates_time_scan", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), NN = linfit::nn_of(K), nk = of.nk;
     c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
     c->global_d.ensure((size_t)c->nsrc, &c->dev_bytes);
-    const int base = c->halo, shalo = of.max_abs();
     c->fuse_now = false;                                   // the plain synthetics go to memory
-    struct Restore {
-        kiwi_hip_ctx *c; bool want; int halo;
-        ~Restore()
-        {
-            c->want_spansrc = want;
-            try { HIPCHECK(hipSetDevice(c->device)); timescan::set_halo(c, halo); }
-            catch (...) { c->prepared = false; }           // (the next call lays everything out again)
-        }
-    } restore{ c, c->want_spansrc, base };
-    c->want_spansrc = true;
-    timescan::set_halo(c, base + shalo);
+    timescan::HaloScope halo(c);
+    halo.widen(of.max_abs());
 
-    std::vector<double> w((size_t)nrec, 0.0);
-    for (int r = 0; r < nrec; r++)
-        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    const std::vector<double> w = receiver_weights(c, receiver_weight);
     DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d;
     DevBuf<int> st_d, best_d;
     Bufs bufs;
@@ -388,25 +372,12 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[6];
-    for (int i = 0; i < 6; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 6; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
-    const size_t per_group = bytes_per_group(sc, nrec, nk);
+    const PooledEvents<6> ev(c);
+    // per group: the sums by receiver and their fold at every offset, the candidate outputs
+    const size_t per_group = (size_t)nk * (nrec + 1) * NN * sizeof(double) + bytes_per_group(sc, nrec, nk);
     int g0 = 0;
     while (g0 < ngroup) {
-        // whole groups, bounded by workspace bytes the way linfit_timescan::run bounds its chunks, and by the candidate outputs
-        size_t bytes = 0;
-        int ng = 0;
-        while (g0 + ng < ngroup) {
-            size_t add = 0;
-            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
-                const size_t ncent = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += ncent * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float);
-            }
-            add += (size_t)nk * (nrec + 1) * NN * sizeof(double) + per_group;
-            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
-            bytes += add; ng++;
-        }
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 1, per_group, kNoSourceCap);
         const int s0 = isrc0 + g0 * K;
         const size_t nsolve = (size_t)ng * nk;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
@@ -434,24 +405,14 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
         HIPCHECK(hipMemcpyAsync(fit.status + o, st_d.p, nsolve * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[5], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 5; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->linfit_cand_timescan_ms[i] += t;
-        }
+        for (int i = 0; i < 5; i++) ev.add_elapsed(c->linfit_cand_timescan_ms, i, i, i + 1);
         g0 += ng;
     }
-    // what an evaluation of the range leaves behind (eval_impl): the plain evaluation of the basis sources was made on the way
-    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = 0;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
-    for (int g = 0; g < ngroup; g++) {
-        bool bad = false;
-        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
-        if (!bad) continue;
+    leave_evaluated(c, isrc0, ngroup * K, 0);              // the plain evaluation of the basis sources was made on the way
+    for_each_failed_group(c, isrc0, ngroup, K, [&](int g) {
         linfit_timescan::mark_failed((size_t)g, (size_t)K, (size_t)nk, fit);
         fill_failed(1, (size_t)nk, (size_t)nrec, sc.at((size_t)g, (size_t)nk, (size_t)nrec));
-    }
+    });
 }
 
 } // namespace linfit_candidates_timescan

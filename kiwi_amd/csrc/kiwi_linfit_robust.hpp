@@ -243,16 +243,7 @@ static void robust_launch(kiwi_hip_ctx *c, int ng, const FftPair *pairs, const d
 static void robust_launch_any(kiwi_hip_ctx *c, int K, int ng, const FftPair *pairs, const double *w_d, int anarchy, const double *nbr,
                               const Robust &rb, double *wbr, double *x, double *misfit, int *status, double *trace)
 {
-    switch (K) {
-    case 1: robust_launch<1>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 2: robust_launch<2>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 3: robust_launch<3>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 4: robust_launch<4>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 5: robust_launch<5>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 6: robust_launch<6>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    case 7: robust_launch<7>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    default: robust_launch<8>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); break;
-    }
+    by_basis(K, [&](auto k) { robust_launch<k.value>(c, ng, pairs, w_d, anarchy, nbr, rb, wbr, x, misfit, status, trace); });
 }
 
 } // namespace linfit

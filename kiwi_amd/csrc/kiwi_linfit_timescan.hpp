@@ -173,16 +173,7 @@ static void launch(kiwi_hip_ctx *c, const GramArgs &a, int ng, const double *w_d
 static void launch_any(kiwi_hip_ctx *c, int K, const GramArgs &a, int ng, const double *w_d, int anarchy, double *coef, double *misfit,
                        int *status, double *pivot, double *normal, int *best, hipEvent_t between)
 {
-    switch (K) {
-    case 1: launch<1>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 2: launch<2>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 3: launch<3>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 4: launch<4>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 5: launch<5>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 6: launch<6>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    case 7: launch<7>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    default: launch<8>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); break;
-    }
+    by_basis(K, [&](auto k) { launch<k.value>(c, a, ng, w_d, anarchy, coef, misfit, status, pivot, normal, best, between); });
 }
 
 // host arrays of the caller for the groups of ONE call of run(); pivot_min, best and normal may be null
@@ -234,58 +225,30 @@ static void check_setup(kiwi_hip_ctx *c, int K, const timescan::Offsets &of, con
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const Out &out)
 {
     check_setup(c, K, of, out);
-    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
-        throw std::runtime_error("linear_fit_time_scan: sources " + std::to_string(isrc0) + " .. " +
-                                 std::to_string((long long)isrc0 + (long long)ngroup * K) + " are not inside the uploaded batch of " +
-                                 std::to_string(c->nsrc));
+    check_group_range("linear_fit_time_scan", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), NN = linfit::nn_of(K), nk = of.nk;
     c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
     c->global_d.ensure((size_t)c->nsrc, &c->dev_bytes);
-    const int base = c->halo, shalo = of.max_abs();
     c->fuse_now = false;                                   // the plain synthetics go to memory
     // every source is synthesised (run_chunk shares no synthetics between sources then), as in timescan::run
-    struct Restore {
-        kiwi_hip_ctx *c; bool want; int halo;
-        ~Restore()
-        {
-            c->want_spansrc = want;
-            try { HIPCHECK(hipSetDevice(c->device)); timescan::set_halo(c, halo); }
-            catch (...) { c->prepared = false; }           // (the next call lays everything out again)
-        }
-    } restore{ c, c->want_spansrc, base };
-    c->want_spansrc = true;
-    timescan::set_halo(c, base + shalo);
+    timescan::HaloScope halo(c);
+    halo.widen(of.max_abs());
 
-    std::vector<double> w((size_t)nrec, 0.0);
-    for (int r = 0; r < nrec; r++)
-        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    const std::vector<double> w = receiver_weights(c, receiver_weight);
     DevBuf<double> w_d, nbr_d, coef_d, mis_d, piv_d, normal_d;
     DevBuf<int> st_d, best_d;
     w_d.alloc((size_t)nrec, &c->dev_bytes);
     HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
 
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 5; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<5> ev(c);
     std::vector<double> piv_h;
     std::vector<int> best_h;
     int g0 = 0;
     while (g0 < ngroup) {
-        // whole groups, bounded by workspace bytes the way linfit::run bounds its chunks; the sums are nk times those of a plain fit
-        size_t bytes = 0;
-        int ng = 0;
-        while (g0 + ng < ngroup) {
-            size_t add = 0;
-            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
-                const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float);
-            }
-            add += (size_t)nk * nrec * NN * sizeof(double);
-            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
-            bytes += add; ng++;
-        }
+        // per group: the sums by receiver, nk times those of a plain fit
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 1, (size_t)nk * nrec * NN * sizeof(double), kNoSourceCap);
         const int s0 = isrc0 + g0 * K;
         const size_t nsolve = (size_t)ng * nk;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
@@ -316,22 +279,11 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
         if (out.normal) HIPCHECK(hipMemcpyAsync(out.normal + o * NN, normal_d.p, nsolve * NN * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[4], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 4; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->linfit_timescan_ms[i] += t;
-        }
+        for (int i = 0; i < 4; i++) ev.add_elapsed(c->linfit_timescan_ms, i, i, i + 1);
         g0 += ng;
     }
-    // what an evaluation of the range leaves behind (eval_impl): the plain evaluation of the basis sources was made on the way
-    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = 0;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
-    for (int g = 0; g < ngroup; g++) {
-        bool bad = false;
-        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
-        if (bad) mark_failed((size_t)g, (size_t)K, (size_t)nk, out);
-    }
+    leave_evaluated(c, isrc0, ngroup * K, 0);              // the plain evaluation of the basis sources was made on the way
+    for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { mark_failed((size_t)g, (size_t)K, (size_t)nk, out); });
 }
 
 } // namespace linfit_timescan

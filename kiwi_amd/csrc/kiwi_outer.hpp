@@ -204,14 +204,7 @@ static void run(kiwi_hip_ctx *c, int nsrc, int nmis, int nrec, const int *slot_r
     bestv_d.alloc((size_t)ndraw, &c->dev_bytes); besti_d.alloc((size_t)ndraw, &c->dev_bytes);
     if (global_of_draw) g_d.alloc((size_t)chunk, &c->dev_bytes);
 
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 4; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
-    auto add_ms = [&](int what, hipEvent_t e0, hipEvent_t e1) {
-        float t = 0.f;
-        HIPCHECK(hipEventElapsedTime(&t, e0, e1));
-        c->outer_ms[what] += t;
-    };
+    const PooledEvents<4> ev(c);
     HIPCHECK(hipEventRecord(ev[0], c->stream));
     if (nrec > 0) {
         HIPCHECK(hipMemcpyAsync(w_d.p, receiver_weights, (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -223,8 +216,8 @@ static void run(kiwi_hip_ctx *c, int nsrc, int nmis, int nrec, const int *slot_r
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(ev[2], c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
-    add_ms(0, ev[0], ev[1]);
-    add_ms(1, ev[1], ev[2]);
+    ev.add_elapsed(c->outer_ms, 0, 0, 1);
+    ev.add_elapsed(c->outer_ms, 1, 1, 2);
     for (long long s0 = 0; s0 < nsrc; s0 += chunk) {
         const int ns = (int)std::min<long long>(chunk, nsrc - s0);
         const int ntiles = (ns + kTileS - 1) / kTileS;
@@ -252,16 +245,16 @@ static void run(kiwi_hip_ctx *c, int nsrc, int nmis, int nrec, const int *slot_r
             HIPCHECK(hipMemcpyAsync(global_of_draw + s0, g_d.p, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[3], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        add_ms(0, ev[0], ev[1]);
-        add_ms(1, ev[1], ev[2]);
-        add_ms(2, ev[2], ev[3]);
+        ev.add_elapsed(c->outer_ms, 0, 0, 1);
+        ev.add_elapsed(c->outer_ms, 1, 1, 2);
+        ev.add_elapsed(c->outer_ms, 2, 2, 3);
     }
     HIPCHECK(hipEventRecord(ev[0], c->stream));
     HIPCHECK(hipMemcpyAsync(best_value, bestv_d.p, (size_t)ndraw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipMemcpyAsync(best_index, besti_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(hipEventRecord(ev[1], c->stream));
     HIPCHECK(hipStreamSynchronize(c->stream));
-    add_ms(2, ev[0], ev[1]);
+    ev.add_elapsed(c->outer_ms, 2, 0, 1);
 }
 
 } // namespace outer

@@ -357,16 +357,7 @@ static void launch(kiwi_hip_ctx *c, const Args &a, bool free_scale)
 
 static void launch_any(kiwi_hip_ctx *c, int K, const Args &a, bool free_scale)
 {
-    switch (K) {
-    case 1: launch<1>(c, a, free_scale); break;
-    case 2: launch<2>(c, a, free_scale); break;
-    case 3: launch<3>(c, a, free_scale); break;
-    case 4: launch<4>(c, a, free_scale); break;
-    case 5: launch<5>(c, a, free_scale); break;
-    case 6: launch<6>(c, a, free_scale); break;
-    case 7: launch<7>(c, a, free_scale); break;
-    default: launch<8>(c, a, free_scale); break;
-    }
+    by_basis(K, [&](auto k) { launch<k.value>(c, a, free_scale); });
 }
 
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->speccand_ms: evaluation (run_chunk),
@@ -374,9 +365,7 @@ static void launch_any(kiwi_hip_ctx *c, int K, const Args &a, bool free_scale)
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Call &cl)
 {
     check_setup(c, K, cl);
-    if (isrc0 < 0 || ngroup < 0 || (long long)isrc0 + (long long)ngroup * K > (long long)c->nsrc)
-        throw std::runtime_error("spectral_candidates: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + (long long)ngroup * K) +
-                                 " are not inside the uploaded batch of " + std::to_string(c->nsrc));
+    check_group_range("spectral_candidates", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), nmis = c->nmis;
     c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
@@ -386,9 +375,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     c->fuse_now = can_fuse(c, proc_which, isrc0, ngroup * K);
     if (c->fft_cap < K) throw std::runtime_error("spectral_candidates: the transform workspace (KIWI_HIP_CHUNK_MB) does not hold one group");
 
-    std::vector<double> w((size_t)nrec, 0.0);
-    for (int r = 0; r < nrec; r++)
-        if (c->recv[r].enabled && c->recv[r].ncomp > 0) w[r] = receiver_weight ? receiver_weight[r] : 1.0;
+    const std::vector<double> w = receiver_weights(c, receiver_weight);
     std::vector<SlotInfo> info((size_t)nmis);
     for (int m = 0; m < nmis; m++)
         info[(size_t)m] = SlotInfo{ c->comps[(size_t)m].rec, (m + 1 == nmis || c->comps[(size_t)m + 1].rec != c->comps[(size_t)m].rec) ? 1 : 0,
@@ -417,9 +404,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         c->speccand_attr = true;
     }
 
-    hipEvent_t ev[6];                                      // (ev[5]: immediately in front of the spectra kernel)
-    for (int i = 0; i < 6; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 6; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<6> ev(c);                           // (ev[5]: immediately in front of the spectra kernel)
     // the kept bins of (slot, variant): from the host mirror of the filter weights, made once per variant and call
     std::map<std::pair<int, int>, std::pair<int, int>> kept;
     auto kept_range = [&](int m, int ntrans, int specofs) {
@@ -441,23 +426,12 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     };
     std::vector<SlotRec> sl;
     std::vector<float2> spec_h;
+    // per group: the spectra of the basis, the slot table, the candidate outputs
+    const size_t per_group = c->spec_cplx_per_src * K * sizeof(float2) + (size_t)nmis * sizeof(SlotRec) + ntile * (sizeof(double) + sizeof(int)) +
+                             (size_t)cl.ncand * ((cl.misfit ? sizeof(double) : 0) + (cl.scale ? sizeof(double) : 0) + (cl.slot_misfit ? (size_t)nmis * sizeof(float) : 0));
     int g0 = 0;
     while (g0 < ngroup) {
-        // whole groups, bounded by workspace bytes the way eval_impl bounds its chunks
-        size_t bytes = 0;
-        int ng = 0;
-        while (g0 + ng < ngroup) {
-            size_t add = 0;
-            for (int s = isrc0 + (g0 + ng) * K; s < isrc0 + (g0 + ng + 1) * K; s++) {
-                const size_t nc = (size_t)(c->cent_ofs[s + 1] - c->cent_ofs[s]);
-                add += nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s, (size_t)nrec) + c->syn_stride * sizeof(float) * 2;
-            }
-            add += c->spec_cplx_per_src * K * sizeof(float2) + (size_t)nmis * sizeof(SlotRec) + ntile * (sizeof(double) + sizeof(int));
-            add += (size_t)cl.ncand * ((cl.misfit ? sizeof(double) : 0) + (cl.scale ? sizeof(double) : 0) + (cl.slot_misfit ? (size_t)nmis * sizeof(float) : 0));
-            if (ng > 0 && (bytes + add > c->chunk_bytes_limit || (ng + 1) * K > 65535)) break;
-            if ((ng + 1) * K > c->fft_cap) break;
-            bytes += add; ng++;
-        }
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 2, per_group, c->fft_cap);
         const int s0 = isrc0 + g0 * K;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
         run_chunk(c, s0, ng * K, proc_which);
@@ -555,24 +529,14 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
             }
         // (the host's slot table, the twiddle tables of lengths seen for the first time and the table's upload lie between ev[1] and
         // ev[5]: in none of the four)
-        const hipEvent_t from[4] = { ev[0], ev[5], ev[2], ev[3] }, to[4] = { ev[1], ev[2], ev[3], ev[4] };
-        for (int i = 0; i < 4; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, from[i], to[i]));
-            c->speccand_ms[i] += t;
-        }
+        ev.add_elapsed(c->speccand_ms, 0, 0, 1);
+        ev.add_elapsed(c->speccand_ms, 1, 5, 2);
+        ev.add_elapsed(c->speccand_ms, 2, 2, 3);
+        ev.add_elapsed(c->speccand_ms, 3, 3, 4);
         g0 += ng;
     }
-    // what an evaluation of the range leaves behind (eval_impl)
-    c->last_isrc0 = isrc0; c->last_nsrc = ngroup * K; c->last_proc_which = proc_which;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + ngroup * K, 1);
-    // a basis source that failed to discretise: no answer for its group
-    for (int g = 0; g < ngroup; g++) {
-        bool bad = false;
-        for (int i = 0; i < K; i++) if (c->src_status[(size_t)isrc0 + (size_t)g * K + i]) bad = true;
-        if (bad) fill_failed(1, nmis, K, cl.at(g, nmis, K));
-    }
+    leave_evaluated(c, isrc0, ngroup * K, proc_which);
+    for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { fill_failed(1, nmis, K, cl.at(g, nmis, K)); });
 }
 
 } // namespace spectral_candidates

@@ -310,16 +310,34 @@ static void set_halo(kiwi_hip_ctx *c, int halo)
     HIPCHECK(hipStreamSynchronize(c->stream));
 }
 
+// for the length of a scan: the halo widened by `more` samples and every source synthesised with its own strip spans kept; both
+// are put back on the way out, also where widen() itself threw
+struct HaloScope {
+    kiwi_hip_ctx *c; bool want; int halo;
+    explicit HaloScope(kiwi_hip_ctx *ctx) : c(ctx), want(ctx->want_spansrc), halo(ctx->halo) {}
+    void widen(int more)
+    {
+        c->want_spansrc = true;
+        set_halo(c, halo + more);
+    }
+    ~HaloScope()
+    {
+        c->want_spansrc = want;
+        try { HIPCHECK(hipSetDevice(c->device)); set_halo(c, halo); }
+        catch (...) { c->prepared = false; }               // (the next call lays everything out again)
+    }
+    HaloScope(const HaloScope &) = delete;
+    HaloScope &operator=(const HaloScope &) = delete;
+};
+
 // the sources [isrc0, isrc0 + nsrc) of the uploaded batch; adds its HIP-event times to c->timescan_ms
 static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Offsets &of, const Out &out)
 {
     check_setup(c, of.k0, of.kstep, of.nk);
-    if (isrc0 < 0 || nsrc < 0 || (long long)isrc0 + nsrc > (long long)c->nsrc)
-        throw std::runtime_error("time_scan: sources " + std::to_string(isrc0) + " .. " + std::to_string((long long)isrc0 + nsrc) +
-                                 " are not inside the uploaded batch of " + std::to_string(c->nsrc));
+    check_group_range("time_scan", c, isrc0, nsrc, 1);
     if (nsrc == 0) return;
     TimeScanState &st = c->timescan_state;
-    const int nrec = (int)c->recv.size(), nmis = c->nmis, nk = of.nk;
+    const int nmis = c->nmis, nk = of.nk;
     const bool spectral = c->method == KIWI_AMPSPEC_L2NORM || c->method == KIWI_AMPSPEC_L1NORM;
     if (c->fft_needed && !c->fused_fft)
         throw std::runtime_error("time_scan: slots with a frequency filter or an amplitude-spectrum method go through the in-LDS transforms, "
@@ -342,38 +360,19 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Offsets &of, const O
                                  std::to_string(row_limit));
     c->fuse_now = false;                                   // the plain synthetics go to memory
     // every source is synthesised (run_chunk shares no synthetics between sources then), with its own strip spans kept
-    struct Restore {
-        kiwi_hip_ctx *c; bool want; int halo;
-        ~Restore()
-        {
-            c->want_spansrc = want;
-            try { HIPCHECK(hipSetDevice(c->device)); set_halo(c, halo); }
-            catch (...) { c->prepared = false; }           // (the next call lays everything out again)
-        }
-    } restore{ c, c->want_spansrc, base };
-    c->want_spansrc = true;
-    set_halo(c, base + shalo);
+    HaloScope halo(c);
+    halo.widen(shalo);
     if (!st.attr) {
         HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&time_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds));
         st.attr = true;
     }
 
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; i++) ev[i] = c->get_event();
-    struct Return { kiwi_hip_ctx *c; hipEvent_t *ev; ~Return() { for (int i = 0; i < 4; i++) c->event_pool.push_back(ev[i]); } } ret{ c, ev };
+    const PooledEvents<4> ev(c);
     int s = isrc0;
     while (s < isrc0 + nsrc) {
-        // greedy chunk bounded by workspace bytes (eval_impl), the outputs nk times those of a plain call
-        size_t bytes = 0;
-        int n = 0;
-        while (s + n < isrc0 + nsrc) {
-            const size_t nc = (size_t)(c->cent_ofs[s + n + 1] - c->cent_ofs[s + n]);
-            const size_t add = nc * nrec * (sizeof(GeoRec) + (c->accum_mode == 0 ? 512 + kCoefLine * sizeof(float) : 0)) + plan_bytes(c, s + n, (size_t)nrec) + c->syn_stride * sizeof(float) +
-                               ((size_t)nk * nmis + nmis + nk + 1) * sizeof(float);
-            if (n > 0 && (bytes + add > c->chunk_bytes_limit || n >= 65535)) break;
-            if (c->fft_needed && n >= c->fft_cap) break;
-            bytes += add; n++;
-        }
+        // a chunk of sources (groups of one), the outputs nk times those of a plain call
+        const int n = next_group_chunk(c, isrc0, s - isrc0, nsrc, 1, 1, ((size_t)nk * nmis + nmis + nk + 1) * sizeof(float),
+                                       c->fft_needed ? c->fft_cap : kNoSourceCap);
         HIPCHECK(hipEventRecord(ev[0], c->stream));
         run_chunk(c, s, n, 0);
         HIPCHECK(hipEventRecord(ev[1], c->stream));
@@ -419,17 +418,10 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Offsets &of, const O
         if (o.best) HIPCHECK(hipMemcpyAsync(o.best, st.best_d.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHECK(hipEventRecord(ev[3], c->stream));
         HIPCHECK(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < 3; i++) {
-            float t = 0.f;
-            HIPCHECK(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-            c->timescan_ms[i] += t;
-        }
+        for (int i = 0; i < 3; i++) ev.add_elapsed(c->timescan_ms, i, i, i + 1);
         s += n;
     }
-    // what an evaluation of the range leaves behind (eval_impl): the plain evaluation -- offset 0 -- was made on the way
-    c->last_isrc0 = isrc0; c->last_nsrc = nsrc; c->last_proc_which = 0;
-    c->evaluated.resize((size_t)c->nsrc, 0);
-    std::fill(c->evaluated.begin() + isrc0, c->evaluated.begin() + isrc0 + nsrc, 1);
+    leave_evaluated(c, isrc0, nsrc, 0);                    // the plain evaluation -- offset 0 -- was made on the way
 }
 
 } // namespace timescan

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Register / LDS / spill table of the accumulate kernels, per kernel family and arithmetic contract, and of the outer-misfit
 kernels (kiwi_outer.hpp), the misfit-band kernels (kiwi_bands.hpp), the time-scan kernels (kiwi_timescan.hpp), the kernels of the
-linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation (kiwi_linfit_candidates.hpp) and of the candidate
-evaluation's time scan (kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp) and
+linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation, plain and as the candidate
+evaluation's time scan (both kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp) and
 under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), from the compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands|timescan|linfit_timescan|linfit_candidates|linfit_candidates_timescan|linfit_candidates_floating|spectral_candidates]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|spectral_candidates]"""
 import json
 import os
 import re
@@ -37,11 +37,11 @@ def collect_outer():
         if m:
             cur = None
             for prefix, fam in (("_ZN5outer", "outer"), ("_ZN5bands", "bands"), ("_ZN8timescan", "timescan"),
-                                ("_ZN15linfit_timescan", "linfit_timescan"), ("_ZN6linfit", "linfit_candidates"),
+                                ("_ZN15linfit_timescan", "linfit_timescan"),
                                 ("_ZN26linfit_candidates_timescan", "linfit_candidates_timescan"),
                                 ("_ZN26linfit_candidates_floating", "linfit_candidates_floating"),
                                 ("_ZN19spectral_candidates", "spectral_candidates")):
-                if m.group(1).startswith(prefix) and (fam != "linfit_candidates" or "linfit_candidates_" in m.group(1)):
+                if m.group(1).startswith(prefix):
                     cur = {"family": fam, "arith": "exact", "mangled": m.group(1)}
                     rows.append(cur)
             continue

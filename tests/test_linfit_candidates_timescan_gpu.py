@@ -83,6 +83,78 @@ def test_one_offset_at_zero_equals_linear_fit_candidates(K, ngroup):
         p.close()
 
 
+_WIDE = {}
+
+
+def wide_scenario():
+    """one receiver more than an LDS stage of the candidate kernels, one component each; made once for the cases below"""
+    if not _WIDE:
+        S = 64
+        sc = Scenario(nrec=S + 1, comps_list=["d"] * (S + 1), true_type=6, true_params=mt_row(PLANTED))
+        sc.make_references(sc.oracle())
+        _WIDE["sc"] = sc
+    return _WIDE["sc"]
+
+
+@pytest.mark.parametrize("K", [1, 6, 8])
+def test_plain_call_and_one_offset_scan_share_their_bits_over_chunks(K, monkeypatch):
+    """kiwi_hip_linear_fit_candidates is the nk = 1 case of the scan's kernels: both calls on ONE context whose workspace bound
+    cuts 3 groups into 2 chunks or more, 65 receivers (a second LDS stage of one receiver) of which one is disabled and one has
+    the weight 0, 257 candidates (a second tile of one live lane), traces of 256 samples, a basis source of group 1 that fails to
+    discretise.  The arrays both calls make have the same bits (exact contract; fused: the module's rule)"""
+    ngroup, ncand = 3, 257
+    sc = wide_scenario()
+    monkeypatch.setenv("KIWI_HIP_CHUNK_MB", "1")              # read when the context is made
+    p = sc.product()
+    sc.apply_setup(p, False)
+    try:
+        C, S = p.linear_fit_candidates_time_scan_shape(K)
+        assert ncand == C + 1 and sc.nrec == S + 1
+        p.switch_receiver(3, False)
+        rng = np.random.default_rng(700 + K)
+        w = rng.uniform(0.5, 2.0, sc.nrec)
+        w[10] = 0.0
+        G = np.load(os.path.join(ROOT, "tests", "golden", "eikonal_vectors.npz"))
+        p.set_source_crust(G["rupture_profile"], G["origin_profile"])
+        p.set_source_constraints(np.array([[0, 0, 6500.0], [0, 0, 15500.0]], np.float32), np.array([[0, 0, -1.0], [0, 0, 1.0]], np.float32))
+        rows = np.tile(np.array([0., 0., 0., 10500., 1.0, 80., 70., 100., -50., 2500., 500., 200., 0.8] + [0.] * 6 + [1.5], np.float32),
+                       (ngroup * K, 1))
+        rows[:, 13:19] = rng.standard_normal((ngroup * K, 6)) * 1e18
+        rows[2 * K - 1, 3] = 500.0                            # "Empty rupture area": the last basis source of group 1
+        cand = rng.uniform(-2.0, 2.0, (ncand, K))
+        ok = np.array([True, False, True])
+        for norm, free in cc.MODES:
+            kw = dict(outer_norm=norm, receiver_weights=w, anarchy=True, free_scale=free)
+            what = "K=%d %s free=%s" % (K, norm, free)
+            p.kernel_ms()
+            parent = p.linear_fit_candidates_params("mt_eikonal", rows, K, cand, receiver_misfit=True, **kw)
+            chunks_plain = int(p.kernel_ms()[1][1])
+            got = p.linear_fit_candidates_time_scan_params("mt_eikonal", rows, K, cand, 0, 1, 1, **kw, **ALL)
+            chunks_scan = int(p.kernel_ms()[1][1])
+            print(what, "chunks: plain", chunks_plain, "scan", chunks_scan)
+            assert chunks_plain >= 2 and chunks_scan >= 2, what
+            assert np.array_equal(parent.status, [0, 2, 0]) and np.array_equal(got.status, parent.status), what
+            assert np.all(got.best_offset[ok] == 0) and got.best_offset[1] == -1, what
+            assert np.all(parent.best_index[ok] >= 0) and parent.best_index[1] == -1 and np.isnan(parent.best_misfit[1]), what
+            assert np.all(parent.receiver_norm[ok][:, S] > 0) and np.all(parent.receiver_misfit[..., [2, 10]] == 0), what
+            assert (parent.scale is None) == (not free) and (got.scale is None) == (not free), what
+            if common.arith() == "exact":
+                pairs = [("best_index", got.best_index[:, 0]), ("best_misfit", got.best_misfit[:, 0]), ("status", got.status),
+                         ("misfit", got.misfit[:, 0]), ("receiver_misfit", got.receiver_misfit[:, 0]), ("receiver_norm", got.receiver_norm)]
+                if free:
+                    pairs.append(("scale", got.scale[:, 0]))
+                for name, a in pairs:
+                    b = getattr(parent, name)
+                    assert a.shape == b.shape and a.dtype == b.dtype, (what, name, a.shape, b.shape, a.dtype, b.dtype)
+                    assert np.array_equal(a, b, equal_nan=a.dtype != np.int32), (what, name)
+            else:
+                fit = p.linear_fit_params("mt_eikonal", rows, K, receiver_weights=w, anarchy=True, by_receiver=True)
+                want = cc.from_parents([parent])
+                cc.assert_scan(got, want, cc.slack_of(fit.by_receiver[:, None], w, cand, want["scale"] if free else None), what)
+    finally:
+        p.close()
+
+
 # ------------------------------------------------------------------------------------------------ 2: route B
 def test_references_and_tapers_moved_the_other_way():
     """basis sources with fractional centroid times and rise times of 0, 1 and 2 s in one batch; every offset against the parent's
