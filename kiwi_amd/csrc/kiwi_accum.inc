@@ -992,7 +992,7 @@ __device__ __forceinline__ typename Set2Sel<NG>::type make_set2(f2v &a0, f2v &a1
 // ---- the apply of one centroid group as a hand-allocated assembly routine (accumulate_multi_kernel; accumulate_grouped_kernel for
 // workgroups of one source)
 #include "kiwi_apply_asm.inc"
-#include "kiwi_apply_plan_asm.inc"      // (generated at build time: Makefile, tools/gen_apply_asm.py plan)
+#include "kiwi_apply_steps_asm.inc"     // (generated at build time: Makefile, tools/gen_apply_asm.py steps)
 // Scalar loads whose only purpose is to bring 512 bytes behind p into the scalar data cache.  Nothing waits for them; the
 // register they all write must stay allocated until they have returned (the caller keeps it live across the build).
 __device__ __forceinline__ int coef_warm(const float *p)
@@ -1005,10 +1005,10 @@ __device__ __forceinline__ int coef_warm(const float *p)
 }
 #if KIWI_ARITH == 1
 #define KIWI_APPLY_ASM(NGV, KV, RV) apply_group_asm_##NGV##_k##KV##_##RV##_fused
-#define KIWI_APPLY_PLAN(NGV, KV, RV) apply_plan_asm_##NGV##_k##KV##_##RV##_fused
+#define KIWI_APPLY_PLAN(NGV, KV, RV) apply_steps_asm_##NGV##_k##KV##_##RV##_fused
 #else
 #define KIWI_APPLY_ASM(NGV, KV, RV) apply_group_asm_##NGV##_k##KV##_##RV##_exact
-#define KIWI_APPLY_PLAN(NGV, KV, RV) apply_plan_asm_##NGV##_k##KV##_##RV##_exact
+#define KIWI_APPLY_PLAN(NGV, KV, RV) apply_steps_asm_##NGV##_k##KV##_##RV##_exact
 #endif
 
 template <int NG, int T, bool FUSE, bool RUNS, bool COMPACT /* `tab` holds compact descriptors, four ints per record (geometry_kernel's off4; desc_expand), not 128-int rows */>
@@ -1678,7 +1678,8 @@ template <int NS>
 __global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict__ recs, const int *__restrict__ cent_ofs, int isrc0, int nrec,
     const RecvDev *__restrict__ recv, const int *__restrict__ off4, const int *__restrict__ pairflag, const int *__restrict__ mate,
     const int *__restrict__ mate_wider, const int *__restrict__ plan_ofs, int4 *__restrict__ plan,
-    int regular_on /* 0: no plan is marked regular (KIWI_HIP_MULTI_REGULAR=0) */, unsigned *__restrict__ count /* debug: [0] += PlanSrc written, [1] += regular ones; or null */)
+    int regular_on /* 0: no plan is marked regular (KIWI_HIP_MULTI_REGULAR=0) */, int repeat_on /* 0: no plan names repeated shifts (KIWI_HIP_MULTI_REPEAT=0) */,
+    unsigned *__restrict__ count /* debug: [0] += PlanSrc written, [1] += regular ones, [2] += ones with a repeat mask; or null */)
 {
     constexpr int TILE = 1024 / NS, LDS_TILE = TILE + kHalo;
     const int k = (int)blockIdx.x, s0 = NS * k, r = (int)(blockIdx.y * 64 + threadIdx.x);
@@ -1720,22 +1721,34 @@ __global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict
         }
         const int glen = h[0]->pad & 0xff;
         int4 *__restrict__ out = plan + pi * (kPlanStride / 16);
-        unsigned nreg = 0;
+        unsigned nreg = 0, nrep = 0;
 #pragma unroll
         for (int i = 0; i < NS; i++) {
             const int4 o = *(const int4 *)(off4 + ((size_t)(cent_ofs[isrc0 + s0 + i] - cb) * nrec + (size_t)r * nc + c) * 4);
             // regular: the test the apply routine makes at every step (`s_cmp_lg_u32 d, 4`, tools/gen_apply_asm.py), made once here
             const int e0 = smaxs[i] - h[i]->ishift;
             bool regular = regular_on != 0 && e0 >= 0 && e0 <= kPlanE0Mask;
-            for (int j = 1; j < glen && c + j < nc; j++) regular = regular && h[i][j].ishift == h[i][j - 1].ishift + 1;
+            // repeats: a group of at most five whose every step is its predecessor's shift + 1 or its predecessor's shift, bit j of the
+            // mask: record j + 1 stays (PlanSrc::head) -- a step that stays needs no tile read, lines_repeat() of tools/gen_apply_asm.py
+            bool steps01 = regular && repeat_on != 0 && glen <= 5;
+            int repeats = 0;
+            for (int j = 1; j < glen && c + j < nc; j++) {
+                const int d = h[i][j].ishift - h[i][j - 1].ishift;
+                regular = regular && d == 1;
+                steps01 = steps01 && (d == 0 || d == 1);
+                if (d == 0 && j <= 4) repeats |= 1 << (j - 1);
+            }
+            if (regular || !steps01) repeats = 0;
             nreg += regular ? 1u : 0u;
-            const int head = (h[i]->flags & 0xffff) | (regular ? (e0 << kPlanE0Shift) | kPlanRegularBit : 0) | (glen << 16) | ((shared ? 1 : 0) << 23) | ((npos - TILE) << 24);
+            nrep += repeats ? 1u : 0u;
+            const int head = (h[i]->flags & 0xffff) | (regular || repeats ? (e0 << kPlanE0Shift) | (regular ? kPlanRegularBit : 0) | (repeats << kPlanRepeatShift) : 0)
+                             | (glen << 16) | ((shared ? 1 : 0) << 23) | ((npos - TILE) << 24);
             out[4 * i + 0] = make_int4(h[i]->row[0], h[i]->row[1], h[i]->row[2], h[i]->row[3]);
             out[4 * i + 1] = o;
             out[4 * i + 2] = make_int4(__float_as_int(h[i]->w[0]), __float_as_int(h[i]->w[1]), __float_as_int(h[i]->w[2]), __float_as_int(h[i]->w[3]));
             out[4 * i + 3] = make_int4(smaxs[i], head, __float_as_int(h[i]->cl), __float_as_int(h[i]->sl));
         }
-        if (count) { atomicAdd(count, (unsigned)NS); atomicAdd(count + 1, nreg); }
+        if (count) { atomicAdd(count, (unsigned)NS); atomicAdd(count + 1, nreg); atomicAdd(count + 2, nrep); }
         if (glen < 1) break;
         c += glen;
     }
@@ -1914,9 +1927,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             flags = REC_I(curme, 18);
             gcl = REC_F(curme, 16); gsl = REC_F(curme, 17);
             }
-            // the group's integer shifts, lane k: step k -- not for a group the plan calls regular (PlanSrc::head: its apply takes e0
-            // and the step count).  Wave-uniform: the waves of a workgroup may differ.
-            if (!(PLAN && (flags & kPlanRegularBit))) { if (lane < glen) ishv = rc[c + lane].ishift; }
+            // the group's integer shifts, lane k: step k -- not for a group the plan calls regular or whose repeats it names
+            // (PlanSrc::head: its apply takes e0, the step count and those bits).  Wave-uniform: the waves of a workgroup may differ.
+            if (!(PLAN && (flags & (kPlanRegularBit | kPlanRepeatMask)))) { if (lane < glen) ishv = rc[c + lane].ishift; }
             // this group's coefficient lines (80 bytes per step, consecutive) on their way into the scalar cache
             const size_t crow = (base_me + c) * kCoefLine;
             const unsigned clo = __builtin_amdgcn_readfirstlane((unsigned)crow), chi = __builtin_amdgcn_readfirstlane((unsigned)(crow >> 32));
@@ -1994,9 +2007,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
 #define KIWI_ASM_ARGS ar1[0], ar1[1], ar2[0], ar2[1], dz[0], dz[1], abase, ishv, smax, n, coef_u, gcl_u, gsl_u
 #define KIWI_PLAN_ARGS ar1[0], ar1[1], ar2[0], ar2[1], dz[0], dz[1], abase, ishv, smax, n, coef_u, gcl_u, gsl_u, head_u
                 if constexpr (PLAN) {
-                    // regular group or not (the plan's header word, PlanSrc::head): both routines in one statement, the choice a scalar bit
-                    // test inside it (apply_plan_asm_*, tools/gen_apply_asm.py routine_plan) -- a regular group takes the routine with
-                    // neither the shifts nor a test per step (apply_regular_asm_*'s text)
+                    // regular group, group with named repeats or neither (the plan's header word, PlanSrc::head): the three texts in one
+                    // statement, the choice scalar bit tests inside it (apply_steps_asm_*, tools/gen_apply_asm.py routine_steps) -- a
+                    // regular group takes the routine with neither the shifts nor a test per step (apply_regular_asm_*'s text), one with
+                    // repeats that text with a bit test per step and no tile read for a step that stays
                     const int head_u = __builtin_amdgcn_readfirstlane(flags);
                     if constexpr (NG == 10) {
                         if (flags & 2) { if constexpr (K == 5) KIWI_APPLY_PLAN(10, 5, rot)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(10, 9, rot)(KIWI_PLAN_ARGS); }

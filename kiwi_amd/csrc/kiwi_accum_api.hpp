@@ -20,7 +20,8 @@ struct AccumArgs {
     const PlanSrc *plan = nullptr;       // accumulate_multi_kernel: the plans of THIS launch's source groups (multi_plan_kernel), or null: none
     const int *plan_ofs = nullptr;       // ... and the index of every source group's first plan (one more entry than groups)
     int plan_regular = 1;                // multi_plan_kernel: mark regular groups (PlanSrc::head); 0 (KIWI_HIP_MULTI_REGULAR=0): none
-    unsigned *plan_count = nullptr;      // ... debug: two counters the plan kernel adds to (PlanSrc written, regular ones), or null
+    int plan_repeat = 1;                 // ... and name the repeated shifts of the short groups that have some; 0 (KIWI_HIP_MULTI_REPEAT=0): none
+    unsigned *plan_count = nullptr;      // ... debug: three counters the plan kernel adds to (PlanSrc written, regular ones, ones with repeats), or null
 };
 
 #define KIWI_ACCUM_LAUNCHERS                                                                                                      \

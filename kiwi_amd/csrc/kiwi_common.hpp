@@ -126,14 +126,17 @@ struct PlanSrc {
     int   smax;       // tile origin of this source's tile set: its own largest shift, or the common one of a shared build
     int   head;       // GeoRec::flags & 0xffff | glen << 16 | shared << 23 | (npos - 1024 / NS) << 24   (glen, shared, npos: equal for all NS)
                       // Bits 4 .. 15 of the flags are zero in every plan (multi_taken() admits pairflag 0 only; geometry_kernel sets flag
-                      // bit 3 and the limit nibbles 8 .. 15 only together with pairflag bit 0), two fields of THIS source sit there:
+                      // bit 3 and the limit nibbles 8 .. 15 only together with pairflag bit 0), three fields of THIS source sit there:
                       //   bits 4 .. 10  e0 = smax - ishift of the head record: LDS position of b[j-1] of the group's first step (0 .. 63)
                       //   bit 11        regular: every record of the group behind the head has its predecessor's ishift + 1 (a group of
                       //                 one is regular) -- the apply then needs e0 and the step count only (apply_regular_asm_*)
+                      //   bits 12 .. 15 repeats, bit 11 clear: a group of at most five records, each with its predecessor's ishift + 1 or
+                      //                 its predecessor's ishift; bit 12 + j: record j + 1 has record j's.  Not zero (there is a repeat),
+                      //                 e0 as above -- the apply needs e0, the step count and these bits (lines_repeat, gen_apply_asm.py)
     float cl, sl;     // GeoRec::cl, sl
 };
 static_assert(sizeof(PlanSrc) == 64, "PlanSrc layout");
-constexpr int kPlanE0Shift = 4, kPlanE0Mask = 0x7f, kPlanRegularBit = 1 << 11;
+constexpr int kPlanE0Shift = 4, kPlanE0Mask = 0x7f, kPlanRegularBit = 1 << 11, kPlanRepeatShift = 12, kPlanRepeatMask = 0xf << kPlanRepeatShift;
 constexpr int kPlanStride = 256;   // bytes per plan
 template <int NG> __host__ __device__ constexpr int coef_wl(int a) { return 2 * a; }
 template <int NG> __host__ __device__ constexpr int coef_wr(int a) { return 2 * a + 1; }

@@ -226,7 +226,8 @@ struct kiwi_hip_ctx {
     DevBuf<int4> plan_d;              // accumulate_multi_kernel's plans of a chunk: the groups of four, then the pairs
     int multi_plan = 1;               // KIWI_HIP_MULTI_PLAN=0: accumulate_multi_kernel derives every group's parameters from the head records (A/B)
     int multi_regular = 1;            // KIWI_HIP_MULTI_REGULAR=0: no plan is marked regular, every group takes the general apply routine (A/B)
-    DevBuf<unsigned> plancount_d;     // KIWI_HIP_DEBUG: PlanSrc written / regular ones of a chunk (multi_plan_kernel)
+    int multi_repeat = 1;             // KIWI_HIP_MULTI_REPEAT=0: no plan names repeated shifts, groups that have some take the general apply routine (A/B)
+    DevBuf<unsigned> plancount_d;     // KIWI_HIP_DEBUG: PlanSrc written / regular ones / ones with named repeats of a chunk (multi_plan_kernel)
     int duo = 4;                      // accumulate_multi_kernel: up to this many consecutive sources of equal structure per workgroup
                                       // (4, 2, or 0 = off); env KIWI_HIP_DUO
     std::vector<char> single_group;
@@ -1320,19 +1321,21 @@ void run_chunk(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
                 aa4.plan = (const PlanSrc *)c->plan_d.p; aa4.plan_ofs = c->planofs_d.p;
                 aa2.plan = (const PlanSrc *)(c->plan_d.p + plan_n4 * (kPlanStride / 16)); aa2.plan_ofs = c->planofs_d.p + n4 + 1;
                 aa4.plan_regular = aa2.plan_regular = c->multi_regular;
+                aa4.plan_repeat = aa2.plan_repeat = c->multi_repeat;
                 const bool count_plans = std::getenv("KIWI_HIP_DEBUG") != nullptr;
                 if (count_plans) {
-                    c->plancount_d.ensure(2, &c->dev_bytes);
-                    HIPCHECK(hipMemsetAsync(c->plancount_d.p, 0, 2 * sizeof(unsigned), c->stream));
+                    c->plancount_d.ensure(3, &c->dev_bytes);
+                    HIPCHECK(hipMemsetAsync(c->plancount_d.p, 0, 3 * sizeof(unsigned), c->stream));
                     aa4.plan_count = aa2.plan_count = c->plancount_d.p;
                 }
                 if (any4) { if (fusedar) fused::launch_multi_plan(aa4, 4, (int)qgrid.x, m4p, nullptr, (PlanSrc *)aa4.plan); else exact::launch_multi_plan(aa4, 4, (int)qgrid.x, m4p, nullptr, (PlanSrc *)aa4.plan); }
                 if (any2) { if (fusedar) fused::launch_multi_plan(aa2, 2, (int)dgrid.x, m2p, m4p, (PlanSrc *)aa2.plan); else exact::launch_multi_plan(aa2, 2, (int)dgrid.x, m2p, m4p, (PlanSrc *)aa2.plan); }
                 if (count_plans) {
-                    unsigned cnt[2] = { 0u, 0u };
+                    unsigned cnt[3] = { 0u, 0u, 0u };
                     HIPCHECK(hipMemcpyAsync(cnt, c->plancount_d.p, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
                     HIPCHECK(hipStreamSynchronize(c->stream));
                     std::fprintf(stderr, "[kiwi_hip] multi plans: %u of a (source, centroid group, receiver), %u regular\n", cnt[0], cnt[1]);
+                    std::fprintf(stderr, "[kiwi_hip] multi plans with named repeats: %u\n", cnt[2]);
                 }
             }
             if (any4) { if (fusedar) fused::launch_multi(aa4, qgrid, 4, ntiles_q, m4p, nullptr); else exact::launch_multi(aa4, qgrid, 4, ntiles_q, m4p, nullptr); }
@@ -1590,6 +1593,7 @@ int kiwi_hip_init(int device, kiwi_hip_ctx **out)
         if (const char *m = std::getenv("KIWI_HIP_DUO")) { const int v = std::atoi(m); c->duo = v >= 4 ? 4 : (v >= 1 ? 2 : 0); }
         if (const char *m = std::getenv("KIWI_HIP_MULTI_PLAN")) c->multi_plan = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_MULTI_REGULAR")) c->multi_regular = std::atoi(m) ? 1 : 0;
+        if (const char *m = std::getenv("KIWI_HIP_MULTI_REPEAT")) c->multi_repeat = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_CELL")) c->cell_mode = std::atoi(m) ? 1 : 0;
         if (const char *m = std::getenv("KIWI_HIP_DEDUPE")) c->dedupe_enabled = std::atoi(m);      // 0 off, 1 default, 2 also for point sources
         if (const char *m = std::getenv("KIWI_HIP_FUSED_FFT")) c->fused_fft = std::atoi(m) != 0;   // 0: amplitude spectra through hipFFT

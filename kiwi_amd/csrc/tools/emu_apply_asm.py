@@ -17,7 +17,8 @@ memory model that matters here:
   reference model of the test uses the same expression).
 
 Operands %0 .. %12 of the inline-assembly statement are bound to registers outside the routine's fixed ranges (v[200:211], s[90:95]);
-the apply_regular_asm_* and apply_plan_asm_* routines take other operands (OPERANDS_REGULAR, OPERANDS_PLAN: `operands` of Machine.run)."""
+the apply_regular_asm_*, apply_plan_asm_* and apply_steps_asm_* routines take other operands (OPERANDS_REGULAR, OPERANDS_PLAN: `operands` of
+Machine.run)."""
 import re
 
 import numpy as np
@@ -32,7 +33,7 @@ class EmuError(AssertionError):
 def routines(text):
     """{name: [instruction, ...]} of every routine in the generated file"""
     out = {}
-    for m in re.finditer(r"void (apply_(?:group|regular|plan)_asm_\w+)\(.*?asm volatile\(\n(.*?)\n\s*: \"\+v\"", text, re.S):
+    for m in re.finditer(r"void (apply_(?:group|regular|plan|steps)_asm_\w+)\(.*?asm volatile\(\n(.*?)\n\s*: \"\+v\"", text, re.S):
         ins = []
         for line in m.group(2).split("\n"):
             line = line.strip()
@@ -55,7 +56,7 @@ OPERANDS_REGULAR = {"%0": "v[200:201]", "%1": "v[202:203]", "%2": "v[204:205]", 
                     "%6": "v212", "%7": "s90", "%8": "s91", "%9": "s[92:93]", "%10": "s94", "%11": "s95"}
 
 
-# apply_plan_asm_*: apply_group_asm_*'s, then %13 the plan's header word
+# apply_plan_asm_* and apply_steps_asm_*: apply_group_asm_*'s, then %13 the plan's header word
 OPERANDS_PLAN = dict(OPERANDS, **{"%13": "s96"})
 
 
@@ -153,8 +154,8 @@ class Machine:
             if op == "s_branch":
                 pc = labels[args[0]]
                 continue
-            if op == "s_cbranch_scc1":
-                if self.scc:
+            if op in ("s_cbranch_scc1", "s_cbranch_scc0"):
+                if self.scc == int(op.endswith("1")):
                     pc = labels[args[0]]
                 continue
             if op == "s_mov_b32":
@@ -182,8 +183,13 @@ class Machine:
                     r = a << (b & 31)
                 self.s[int(args[0][1:])] = r & 0xffffffff
                 continue
-            if op == "s_bitcmp0_b32":
-                self.scc = int(((int(self.src32(args[0], ins)[0]) >> (int(self.src32(args[1], ins)[0]) & 31)) & 1) == 0)
+            if op in ("s_bitcmp0_b32", "s_bitcmp1_b32"):     # (the bit's number: an immediate or a register, bits 0 .. 4 of it)
+                self.scc = int(((int(self.src32(args[0], ins)[0]) >> (int(self.src32(args[1], ins)[0]) & 31)) & 1) == int(op[8]))
+                continue
+            if op == "s_and_b32":
+                r = int(self.src32(args[1], ins)[0]) & int(self.src32(args[2], ins)[0])
+                self.s[int(args[0][1:])] = r
+                self.scc = int(r != 0)
                 continue
             if op == "s_bfe_u32":                          # (offset in bits 0 .. 4 of the second source, width in bits 16 .. 22)
                 a, b = int(self.src32(args[1], ins)[0]), int(self.src32(args[2], ins)[0])

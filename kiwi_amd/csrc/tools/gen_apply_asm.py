@@ -25,10 +25,15 @@ Registers (kernel budget: 168 VGPRs at three waves per SIMD):
   s80 k  s81, s82 4 x integer shift of this step / the next (swapping)  s83 tmp  s84 4 d  s[86:87] coefficient pointer
   v44 address of position smax  v45 4 x shifts (lane k: step k)  v46, v47 addresses of the next reads
 
-Two more families (python tools/gen_apply_asm.py regular | plan; not committed: the Makefile writes the plan family into
-build/kiwi_apply_plan_asm.inc, the tests call the generator): apply_regular_asm_* serves the groups whose shifts grow by one per step (routine_regular()), and
-apply_plan_asm_*, what accumulate_multi_kernel calls where it has plans, holds that text and the general routine's in one statement
-(routine_plan()).
+Three more families (python tools/gen_apply_asm.py regular | plan | steps; not committed: the Makefile writes the steps family into
+build/kiwi_apply_steps_asm.inc, the tests call the generator): apply_regular_asm_* serves the groups whose shifts grow by one per step
+(routine_regular()); apply_plan_asm_* holds that text and the general routine's in one statement (routine_plan(): what
+accumulate_multi_kernel called where it has plans until the plans named repeated shifts; kept as it is, tests/
+test_apply_regular_asm_emulated.py pins its instruction counts); apply_steps_asm_*, what the kernel calls there now, holds a third text
+beside the two, for groups of at most five steps whose shifts grow by one or stay (lines_repeat(), routine_steps()): a step whose
+successor has its shift reads no tile -- both banks are the successor's as they stand -- and copies the successor's coefficient line into
+the buffer at hand, so that banks and buffers keep their parity and the same step text runs again.  s84: the plan's repeat bits, s82:
+number of the successor's bit.  `steps-one-text` prints the A/B variant in which regular groups take that third text too.
 """
 import os
 import sys
@@ -275,10 +280,8 @@ def routine_regular(ng, K, rot, fused):
     return wrap_regular(name, L)
 
 
-def lines_regular(ng, K, rot, fused, op, end, jump_end):
-    """op: the statement's operands by name (e0, or head: the plan's header word, which holds it); end: the label behind the routine,
-    jump_end: it does not follow the text"""
-    acc = ["%0", "%1", "%2", "%3", "%4", "%5"]
+def prologue_regular(ng, K, op):
+    """what lines_regular() and lines_repeat() do in front of their steps: rotation, the first coefficient line, the counters, both banks"""
     L = []
     a = L.append
     a("s_mov_b32 s%d, %s" % (CLSL, op["cl"]))
@@ -298,6 +301,15 @@ def lines_regular(ng, K, rot, fused, op, end, jump_end):
     a("v_add_u32 v%d, 4, v%d" % (VN4, VN))
     L += reads(0, ng, K, VN4)            # bank 0 = b[j]
     L += reads(1, ng, K, VN)             # bank 1 = b[j-1]
+    return L
+
+
+def lines_regular(ng, K, rot, fused, op, end, jump_end):
+    """op: the statement's operands by name (e0, or head: the plan's header word, which holds it); end: the label behind the routine,
+    jump_end: it does not follow the text"""
+    acc = ["%0", "%1", "%2", "%3", "%4", "%5"]
+    L = prologue_regular(ng, K, op)
+    a = L.append
     tail = []                            # the last step: out of line
     for r in range(2):
         H, Lb = r, 1 - r
@@ -352,13 +364,94 @@ def routine_plan(ng, K, rot, fused):
     return wrap_general(name, L, head=True)
 
 
+REPEAT_BIT0 = 12                          # PlanSrc::head: bit 12 + j is set if record j + 1 of the group has record j's integer shift
+
+
+def lines_repeat(ng, K, rot, fused, op, last, have_mask):
+    """The apply of a group whose shifts grow by one OR STAY from step to step (bits 12 .. 15 of the plan's header word name the steps
+    that stay: at most five steps).  routine_regular()'s text with a scalar test of the successor's bit in every step that has one:
+      successor one sample on: the regular step -- its b[j-1] read behind this step's multiplies into the b[j] bank, the banks and the
+        coefficient buffers swap (the other step text follows);
+      successor at the SAME shift: its b[j] and b[j-1] are the two banks as they stand, so nothing is read.  The arithmetic runs without
+        read-behind, the successor's coefficient line -- loaded into the other buffer at the top of this step -- is copied into the
+        buffer at hand behind a wait, and the SAME step text runs again: banks, roles and buffers keep their parity.
+    last: labels of the last-step bodies by parity (lines_regular()'s: a last step reads nothing ahead, whatever the group).
+    have_mask: s84 holds the four bits already (the test at the statement's top).
+    Registers as routine_regular()'s, and s84: the four bits (bit j: step j + 1 stays), s82: number of the successor's bit in them."""
+    acc = ["%0", "%1", "%2", "%3", "%4", "%5"]
+    L = prologue_regular(ng, K, op)
+    a = L.append
+    if not have_mask:
+        a("s_bfe_u32 s%d, %s, 0x%x" % (SD, op["head"], 0x40000 | REPEAT_BIT0))
+    a("s_mov_b32 s%d, -1" % SEN)
+    tail = []                            # the steps whose successor repeats the shift: out of line, the regular path falls through
+    for r in range(2):
+        H, Lb = r, 1 - r
+        Cc, Cn = (CA, CB) if r == 0 else (CB, CA)
+        a(".Lkiwi_pstep%d_%%=:" % r)
+        a("s_waitcnt lgkmcnt(0)")
+        a("s_sub_u32 s%d, s%d, 1" % (SK, SK))          # (the borrow: this is the last step)
+        a("s_cbranch_scc1 %s" % last[r])
+        a("s_add_u32 s%d, s%d, %d" % (SK1, SK1, 80))
+        a("s_load_dwordx16 s[%d:%d], %s, s%d" % (Cn, Cn + 15, sp(SCP), SK1))
+        if ng == 10:
+            a("s_load_dwordx4 s[%d:%d], %s, s%d offset:0x40" % (Cn + 16, Cn + 19, sp(SCP), SK1))
+        a("s_add_u32 s%d, s%d, 1" % (SEN, SEN))
+        a("s_bitcmp1_b32 s%d, s%d" % (SD, SEN))
+        a("s_cbranch_scc1 .Lkiwi_prep%d_%%=" % r)
+        a("v_add_u32 v%d, -4, v%d" % (VN, VN))
+        L += arithmetic(ng, rot, fused, H, Lb, acc, K, True, C=Cc)
+        if r == 1:
+            a("s_branch .Lkiwi_pstep0_%=")
+        t = tail.append
+        t(".Lkiwi_prep%d_%%=:" % r)
+        tail += arithmetic(ng, rot, fused, H, Lb, acc, C=Cc)
+        t("s_waitcnt lgkmcnt(0)")                      # (the successor's coefficient line; no LDS read is in flight)
+        for i in range(ng):
+            t("s_mov_b64 %s, %s" % (sp(Cc + 2 * i), sp(Cn + 2 * i)))
+        t("s_branch .Lkiwi_pstep%d_%%=" % r)
+    return L + tail
+
+
+def routine_steps(ng, K, rot, fused, one_text=False):
+    """What accumulate_multi_kernel calls where it has plans, since the plans name the steps that repeat a shift: one statement, a
+    three-way choice on the plan's header word at its top --
+      bit 11 set                 lines_regular()'s text, as in routine_plan();
+      a bit of 12 .. 15 set      lines_repeat()'s;
+      neither                    lines_general()'s.
+    one_text (A/B: `steps-one-text`, STEPS=steps-one-text of the Makefile): regular groups take lines_repeat()'s text too -- a mask of zero --, a test per
+    step dearer, the statement four step bodies shorter.
+    Operands: routine_plan()'s."""
+    name = "apply_steps_asm_%d_k%d_%s_%s" % (ng, K, "rot" if rot else "plain", "fused" if fused else "exact")
+    op = {"abase": "%6", "head": "%13", "n": "%9", "coef": "%10", "cl": "%11", "sl": "%12"}
+    if one_text:
+        L = ["s_and_b32 s%d, %%13, 0x%x" % (ST, (1 << 11) | (0xf << REPEAT_BIT0)), "s_cbranch_scc0 .Lkiwi_general_%="]
+        L += lines_repeat(ng, K, rot, fused, op, [".Lkiwi_plast0_%=", ".Lkiwi_plast1_%="], False)
+        for r in range(2):
+            L.append(".Lkiwi_plast%d_%%=:" % r)
+            L += arithmetic(ng, rot, fused, r, 1 - r, ["%0", "%1", "%2", "%3", "%4", "%5"], C=(CA, CB)[r])
+            L.append("s_branch .Lkiwi_end_%=")
+    else:
+        L = ["s_bitcmp0_b32 %%13, %d" % 11, "s_cbranch_scc1 .Lkiwi_notregular_%="]
+        L += lines_regular(ng, K, rot, fused, op, ".Lkiwi_end_%=", True)
+        L.append(".Lkiwi_notregular_%=:")
+        L += ["s_bfe_u32 s%d, %%13, 0x%x" % (SD, 0x40000 | REPEAT_BIT0), "s_cbranch_scc0 .Lkiwi_general_%="]       # (SCC: the field is not zero)
+        L += lines_repeat(ng, K, rot, fused, op, [".Lkiwi_rlast0_%=", ".Lkiwi_rlast1_%="], True)
+    L.append(".Lkiwi_general_%=:")
+    L += lines_general(ng, K, rot, fused)          # (ends in its label .Lkiwi_end)
+    return wrap_general(name, L, head=True)
+
+
 if __name__ == "__main__":
-    # no argument: kiwi_apply_asm.inc, the general routines.  `regular` / `plan`: the routines of accumulate_multi_kernel's plans (K = 17 is
-    # the grouped kernel's: no plan) -- `plan` is what the Makefile writes into build/kiwi_apply_plan_asm.inc
+    # no argument: kiwi_apply_asm.inc, the general routines.  `regular` / `plan` / `steps`: the routines of accumulate_multi_kernel's plans
+    # (K = 17 is the grouped kernel's: no plan) -- `steps` is what the Makefile writes into build/kiwi_apply_steps_asm.inc
     family = sys.argv[1] if len(sys.argv) > 1 else "general"
-    assert family in ("general", "regular", "plan")
+    assert family in ("general", "regular", "plan", "steps", "steps-one-text")
+    one_text = family == "steps-one-text"                 # (A/B: regular and repeating groups from one text, routine_steps)
+    family = "steps" if one_text else family
     what = {"general": "the apply of one centroid group", "regular": "the apply of one REGULAR centroid group (shifts one apart: routine_regular)",
-            "plan": "the apply of one centroid group, regular or not by the plan's header word (routine_plan)"}[family]
+            "plan": "the apply of one centroid group, regular or not by the plan's header word (routine_plan)",
+            "steps": "the apply of one centroid group: regular, with repeated shifts or general by the plan's header word (routine_steps)"}[family]
     print("// ---- (generated text: tools/gen_apply_asm.py%s) %s as a hand-allocated assembly routine" % ("" if family == "general" else " " + family, what))
     print("// KIWI_ARITH selects the exact (v_pk_mul_f32 + v_pk_add_f32) or the fused (v_pk_fma_f32) text")
     for fused in (False, True):
@@ -366,6 +459,7 @@ if __name__ == "__main__":
         for ng in (10, 8):
             for K in (5, 9, 17) if family == "general" else (5, 9):
                 for rot in (True, False):
-                    print({"general": routine, "regular": routine_regular, "plan": routine_plan}[family](ng, K, rot, fused))
+                    print({"general": routine, "regular": routine_regular, "plan": routine_plan,
+                           "steps": lambda *a: routine_steps(*a, one_text=one_text)}[family](ng, K, rot, fused))
         print("#endif")
     print("// ---- (end of generated text)")

@@ -5,7 +5,8 @@ linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation, 
 evaluation's time scan (both kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp) and
 under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), from the compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--only=bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|spectral_candidates]"""
+--text adds the kernels' text sizes in bytes (accumulate families: `make co`, the symbol sizes of the device code object).
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|spectral_candidates]"""
 import json
 import os
 import re
@@ -54,10 +55,20 @@ def collect_outer():
     return rows
 
 
-def collect(only=None):
+def text_sizes(fam, ar):
+    """{mangled kernel name: bytes of text} of one accumulate family and contract"""
+    subprocess.run(["make", "-s", "-C", CSRC, "co", "FAMILY=%d" % fam, "ARITH=%s" % ar], capture_output=True, text=True, check=True)
+    readelf = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf")
+    out = subprocess.run([readelf, "-s", "-W", os.path.join(CSRC, "build", "accum_%d_%s.co" % (fam, ar))], capture_output=True, text=True, check=True).stdout
+    return {f[7]: int(f[2]) for f in (line.split() for line in out.split("\n")) if len(f) == 8 and f[3] == "FUNC"}
+
+
+def collect(only=None, text=False):
     rows = []
-    for fam in ([] if only else FAMILIES):
+    accum = [f for f, n in FAMILIES.items() if n == only] if only in FAMILIES.values() else ([] if only else FAMILIES)
+    for fam in accum:
         for ar in ("exact", "fused"):
+            sizes = text_sizes(fam, ar) if text else {}
             r = subprocess.run(["make", "-s", "-C", CSRC, "asm", "FAMILY=%d" % fam, "ARITH=%s" % ar], capture_output=True, text=True)
             txt = r.stderr + r.stdout
             cur = None
@@ -65,6 +76,8 @@ def collect(only=None):
                 m = re.search(r"Function Name: (\S+)", line)
                 if m:
                     cur = {"family": FAMILIES[fam], "arith": ar, "mangled": m.group(1)}
+                    if m.group(1) in sizes:
+                        cur["text"] = sizes[m.group(1)]
                     rows.append(cur)
                     continue
                 if cur is None:
@@ -76,7 +89,8 @@ def collect(only=None):
                     m = re.search(pat, line)
                     if m:
                         cur[key] = int(m.group(1))
-    rows += [r for r in collect_outer() if not only or r["family"] == only]
+    if only not in FAMILIES.values():
+        rows += [r for r in collect_outer() if not only or r["family"] == only]
     names = demangle([r["mangled"] for r in rows])
     for r, n in zip(rows, names):
         r["kernel"] = n
@@ -86,13 +100,14 @@ def collect(only=None):
 
 def main():
     only = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--only=")]
-    rows = collect(only[0] if only else None)
-    print("| kernel | contract | VGPR | AGPR | SGPR | VGPR spills | SGPR spills | scratch B/lane | LDS B | waves/SIMD |")
-    print("|---|---|---|---|---|---|---|---|---|---|")
+    text = "--text" in sys.argv
+    rows = collect(only[0] if only else None, text)
+    print("| kernel | contract | VGPR | AGPR | SGPR | VGPR spills | SGPR spills | scratch B/lane | LDS B | waves/SIMD |%s" % (" text B |" if text else ""))
+    print("|---|---|---|---|---|---|---|---|---|---|%s" % ("---|" if text else ""))
     for r in rows:
-        print("| `%s` | %s | %d | %d | %d | %d | %d | %d | %d | %d |" % (r["kernel"], r["arith"], r.get("vgpr", -1), r.get("agpr", 0), r.get("sgpr", -1),
-                                                                       r.get("vgpr_spill", 0), r.get("sgpr_spill", 0), r.get("scratch", 0),
-                                                                       r.get("lds", 0), r.get("occupancy", -1)))
+        print("| `%s` | %s | %d | %d | %d | %d | %d | %d | %d | %d |%s" % (r["kernel"], r["arith"], r.get("vgpr", -1), r.get("agpr", 0), r.get("sgpr", -1),
+                                                                         r.get("vgpr_spill", 0), r.get("sgpr_spill", 0), r.get("scratch", 0),
+                                                                         r.get("lds", 0), r.get("occupancy", -1), (" %d |" % r.get("text", -1)) if text else ""))
     if "--json" in sys.argv:
         json.dump(rows, open(sys.argv[sys.argv.index("--json") + 1], "w"), indent=1)
 
