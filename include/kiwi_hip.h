@@ -669,6 +669,59 @@ int kiwi_hip_get_linear_fit_candidates_time_scan_ms(kiwi_hip_ctx *ctx, float ms[
 /* how the candidate-scan kernel walks its work: *candidates_per_workgroup (one per lane), *receivers_per_stage rows of sums per LDS
  * stage; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage);
+/* ---- the JOINT BOOTSTRAP of a candidate search over group (location), origin time and candidate (mechanism) on the device
+ * (kiwi_amd/csrc/kiwi_linfit_candidates_bootstrap.hpp): the [candidate][receiver] matrix is never written.  Nothing new is defined.
+ * Groups, K (1 .. 8), candidates [ncand][K], receiver_weight and anarchy are kiwi_hip_linear_fit_candidates'; the offsets
+ * k0 + j kstep, j < nk, are kiwi_hip_time_scan's (nk = 1 with k0 = 0 is the plain case); draw_weights [ndraw][nrec] and outer_norm
+ * are kiwi_hip_outer_misfits'.  The context's method must be l2norm.  There is no free_scale: a scale fitted on all receivers and
+ * then held over the draws is not a bootstrap of anything.
+ * The equality that defines every output: call kiwi_hip_linear_fit_candidates_time_scan on the same context with the same
+ * arguments, free_scale = 0, receiver_misfit and receiver_norm requested; read receiver_misfit [ngroup][nk][ncand][nrec] as
+ * nsrc = ngroup nk ncand sources of nmis = nrec slots with slot_receiver = 0 .. nrec - 1, the norm row of group g repeated for each
+ * of its sources; call kiwi_hip_outer_misfits with the same outer_norm, receiver_weight, anarchy and draw_weights.  Then
+ *   best_value  [ndraw]    is that call's best_value[d], bit for bit
+ *   best_group, best_offset, best_cand [ndraw]   are its best_index[d] taken apart as (g nk + j) ncand + c.  A draw with every source
+ *                          excluded answers NaN and -1, -1, -1 (kiwi_hip_outer_misfits writes index 0 there: the one deliberate
+ *                          difference)
+ *   group_value, group_offset, group_cand [ngroup][ndraw], all three or all NULL: the same per group -- kiwi_hip_outer_misfits on
+ *                          group g's nk ncand sources alone: the best mechanism and time of every location in every draw, the depth
+ *                          profile under resampling
+ *   status      [ngroup]   the candidate call's 0 / 1 / 2; groups with status 1 or 2 have zero norms and are excluded from every draw
+ * Operation by operation: m_r is the candidate call's receiver misfit (linfit::quad on the row of sums, val = (R - 2 x.b) + x.G.x
+ * clamped at 0, the root, ROUNDED TO FLOAT), n_r = (float) sqrt(R_r), both 0 for a receiver that is disabled, has weight 0 or has
+ * R_r <= 0; then kiwi_hip_outer_misfits' prepare step with one slot per receiver (under l2norm sqrt(m m), which is m for a float;
+ * the receiver weight, under anarchy w / N clipped at zero with N the float n_r widened; a = M rw, b = N rw, both squared under
+ * l2norm) and its draw sums ms = ms + a c, ns = ns + b c, receivers ascending from zero, every product and sum rounded on its own;
+ * g = ms / ns, the root under l2norm; excluded where ns <= 0, g < 0 or g is NaN.  Order of "best": excluded last, then the value,
+ * then the lowest (g, j, c).  This order is total, so nothing depends on tiles, draw passes, chunks (KIWI_HIP_CHUNK_MB), isrc0,
+ * piece or the number of devices.
+ * A consequence: a draw of all ones is NOT bit for bit kiwi_hip_linear_fit_candidates' misfit under anarchy, because n_r passes
+ * through float here, as it does on the host route.  It is bit for bit the host route, and the host route is the contract.  Put a
+ * row of ones in as draw 0 to get the plain winner from the same call.
+ * Refused with a message that starts with "linear_fit_candidates_bootstrap:", nothing approximated: everything
+ * kiwi_hip_linear_fit_candidates_time_scan refuses; ndraw < 1; null draw_weights, best_* or status; a draw_weights or
+ * receiver_weight entry that is not finite; more receivers than max_receivers of the shape call (a candidate's misfits of all
+ * receivers stay in LDS); only some of the three group_* arrays.  Afterwards the context is what
+ * kiwi_hip_linear_fit_candidates_time_scan leaves: the halo put back, the basis sources evaluated plain. */
+int kiwi_hip_linear_fit_candidates_bootstrap(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                             const double *candidates, int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                             const double *draw_weights, double *best_value, int *best_group, int *best_offset,
+                                             int *best_cand, int *status, double *group_value, int *group_offset, int *group_cand);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it; the per-draw bests of pieces and devices are combined on the host in the same total order,
+ * with the group index of the whole list */
+int kiwi_hip_linear_fit_candidates_bootstrap_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                    int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                    const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                                    double *best_value, int *best_group, int *best_offset, int *best_cand, int *status,
+                                                    double *group_value, int *group_offset, int *group_cand);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram-scan kernel, ms[2] solve kernels,
+ * ms[3] bootstrap kernels, ms[4] downloads */
+int kiwi_hip_get_linear_fit_candidates_bootstrap_ms(kiwi_hip_ctx *ctx, float ms[5]);
+/* how the bootstrap kernel walks its work: *candidates_per_workgroup (one per lane), *draws_per_tile weight rows per LDS tile,
+ * *max_receivers the most receivers its LDS layout holds (the same for every K); answers without a device.  Non-zero for K outside
+ * 1 .. kiwi_hip_linear_fit_max_basis() or a null pointer */
+int kiwi_hip_linear_fit_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers);
 /* ---- the candidate evaluation with PER-RECEIVER TIME SHIFTS (kiwi_amd/csrc/kiwi_linfit_candidates_floating.hpp): the context's
  * misfit method must be floating_l2norm (receiver.f90:439-510): every receiver slides its reference data under the fixed taper by the
  * whole samples of its own range (kiwi_hip_set_floating_shiftrange: fl_lo .. fl_lo + fl_ns - 1), and per candidate the shift with the

@@ -285,6 +285,8 @@ struct kiwi_hip_ctx {
         DevBuf<int> tile_i, best_index, status, slots, info;
     } speccand_bufs;
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
+    unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
+    float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
@@ -1541,6 +1543,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
 #include "kiwi_linfit_candidates_timescan.hpp"
+#include "kiwi_linfit_candidates_bootstrap.hpp"
 #include "kiwi_spectral_candidates.hpp"
 
 // ================================================================================================
@@ -2919,12 +2922,15 @@ struct CandFloatCall { int K; const double *weight; int anarchy; linfit_candidat
 // (kiwi_hip_spectral_candidates_params the same with `speccand` set: groups of K basis sources as for `fit`, a piece is evaluated by
 // spectral_candidates::run)
 struct SpecCandCall { int K; const double *weight; int anarchy; spectral_candidates::Call call; };
+// (kiwi_hip_linear_fit_candidates_bootstrap_params the same with `candboot` set: groups of K basis sources as for `fit`, a piece is
+// evaluated by linfit_candidates_bootstrap::run, which folds its per-draw bests into those of the call)
+struct CandBootCall { int K; const double *weight; int anarchy; linfit_candidates_bootstrap::Boot boot; timescan::Offsets of; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
                            const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
-                           const SpecCandCall *speccand = nullptr)
+                           const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2939,8 +2945,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (candscan) linfit_candidates_timescan::check_setup(c, candscan->K, candscan->of, candscan->out, candscan->scan);
     if (candfloat) linfit_candidates_floating::check_setup(c, candfloat->K, candfloat->fl);
     if (speccand) spectral_candidates::check_setup(c, speccand->K, speccand->call);
+    if (candboot) linfit_candidates_bootstrap::check_setup(c, candboot->K, candboot->of, candboot->weight, candboot->boot);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2979,18 +2986,21 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool speccanding = speccand != nullptr;
             SpecCandCall mine_speccand{};
             if (speccanding) { mine_speccand = *speccand; mine_speccand.call = speccand->call.at(s0 / unit, (int)nmis, unit); }
+            const bool candbooting = candboot != nullptr;
+            CandBootCall mine_candboot{};
+            if (candbooting) { mine_candboot = *candboot; mine_candboot.boot = candboot->boot.at((size_t)(s0 / unit)); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
                                        candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
-                                       speccanding ? &mine_speccand : nullptr);
+                                       speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3132,6 +3142,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             }
             if (candfloat) linfit_candidates_floating::fill_failed(n / unit, nrec_all, candfloat->fl.at(s0 / unit, nrec_all));
             if (speccand) spectral_candidates::fill_failed(n / unit, (int)nmis, unit, speccand->call.at(s0 / unit, (int)nmis, unit));
+            if (candboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), candboot->boot.at((size_t)(s0 / unit)));
             continue;
         }
         upload_batch(c, hb);
@@ -3151,6 +3162,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             linfit_candidates_floating::run(c, 0, n / unit, unit, candfloat->weight, candfloat->anarchy, candfloat->fl.at(s0 / unit, nrec_all));
         else if (speccand)
             spectral_candidates::run(c, 0, n / unit, unit, speccand->weight, speccand->anarchy, speccand->call.at(s0 / unit, (int)nmis, unit));
+        else if (candboot)
+            linfit_candidates_bootstrap::run(c, 0, n / unit, unit, candboot->of, candboot->weight, candboot->anarchy, candboot->boot.at((size_t)(s0 / unit)));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3647,6 +3660,69 @@ int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_wo
     if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !receivers_per_stage) return 1;
     *candidates_per_workgroup = linfit_candidates_timescan::kCandThreads;
     *receivers_per_stage = linfit_candidates_timescan::kCandStage;
+    return 0;
+}
+
+// The joint bootstrap of a candidate search over group, origin time and candidate (kiwi_linfit_candidates_bootstrap.hpp)
+static const char *const kCandBootBasis = "linear_fit_candidates_bootstrap: K = ";
+
+int kiwi_hip_linear_fit_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                             const double *candidates, int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                             const double *draw_weights, double *best_value, int *best_group, int *best_offset,
+                                             int *best_cand, int *status, double *group_value, int *group_offset, int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->linfit_cand_boot_ms) t = 0.f;
+    if (K < 1 || K > linfit::kMaxBasis)
+        throw std::runtime_error(kCandBootBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
+                                                status, group_value, group_offset, group_cand, 0, nullptr };
+    const timescan::Offsets of{ k0, kstep, nk };
+    linfit_candidates_bootstrap::check_setup(c, K, of, receiver_weight, bt);
+    bt.begin();
+    linfit_candidates_bootstrap::run(c, isrc0, ngroup, K, of, receiver_weight, anarchy, bt);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                    int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                    const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                                    double *best_value, int *best_group, int *best_offset, int *best_cand, int *status,
+                                                    double *group_value, int *group_offset, int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > linfit::kMaxBasis)
+        return fail(c, kCandBootBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "linear_fit_candidates_bootstrap: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->linfit_cand_boot_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_boot_ms) t = 0.f;
+    std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
+    const CandBootCall candboot{ K, receiver_weight, anarchy,
+                                 linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group,
+                                                                    best_offset, best_cand, status, group_value, group_offset, group_cand, 0, &mu },
+                                 timescan::Offsets{ k0, kstep, nk } };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) candboot.boot.begin();      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, &candboot);
+}
+
+int kiwi_hip_get_linear_fit_candidates_bootstrap_ms(kiwi_hip_ctx *c, float ms[5])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 5; i++) ms[i] = c->linfit_cand_boot_ms[i];
+    return 0;
+}
+
+int kiwi_hip_linear_fit_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
+    *candidates_per_workgroup = linfit_candidates_bootstrap::kCandThreads;
+    *draws_per_tile = linfit_candidates_bootstrap::kTileD;
+    *max_receivers = linfit_candidates_bootstrap::kMaxRec;
     return 0;
 }
 
