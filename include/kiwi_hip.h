@@ -820,6 +820,45 @@ int kiwi_hip_get_spectral_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
  * candidate kernel; ctx may be NULL, the call then answers without a device (*spectra_bins 0).  With a context *spectra_bins is the
  * row length of its spectra arrays (spectra_bins may be NULL).  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_spectral_candidates_shape(kiwi_hip_ctx *ctx, int K, int *candidates_per_workgroup, int *bins_per_stage, int *spectra_bins);
+/* The misfits of many GIVEN coefficient vectors per group under the time-domain norms (kiwi_waveform_candidates.hpp): the mechanism
+ * grid of a location from its six syntheses under l1norm (2) inside -- the robust norm, which is not quadratic in the coefficients
+ * and so has no Gram route -- and, from the residual itself, under l2norm (1).  The waveform is linear in the coefficients:
+ * v[t] = sum_a x_a s_a[t], s_a the kept traces of the K basis sources, so a candidate costs K multiply-adds and one |.| per window
+ * sample and no synthesis.  Groups, K, receiver_weight, anarchy and candidates [ncand][K] are kiwi_hip_linear_fit_candidates'; the
+ * kernels use (float) x.  A misfit filter on a receiver is allowed: the kept rows and the reference side are then the filtered
+ * ones, selected as kiwi_hip_linear_fit selects them.  Per slot (enabled receiver component):
+ *   per sample, ascending  v = xf_0 s_0[i]; v = v + xf_a s_a[i], every product and sum rounded in fp32; d = ref - v (synthetics
+ *                          factor as the comparator applies it); one fp64 accumulator: d^2 | |d|
+ *   slot misfit            (float) sqrt(dt acc) | (float) (dt acc); the slot norm factor is that of the group's first source
+ *   outer fold             make_global_misfits per SLOT with outer_norm 1 (l1norm) or 2 (l2norm), receiver weights and anarchy: the
+ *                          expression sequence of kiwi_hip_outer_misfits for one draw of weights 1
+ *   best_index, best_misfit [ngroup]   NaN passed over, then the value, then the lowest index; -1, NaN if none
+ *   status [ngroup]        0 evaluated; 1 no receiver counts; 2 a basis source of the group failed to discretise
+ *   misfit                 [ngroup][ncand] or NULL
+ *   slot_misfit  float [ngroup][ncand][nmis], slot_norm  float [ngroup][nmis], both or neither: the pair kiwi_hip_outer_misfits takes
+ * A unit candidate returns its basis source's own slot misfits up to the order of the fp64 sum.  There is no free scale: under
+ * l1norm the best scale of a direction has no closed form; the moment axis is more candidates.  The answer does not depend on
+ * tiling, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.  Afterwards the context is what kiwi_hip_eval of the
+ * basis sources leaves.  Refused with a message that starts with "waveform_candidates:", nothing approximated: a method other than 1
+ * or 2 (floating_l2norm goes through kiwi_hip_linear_fit_candidates_floating, the ampspec norms through
+ * kiwi_hip_spectral_candidates); an enabled receiver without a misfit taper or without references; K outside 1 .. 8; a range outside
+ * the batch; a transform workspace that does not hold one group; ncand < 1; a candidate that is not finite; a bad outer_norm;
+ * slot_misfit without slot_norm or the reverse; null mandatory arrays. */
+int kiwi_hip_waveform_candidates(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                 const double *receiver_weight, int anarchy, int *best_index, double *best_misfit, int *status,
+                                 double *misfit, float *slot_misfit, float *slot_norm);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_waveform_candidates_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece, int ncand,
+                                        const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                        int *best_index, double *best_misfit, int *status, double *misfit, float *slot_misfit,
+                                        float *slot_norm);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the slot kernel, ms[2] the fold kernels,
+ * ms[3] downloads.  The host's tables of a chunk and their upload lie between ms[0] and ms[1], in neither */
+int kiwi_hip_get_waveform_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the kernels walk their work: *candidates_per_workgroup (one per lane) and *samples_per_stage of the K rows and the reference
+ * side per LDS stage of the slot kernel; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_waveform_candidates_shape(int K, int *candidates_per_workgroup, int *samples_per_stage);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -68,6 +68,21 @@ struct PooledEvents {
     }
 };
 
+// With a misfit filter the traces a call keeps come from the library transforms; the filtered references are made by the transform
+// their trial sources go through (make_variants), so for the length of the call that is the library's for every length -- the way
+// kiwi_hip_get_amp_spectrum forces it --, and the reference variants are made afresh before and after
+struct LibraryTransforms {
+    kiwi_hip_ctx *c; bool fused, touched;
+    explicit LibraryTransforms(kiwi_hip_ctx *ctx) : c(ctx), fused(ctx->fused_fft), touched(ctx->fft_needed && ctx->fused_fft)
+    {
+        if (touched) { c->fused_fft = false; drop_variants(); }
+    }
+    ~LibraryTransforms() { if (touched) { c->fused_fft = fused; drop_variants(); } }
+    LibraryTransforms(const LibraryTransforms &) = delete;
+    LibraryTransforms &operator=(const LibraryTransforms &) = delete;
+    void drop_variants() { c->variants.clear(); c->refamp_h.clear(); c->filtw_h.clear(); c->reffilt_h.clear(); }
+};
+
 // what source s adds to the workspace of a chunk of run_chunk whatever the call: geometry records, coefficient lines, plans.  The
 // synthetic rows differ by call and are added by each
 static size_t source_workspace_bytes(const kiwi_hip_ctx *c, int s, size_t nrec)

@@ -284,6 +284,12 @@ struct kiwi_hip_ctx {
         DevBuf<float2> spec;
         DevBuf<int> tile_i, best_index, status, slots, info;
     } speccand_bufs;
+    float wavecand_ms[4] = { 0.f, 0.f, 0.f, 0.f };    // evaluation, slot kernel, fold kernels, downloads of the last kiwi_hip_waveform_candidates
+    struct WaveCandBufs {                             // device buffers of kiwi_hip_waveform_candidates, grown only (info: records as ints)
+        DevBuf<double> w, misfit, tile_v, best_misfit;
+        DevBuf<float> x, smis, slab, norm;
+        DevBuf<int> tile_i, best_index, status, ok, info;
+    } wavecand_bufs;
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
     float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
@@ -1545,6 +1551,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_candidates_timescan.hpp"
 #include "kiwi_linfit_candidates_bootstrap.hpp"
 #include "kiwi_spectral_candidates.hpp"
+#include "kiwi_waveform_candidates.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2925,12 +2932,16 @@ struct SpecCandCall { int K; const double *weight; int anarchy; spectral_candida
 // (kiwi_hip_linear_fit_candidates_bootstrap_params the same with `candboot` set: groups of K basis sources as for `fit`, a piece is
 // evaluated by linfit_candidates_bootstrap::run, which folds its per-draw bests into those of the call)
 struct CandBootCall { int K; const double *weight; int anarchy; linfit_candidates_bootstrap::Boot boot; timescan::Offsets of; };
+// (kiwi_hip_waveform_candidates_params the same with `wavecand` set: groups of K basis sources as for `fit`, a piece is evaluated by
+// waveform_candidates::run)
+struct WaveCandCall { int K; const double *weight; int anarchy; waveform_candidates::Call call; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
                            const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
-                           const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr)
+                           const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr,
+                           const WaveCandCall *wavecand = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2946,8 +2957,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (candfloat) linfit_candidates_floating::check_setup(c, candfloat->K, candfloat->fl);
     if (speccand) spectral_candidates::check_setup(c, speccand->K, speccand->call);
     if (candboot) linfit_candidates_bootstrap::check_setup(c, candboot->K, candboot->of, candboot->weight, candboot->boot);
+    if (wavecand) waveform_candidates::check_setup(c, wavecand->K, wavecand->call);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -2989,18 +3001,22 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool candbooting = candboot != nullptr;
             CandBootCall mine_candboot{};
             if (candbooting) { mine_candboot = *candboot; mine_candboot.boot = candboot->boot.at((size_t)(s0 / unit)); }
+            const bool wavecanding = wavecand != nullptr;
+            WaveCandCall mine_wavecand{};
+            if (wavecanding) { mine_wavecand = *wavecand; mine_wavecand.call = wavecand->call.at(s0 / unit, (int)nmis); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
                                        fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
                                        candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
-                                       speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr);
+                                       speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr,
+                                       wavecanding ? &mine_wavecand : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3143,6 +3159,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (candfloat) linfit_candidates_floating::fill_failed(n / unit, nrec_all, candfloat->fl.at(s0 / unit, nrec_all));
             if (speccand) spectral_candidates::fill_failed(n / unit, (int)nmis, unit, speccand->call.at(s0 / unit, (int)nmis, unit));
             if (candboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), candboot->boot.at((size_t)(s0 / unit)));
+            if (wavecand) waveform_candidates::fill_failed(n / unit, (int)nmis, wavecand->call.at(s0 / unit, (int)nmis));
             continue;
         }
         upload_batch(c, hb);
@@ -3164,6 +3181,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             spectral_candidates::run(c, 0, n / unit, unit, speccand->weight, speccand->anarchy, speccand->call.at(s0 / unit, (int)nmis, unit));
         else if (candboot)
             linfit_candidates_bootstrap::run(c, 0, n / unit, unit, candboot->of, candboot->weight, candboot->anarchy, candboot->boot.at((size_t)(s0 / unit)));
+        else if (wavecand)
+            waveform_candidates::run(c, 0, n / unit, unit, wavecand->weight, wavecand->anarchy, wavecand->call.at(s0 / unit, (int)nmis));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3581,6 +3600,57 @@ int kiwi_hip_spectral_candidates_shape(kiwi_hip_ctx *c, int K, int *candidates_p
     *spectra_bins = spectral_candidates::spectra_bins(c);
     return 0;
     GUARD_END(c)
+}
+
+// The candidate evaluation under the time-domain l1norm and l2norm from the kept traces of the basis sources
+// (kiwi_waveform_candidates.hpp)
+int kiwi_hip_waveform_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                 const double *receiver_weight, int anarchy, int *best_index, double *best_misfit, int *status,
+                                 double *misfit, float *slot_misfit, float *slot_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->wavecand_ms) t = 0.f;
+    const waveform_candidates::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, misfit, slot_misfit, slot_norm };
+    waveform_candidates::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_waveform_candidates_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int ncand,
+                                        const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                        int *best_index, double *best_misfit, int *status, double *misfit, float *slot_misfit,
+                                        float *slot_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > waveform_candidates::kMaxBasis)
+        return fail(c, "waveform_candidates: K = " + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(waveform_candidates::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "waveform_candidates: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->wavecand_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_ms) t = 0.f;
+    const WaveCandCall wavecand{ K, receiver_weight, anarchy,
+                                 waveform_candidates::Call{ candidates, ncand, outer_norm, best_index, best_misfit, status, misfit,
+                                                            slot_misfit, slot_norm } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, &wavecand);
+}
+
+int kiwi_hip_get_waveform_candidates_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_ms[i];
+    return 0;
+}
+
+int kiwi_hip_waveform_candidates_shape(int K, int *candidates_per_workgroup, int *samples_per_stage)
+{
+    if (K < 1 || K > waveform_candidates::kMaxBasis || !candidates_per_workgroup || !samples_per_stage) return 1;
+    *candidates_per_workgroup = waveform_candidates::kThreads;
+    *samples_per_stage = waveform_candidates::kStage;
+    return 0;
 }
 
 // The candidate evaluation at many origin times from one synthesis of the basis (kiwi_linfit_candidates_timescan.hpp).  The free fit

@@ -402,15 +402,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     check_group_range("linear_fit", c, isrc0, ngroup, K);
     if (ngroup == 0) return;
     const int nrec = (int)c->recv.size(), NN = nn_of(K);
-    // With a misfit filter the kept traces come from the library transforms; the filtered references are made by the transform
-    // their trial sources go through (make_variants), so for the duration of the call that is the library's for every length --
-    // the way kiwi_hip_get_amp_spectrum forces it --, and the reference variants are made afresh before and after.
-    struct Restore {
-        kiwi_hip_ctx *c; bool fused, touched;
-        static void drop_variants(kiwi_hip_ctx *c) { c->variants.clear(); c->refamp_h.clear(); c->filtw_h.clear(); c->reffilt_h.clear(); }
-        ~Restore() { if (touched) { c->fused_fft = fused; drop_variants(c); } }
-    } restore{ c, c->fused_fft, false };
-    if (c->fft_needed && c->fused_fft) { c->fused_fft = false; Restore::drop_variants(c); restore.touched = true; }
+    const LibraryTransforms library_transforms(c);      // (a misfit filter: the kept traces through the library transforms)
     c->misfit_d.ensure((size_t)c->nsrc * c->nmis, &c->dev_bytes);
     c->global_d.ensure((size_t)c->nsrc, &c->dev_bytes);
     if (c->fft_needed && !c->fft_ready) prepare_fft(c, c->reft_h);

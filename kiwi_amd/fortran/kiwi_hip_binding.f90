@@ -800,6 +800,49 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, bins_per_stage, spectra_bins
         end function
 
+        ! the candidate evaluation under the time-domain l1norm / l2norm from the kept traces of the basis sources
+        integer(c_int) function kiwi_hip_waveform_candidates( ctx, isrc0, ngroup, k, ncand, candidates, outer_norm, receiver_weight, &
+                anarchy, best_index, best_misfit, status, misfit, slot_misfit, slot_norm ) bind(C, name='kiwi_hip_waveform_candidates')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, ncand, outer_norm, anarchy      ! isrc0 0-based
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_index(*)  ! (ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: misfit                  ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_misfit             ! c_loc of real(c_float) (nmis, ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_norm               ! c_loc of real(c_float) (nmis, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_params( ctx, sourcetype, ngroup, k, params, piece, ncand, candidates, &
+                outer_norm, receiver_weight, anarchy, best_index, best_misfit, status, misfit, slot_misfit, slot_norm ) &
+                bind(C, name='kiwi_hip_waveform_candidates_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, ncand, outer_norm, anarchy
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_index(*), status(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: misfit, slot_misfit, slot_norm      ! as in kiwi_hip_waveform_candidates
+        end function
+
+        integer(c_int) function kiwi_hip_get_waveform_candidates_ms( ctx, ms ) bind(C, name='kiwi_hip_get_waveform_candidates_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, slot kernel, fold kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_shape( k, candidates_per_workgroup, samples_per_stage ) &
+                bind(C, name='kiwi_hip_waveform_candidates_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, samples_per_stage
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

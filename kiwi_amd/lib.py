@@ -207,6 +207,12 @@ def load():
                                                 C.c_int, c_float_p, c_int_p, c_float_p],
         "kiwi_hip_get_spectral_candidates_ms": [vp, c_float_p],
         "kiwi_hip_spectral_candidates_shape": [vp, C.c_int, c_int_p, c_int_p, c_int_p],
+        "kiwi_hip_waveform_candidates": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, c_int_p, c_double_p,
+                                         c_int_p, c_double_p, c_float_p, c_float_p],
+        "kiwi_hip_waveform_candidates_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
+                                                C.c_int, c_int_p, c_double_p, c_int_p, c_double_p, c_float_p, c_float_p],
+        "kiwi_hip_get_waveform_candidates_ms": [vp, c_float_p],
+        "kiwi_hip_waveform_candidates_shape": [C.c_int, c_int_p, c_int_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],

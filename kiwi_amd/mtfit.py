@@ -317,3 +317,36 @@ def scan_double_couples_spectral(engine, sourcetype, params, strikes, dips, rake
         if free:
             out["moments"] = (scan.scale * float(unit)).reshape(len(p), len(s), len(d), len(r))
     return out
+
+
+def scan_double_couples_waveform(engine, sourcetype, rows, strikes, dips, rakes, moment, outer_norm="l1norm", unit=1e18,
+                                 receiver_weights=None, anarchy=False, piece=0, cube=False, slot_misfit=False):
+    """`scan_double_couples` under the time-domain l1norm inside (`Engine.waveform_candidates_params`): the engine's misfit method
+    is l1norm (or l2norm, evaluated from the residual itself), and every mechanism of the grid is a combination of the kept
+    traces of the SIX syntheses of a row, compared with the data sample by sample -- the fully robust search, l1 inside and
+    outside, without a synthesis per mechanism.  moment [N m] is a number or a sequence: with a sequence the candidates are
+    mechanisms x moments (the moment varies fastest).  moment=None (the best moment per mechanism) is refused: under l1norm the
+    best scale of a direction has no closed form; the moment axis is more candidates.  Returns a dict: strike, dip, rake, moment,
+    misfit [N] of the best candidate (NaN where there is none), index [N] its row among the candidates (-1: none), status [N]
+    (0 evaluated, 1 no receiver counts, 2 the row failed to discretise), scan: the `WaveformCandidateScan`; cube=True adds cube
+    [N, ns, nd, nr], every mechanism's misfit ([N, ns, nd, nr, nmoment] where moment is a sequence)."""
+    if moment is None:
+        raise KiwiHipError("scan_double_couples_waveform: moment=None (the best moment per mechanism) has no closed form under l1norm; "
+                           "give a moment, or a sequence of moments as a further axis of candidates")
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    s, d, r = list(strikes), list(dips), list(rakes)
+    moments = np.atleast_1d(np.asarray(moment, np.float64))
+    mech, sdr = double_couple_candidates(s, d, r, 1.0)
+    cand = (mech[:, None, :] * (moments / float(unit))[None, :, None]).reshape(-1, 6)
+    scan = engine.waveform_candidates_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, outer_norm=outer_norm,
+                                             receiver_weights=receiver_weights, anarchy=anarchy, misfit=cube, slot_misfit=slot_misfit,
+                                             piece=piece)
+    has = scan.best_index >= 0
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, None], sdr[at // len(moments)], np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=np.where(has, moments[at % len(moments)], np.nan),
+               misfit=scan.best_misfit, index=scan.best_index, status=scan.status, scan=scan)
+    if cube:
+        shape = (len(p), len(s), len(d), len(r)) + ((len(moments),) if np.ndim(moment) else ())
+        out["cube"] = scan.misfit.reshape(shape)
+    return out
