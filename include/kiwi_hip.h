@@ -859,6 +859,48 @@ int kiwi_hip_get_waveform_candidates_ms(kiwi_hip_ctx *ctx, float ms[4]);
 /* how the kernels walk their work: *candidates_per_workgroup (one per lane) and *samples_per_stage of the K rows and the reference
  * side per LDS stage of the slot kernel; answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_waveform_candidates_shape(int K, int *candidates_per_workgroup, int *samples_per_stage);
+/* kiwi_hip_waveform_candidates under the floating norms (kiwi_waveform_candidates_floating.hpp): floating_l1norm (8) -- l1 inside
+ * against a glitched station AND per-receiver whole-sample shifts against a mis-timed one, at once -- and floating_l2norm (7) in the
+ * reference's per-slot form (kiwi_hip_linear_fit_candidates_floating folds that norm per receiver).  Every receiver slides its
+ * reference under the fixed taper inside its own range (kiwi_hip_set_floating_shiftrange); the taper stays with the synthetic, so
+ * the combined trace v of a candidate is formed once per sample and a further shift costs a subtraction, a |.| and one fp64 add.
+ * Groups, K, receiver_weight, anarchy, candidates and the fold are kiwi_hip_waveform_candidates'.  Per receiver and candidate, slots
+ * k ascending, shift index q = 0 .. ns - 1 (shift lo + q):
+ *   a_q[i]                 the un-tapered reference moved by lo + q, times the taper weight of sample i (one fp32 product)
+ *   per sample, ascending  v as in kiwi_hip_waveform_candidates; d = a_q[i] - v (synthetics factor as the comparator applies it); ONE
+ *                          fp64 accumulator per (slot, shift): d^2 | |d|
+ *   m_kq                   (float) sqrt(dt acc) | (float) (dt acc)
+ *   the shift              sum_q = sum_q + (l1 inside ? m_kq : m_kq m_kq) in fp32, k ascending from 0; the FIRST minimum over q wins
+ *                          (the receiver's sum decides, not a slot's): exactly how kiwi_hip_eval chooses a source's shifts
+ *   slot misfit            m_kq at the winning shift; the slot norm factor is the context's floating one (the mean over the shifts of
+ *                          the moved reference's norm)
+ *   best_shift             int [ngroup][nrec]: the winner's shifts in samples, 0 for a disabled receiver or where no candidate won
+ *   cand_shift             short [ngroup][ncand][nrec] or NULL (needs misfit): every candidate's shifts
+ *   best_index, best_misfit, status, misfit, slot_misfit, slot_norm   as in kiwi_hip_waveform_candidates
+ * With every range (0, 0) the answers are kiwi_hip_waveform_candidates' under l1norm / l2norm bit for bit.  There is no free scale.
+ * The answer does not depend on the pass a shift falls into, tiling, chunking (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of
+ * devices.  Afterwards the context is what kiwi_hip_eval of the basis sources leaves.  Refused with a message that starts with
+ * "waveform_candidates_floating:", nothing approximated: a method other than 7 or 8 (l1norm and l2norm go through
+ * kiwi_hip_waveform_candidates); an enabled receiver without a misfit taper or without references; K outside 1 .. 8; a range outside
+ * the batch; ncand < 1; a candidate that is not finite; a bad outer_norm; slot_misfit without slot_norm or the reverse; cand_shift
+ * without misfit, or with a shift range beyond 16 bits; null mandatory arrays (best_shift is one). */
+int kiwi_hip_waveform_candidates_floating(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                          int outer_norm, const double *receiver_weight, int anarchy, int *best_index, double *best_misfit,
+                                          int *status, int *best_shift, double *misfit, short *cand_shift, float *slot_misfit,
+                                          float *slot_norm);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it */
+int kiwi_hip_waveform_candidates_floating_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                 int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                 int anarchy, int *best_index, double *best_misfit, int *status, int *best_shift,
+                                                 double *misfit, short *cand_shift, float *slot_misfit, float *slot_norm);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the floating slot kernel, ms[2] the fold
+ * kernels, ms[3] downloads.  The host's tables of a chunk and their upload lie between ms[0] and ms[1], in neither */
+int kiwi_hip_get_waveform_candidates_floating_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the kernel walks its work: *candidates_per_workgroup (one per lane), *samples_per_stage per LDS stage, and *shifts_per_pass
+ * whose accumulators a lane holds in registers at once; answers without a device.  Non-zero for K outside
+ * 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_waveform_candidates_floating_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *shifts_per_pass);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

@@ -290,6 +290,11 @@ struct kiwi_hip_ctx {
         DevBuf<float> x, smis, slab, norm;
         DevBuf<int> tile_i, best_index, status, ok, info;
     } wavecand_bufs;
+    float wavecand_float_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, floating slot kernel, fold kernels, downloads of the last kiwi_hip_waveform_candidates_floating
+    struct WaveCandFloatBufs : WaveCandBufs {         // device buffers of kiwi_hip_waveform_candidates_floating, grown only
+        DevBuf<short> shift, cshift;
+        DevBuf<int> best_shift;
+    } wavecand_float_bufs;
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
     float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
@@ -1552,6 +1557,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_candidates_bootstrap.hpp"
 #include "kiwi_spectral_candidates.hpp"
 #include "kiwi_waveform_candidates.hpp"
+#include "kiwi_waveform_candidates_floating.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2935,13 +2941,16 @@ struct CandBootCall { int K; const double *weight; int anarchy; linfit_candidate
 // (kiwi_hip_waveform_candidates_params the same with `wavecand` set: groups of K basis sources as for `fit`, a piece is evaluated by
 // waveform_candidates::run)
 struct WaveCandCall { int K; const double *weight; int anarchy; waveform_candidates::Call call; };
+// (kiwi_hip_waveform_candidates_floating_params the same with `wavefloat` set: a piece is evaluated by
+// waveform_candidates_floating::run)
+struct WaveCandFloatCall { int K; const double *weight; int anarchy; waveform_candidates_floating::Call call; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
                            const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
                            const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr,
-                           const WaveCandCall *wavecand = nullptr)
+                           const WaveCandCall *wavecand = nullptr, const WaveCandFloatCall *wavefloat = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2958,8 +2967,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (speccand) spectral_candidates::check_setup(c, speccand->K, speccand->call);
     if (candboot) linfit_candidates_bootstrap::check_setup(c, candboot->K, candboot->of, candboot->weight, candboot->boot);
     if (wavecand) waveform_candidates::check_setup(c, wavecand->K, wavecand->call);
+    if (wavefloat) waveform_candidates_floating::check_setup(c, wavefloat->K, wavefloat->call);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -3004,6 +3014,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool wavecanding = wavecand != nullptr;
             WaveCandCall mine_wavecand{};
             if (wavecanding) { mine_wavecand = *wavecand; mine_wavecand.call = wavecand->call.at(s0 / unit, (int)nmis); }
+            const bool wavefloating = wavefloat != nullptr;
+            WaveCandFloatCall mine_wavefloat{};
+            if (wavefloating) { mine_wavefloat = *wavefloat; mine_wavefloat.call = wavefloat->call.at(s0 / unit, (int)nmis, nrec_all); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
@@ -3011,12 +3024,12 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
                                        candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
                                        speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr,
-                                       wavecanding ? &mine_wavecand : nullptr);
+                                       wavecanding ? &mine_wavecand : nullptr, wavefloating ? &mine_wavefloat : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3160,6 +3173,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (speccand) spectral_candidates::fill_failed(n / unit, (int)nmis, unit, speccand->call.at(s0 / unit, (int)nmis, unit));
             if (candboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), candboot->boot.at((size_t)(s0 / unit)));
             if (wavecand) waveform_candidates::fill_failed(n / unit, (int)nmis, wavecand->call.at(s0 / unit, (int)nmis));
+            if (wavefloat) waveform_candidates_floating::fill_failed(n / unit, (int)nmis, nrec_all, wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
             continue;
         }
         upload_batch(c, hb);
@@ -3183,6 +3197,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             linfit_candidates_bootstrap::run(c, 0, n / unit, unit, candboot->of, candboot->weight, candboot->anarchy, candboot->boot.at((size_t)(s0 / unit)));
         else if (wavecand)
             waveform_candidates::run(c, 0, n / unit, unit, wavecand->weight, wavecand->anarchy, wavecand->call.at(s0 / unit, (int)nmis));
+        else if (wavefloat)
+            waveform_candidates_floating::run(c, 0, n / unit, unit, wavefloat->weight, wavefloat->anarchy,
+                                              wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3650,6 +3667,59 @@ int kiwi_hip_waveform_candidates_shape(int K, int *candidates_per_workgroup, int
     if (K < 1 || K > waveform_candidates::kMaxBasis || !candidates_per_workgroup || !samples_per_stage) return 1;
     *candidates_per_workgroup = waveform_candidates::kThreads;
     *samples_per_stage = waveform_candidates::kStage;
+    return 0;
+}
+
+// The candidate evaluation under floating_l1norm and floating_l2norm from the kept traces of the basis sources: per receiver and
+// candidate the best whole-sample shift of the reference (kiwi_waveform_candidates_floating.hpp)
+int kiwi_hip_waveform_candidates_floating(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                          const double *receiver_weight, int anarchy, int *best_index, double *best_misfit, int *status,
+                                          int *best_shift, double *misfit, short *cand_shift, float *slot_misfit, float *slot_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->wavecand_float_ms) t = 0.f;
+    const waveform_candidates_floating::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
+                                                 cand_shift, slot_misfit, slot_norm };
+    waveform_candidates_floating::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_waveform_candidates_floating_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                 int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                 int anarchy, int *best_index, double *best_misfit, int *status, int *best_shift,
+                                                 double *misfit, short *cand_shift, float *slot_misfit, float *slot_norm)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > waveform_candidates_floating::kMaxBasis)
+        return fail(c, "waveform_candidates_floating: K = " + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(waveform_candidates_floating::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "waveform_candidates_floating: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->wavecand_float_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_float_ms) t = 0.f;
+    const WaveCandFloatCall wavefloat{ K, receiver_weight, anarchy,
+                                       waveform_candidates_floating::Call{ candidates, ncand, outer_norm, best_index, best_misfit, status,
+                                                                           best_shift, misfit, cand_shift, slot_misfit, slot_norm } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &wavefloat);
+}
+
+int kiwi_hip_get_waveform_candidates_floating_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_float_ms[i];
+    return 0;
+}
+
+int kiwi_hip_waveform_candidates_floating_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *shifts_per_pass)
+{
+    if (K < 1 || K > waveform_candidates_floating::kMaxBasis || !candidates_per_workgroup || !samples_per_stage || !shifts_per_pass) return 1;
+    *candidates_per_workgroup = waveform_candidates_floating::kThreads;
+    *samples_per_stage = waveform_candidates_floating::kStage;
+    *shifts_per_pass = waveform_candidates_floating::shifts_per_pass(K);
     return 0;
 }
 

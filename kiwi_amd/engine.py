@@ -32,6 +32,8 @@ CandidateBootstrap = collections.namedtuple("CandidateBootstrap", "best_value be
 SpectralCandidateScan = collections.namedtuple("SpectralCandidateScan", "best_index best_misfit status misfit scale slot_misfit slot_norm "
                                                                         "spectra spectra_range spectra_ref")
 WaveformCandidateScan = collections.namedtuple("WaveformCandidateScan", "best_index best_misfit status misfit slot_misfit slot_norm")
+WaveformCandidateFloatingScan = collections.namedtuple("WaveformCandidateFloatingScan",
+                                                       "best_index best_misfit status best_shift misfit cand_shift slot_misfit slot_norm")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -1231,6 +1233,88 @@ class Engine:
         the host's tables of a chunk and their upload lie between the first two, in neither."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_waveform_candidates_ms(self.h, _fp(ms)), "get_waveform_candidates_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ candidates under floating_l1norm / floating_l2norm (kiwi_hip_waveform_candidates_floating)
+    def waveform_candidates_floating_shape(self, K):
+        """(candidates per workgroup, samples per LDS stage, shifts per pass) of `waveform_candidates_floating` for K basis sources;
+        needs no device."""
+        c, s, j = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_waveform_candidates_floating_shape(int(K), _ip(c), _ip(s), _ip(j)):
+            raise KiwiHipError("waveform_candidates_floating: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(s[0]), int(j[0])
+
+    def _waveform_candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift, slot_misfit):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        K, ng = int(K), int(ngroup)
+        if not 1 <= K <= self.linear_fit_max_basis():
+            raise KiwiHipError("waveform_candidates_floating: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != K:
+            raise KiwiHipError("waveform_candidates_floating: candidates must be [ncand, K = %d]" % K)
+        nc, nrec = len(x), len(self.components)
+        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        out = WaveformCandidateFloatingScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nrec), np.int32),
+                                            np.zeros((ng, nc)) if misfit else None, np.zeros((ng, nc, nrec), np.int16) if cand_shift else None,
+                                            np.zeros((ng, nc, nmis), np.float32) if slot_misfit else None,
+                                            np.zeros((ng, nmis), np.float32) if slot_misfit else None)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
+        sp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_short))      # noqa: E731
+        tail = (nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), _ip(out.best_shift), dp(out.misfit), sp(out.cand_shift),      # noqa: E731
+                        fp(out.slot_misfit), fp(out.slot_norm))
+        return tail, out, outs, (x, w)
+
+    def waveform_candidates_floating(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
+                                     misfit=True, cand_shift=False, slot_misfit=False):
+        """`waveform_candidates` under floating_l1norm / floating_l2norm (kiwi_hip_waveform_candidates_floating): per receiver and
+        candidate the reference slides under the fixed taper by the whole-sample shifts of the receiver's range
+        (`set_floating_shiftrange`), and the shift with the smallest sum over the receiver's slots wins, as in `eval`.  Returns
+        a `WaveformCandidateFloatingScan`: best_index[ngroup] (-1: none), best_misfit[ngroup], status[ngroup] (0 evaluated, 1 no
+        receiver counts, 2 a basis source failed to discretise), best_shift[ngroup, nrec] (samples; 0 for a disabled receiver),
+        misfit[ngroup, ncand] (misfit=True), cand_shift[ngroup, ncand, nrec] int16 (cand_shift=True, needs misfit),
+        slot_misfit[ngroup, ncand, nmis] and slot_norm[ngroup, nmis] float32 (slot_misfit=True: what `outer_misfits_slots`
+        takes).  There is no free scale."""
+        tail, out, outs, keep = self._waveform_candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit,
+                                                                         cand_shift, slot_misfit)
+        self._ck(self.L.kiwi_hip_waveform_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0, *outs()),
+                 "waveform_candidates_floating")
+        return out
+
+    def waveform_candidates_floating_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None,
+                                            anarchy=False, misfit=True, cand_shift=False, slot_misfit=False, piece=0):
+        """`waveform_candidates_floating` for a parameter list of any length (kiwi_hip_waveform_candidates_floating_params), cut
+        into pieces and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("waveform_candidates_floating: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("waveform_candidates_floating: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        tail, out, outs, keep = self._waveform_candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit,
+                                                                         cand_shift, slot_misfit)
+        try:
+            self._ck(self.L.kiwi_hip_waveform_candidates_floating_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
+                                                                         1 if anarchy else 0, *outs()), "waveform_candidates_floating")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def waveform_candidates_floating_ms(self):
+        """HIP-event durations [ms] of the last `waveform_candidates_floating`: (evaluation, the floating slot kernel, the fold
+        kernels, downloads); the host's tables of a chunk and their upload lie between the first two, in neither."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_waveform_candidates_floating_ms(self.h, _fp(ms)), "get_waveform_candidates_floating_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)

@@ -50,6 +50,10 @@ program binding_smoke
     if (kiwi_hip_waveform_candidates_shape( 6_c_int, per_group, per_stage ) /= 0) stop 23
     if (per_group < 64 .or. per_stage < 1) stop 24
 
+    ! and of the floating time-domain norms: the shifts a lane holds accumulators for at once as well
+    if (kiwi_hip_waveform_candidates_floating_shape( 6_c_int, per_group, per_stage, per_pass ) /= 0) stop 25
+    if (per_group < 64 .or. per_stage < 1 .or. per_pass < 1) stop 26
+
     ! the joint bootstrap of a candidate search: candidates per workgroup, draws per tile, the most receivers its LDS holds
     if (kiwi_hip_linear_fit_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 15
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 16

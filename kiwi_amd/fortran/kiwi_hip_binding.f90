@@ -843,6 +843,53 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, samples_per_stage
         end function
 
+        ! the candidate evaluation under floating_l1norm / floating_l2norm: kiwi_hip_waveform_candidates with per-receiver shifts
+        integer(c_int) function kiwi_hip_waveform_candidates_floating( ctx, isrc0, ngroup, k, ncand, candidates, outer_norm, &
+                receiver_weight, anarchy, best_index, best_misfit, status, best_shift, misfit, cand_shift, slot_misfit, slot_norm ) &
+                bind(C, name='kiwi_hip_waveform_candidates_floating')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, ncand, outer_norm, anarchy      ! isrc0 0-based
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_index(*)  ! (ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            integer(c_int), intent(out) :: best_shift(*)  ! (nrec, ngroup): the winner's shifts in samples
+            type(c_ptr), value :: misfit                  ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: cand_shift              ! c_loc of integer(c_short) (nrec, ncand, ngroup), or c_null_ptr; needs misfit
+            type(c_ptr), value :: slot_misfit             ! c_loc of real(c_float) (nmis, ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_norm               ! c_loc of real(c_float) (nmis, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_floating_params( ctx, sourcetype, ngroup, k, params, piece, ncand, &
+                candidates, outer_norm, receiver_weight, anarchy, best_index, best_misfit, status, best_shift, misfit, cand_shift, &
+                slot_misfit, slot_norm ) bind(C, name='kiwi_hip_waveform_candidates_floating_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, ncand, outer_norm, anarchy
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_index(*), status(*), best_shift(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: misfit, cand_shift, slot_misfit, slot_norm      ! as in kiwi_hip_waveform_candidates_floating
+        end function
+
+        integer(c_int) function kiwi_hip_get_waveform_candidates_floating_ms( ctx, ms ) &
+                bind(C, name='kiwi_hip_get_waveform_candidates_floating_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, floating slot kernel, fold kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_floating_shape( k, candidates_per_workgroup, samples_per_stage, &
+                shifts_per_pass ) bind(C, name='kiwi_hip_waveform_candidates_floating_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, samples_per_stage, shifts_per_pass
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

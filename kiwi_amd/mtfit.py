@@ -350,3 +350,51 @@ def scan_double_couples_waveform(engine, sourcetype, rows, strikes, dips, rakes,
         shape = (len(p), len(s), len(d), len(r)) + ((len(moments),) if np.ndim(moment) else ())
         out["cube"] = scan.misfit.reshape(shape)
     return out
+
+
+def scan_double_couples_waveform_floating(engine, sourcetype, rows, strikes, dips, rakes, moment, outer_norm="l1norm", unit=1e18,
+                                          receiver_weights=None, anarchy=False, piece=0, cube=False, slot_misfit=False, bootstrap=None):
+    """`scan_double_couples_waveform` with per-receiver time shifts (`Engine.waveform_candidates_floating_params`): the engine's
+    misfit method is floating_l1norm (or floating_l2norm) and every receiver has its own range of whole-sample shifts
+    (`set_floating_shiftrange`); per mechanism every receiver takes the shift under which the sum over its components is smallest,
+    still from the SIX syntheses of a row -- l1 inside and outside against a glitched station, shifts against a mis-timed one.
+    moment [N m] is a number or a sequence (mechanisms x moments, the moment fastest); moment=None is refused as in
+    `scan_double_couples_waveform`.  Returns a dict: strike, dip, rake, moment, misfit [N] of the best candidate (NaN where there
+    is none), index [N] its row among the candidates (-1: none), status [N] (0 evaluated, 1 no receiver counts, 2 the row failed
+    to discretise), shifts [N, nrec]: the best candidate's shift of every receiver in SECONDS (0 for a disabled receiver), scan:
+    the `WaveformCandidateFloatingScan`; cube=True adds cube [N, ns, nd, nr] ([N, ns, nd, nr, nmoment] where moment is a
+    sequence) and cube_shifts, the same with a last axis nrec, in samples (int16).  bootstrap: draw weights [ndraw, nrec]
+    (`engine.bootstrap_draw_weights`); adds boot_misfit and boot_index [N, ndraw], the best candidate of every row under every
+    draw, through `Engine.outer_misfits_slots` on the scan's slot misfits (every candidate keeps the shifts it chose without weights)."""
+    if moment is None:
+        raise KiwiHipError("scan_double_couples_waveform_floating: moment=None (the best moment per mechanism) has no closed form under "
+                           "l1norm or under shifts; give a moment, or a sequence of moments as a further axis of candidates")
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    s, d, r = list(strikes), list(dips), list(rakes)
+    moments = np.atleast_1d(np.asarray(moment, np.float64))
+    mech, sdr = double_couple_candidates(s, d, r, 1.0)
+    cand = (mech[:, None, :] * (moments / float(unit))[None, :, None]).reshape(-1, 6)
+    scan = engine.waveform_candidates_floating_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, outer_norm=outer_norm,
+                                                      receiver_weights=receiver_weights, anarchy=anarchy, misfit=cube, cand_shift=cube,
+                                                      slot_misfit=slot_misfit or bootstrap is not None, piece=piece)
+    has = scan.best_index >= 0
+    at = np.where(has, scan.best_index, 0)
+    pick = np.where(has[:, None], sdr[at // len(moments)], np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=np.where(has, moments[at % len(moments)], np.nan),
+               misfit=scan.best_misfit, index=scan.best_index, status=scan.status, shifts=scan.best_shift * float(engine.dt), scan=scan)
+    if cube:
+        shape = (len(p), len(s), len(d), len(r)) + ((len(moments),) if np.ndim(moment) else ())
+        out["cube"] = scan.misfit.reshape(shape)
+        out["cube_shifts"] = scan.cand_shift.reshape(shape + (-1,))
+    if bootstrap is not None:
+        draws = np.atleast_2d(np.asarray(bootstrap, np.float64))
+        bm, bi = np.full((len(p), len(draws)), np.nan), np.full((len(p), len(draws)), -1, np.int32)
+        nrec = len(engine.components)
+        slot_receiver = np.repeat(np.arange(nrec, dtype=np.int32), [len(c) if engine.enabled[ir] else 0 for ir, c in enumerate(engine.components)])
+        for g in range(len(p)):
+            if scan.status[g] == 0:
+                bv, ix, _ = engine.outer_misfits_slots(scan.slot_misfit[g], np.tile(scan.slot_norm[g], (len(cand), 1)), slot_receiver, nrec,
+                                                       outer_norm, receiver_weights, anarchy, draws)
+                bm[g], bi[g] = bv, np.where(bv == bv, ix, -1)
+        out["boot_misfit"], out["boot_index"] = bm, bi
+    return out
