@@ -901,6 +901,66 @@ int kiwi_hip_get_waveform_candidates_floating_ms(kiwi_hip_ctx *ctx, float ms[4])
  * whose accumulators a lane holds in registers at once; answers without a device.  Non-zero for K outside
  * 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_waveform_candidates_floating_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *shifts_per_pass);
+/* kiwi_hip_waveform_candidates at MANY origin times from ONE synthesis of the basis (kiwi_waveform_candidates_timescan.hpp): the best
+ * mechanism, depth and origin time under l1norm (2) inside -- the robust norm -- or l2norm (1).  Groups, K (1 .. 8), candidates
+ * [ncand][K], receiver_weight, anarchy, outer_norm and the statuses are kiwi_hip_waveform_candidates'; the offsets k_j = k0 + j kstep
+ * samples, j < nk, are kiwi_hip_time_scan's, with its limits kiwi_hip_time_scan_max_offsets() and kiwi_hip_time_scan_max_shift().
+ * A source moved by k samples has the same synthetic, moved; the receiver's taper and reference stay at their fixed place.  For
+ * group g, row_a is the folded, moment-scaled, UNTAPERED synthetic of basis source a over the slot's window widened by S = max |k_j|
+ * on either side -- the rows kiwi_hip_linear_fit_time_scan works on --, xf = (float) x.  Per slot (enabled receiver component):
+ *   per extended sample e, ONCE per candidate   u[e] = xf_0 row_0[e]; u = u + xf_a row_a[e], a ascending, every product and sum
+ *                          rounded in fp32
+ *   offset k, window sample i = e + k, i ascending   vt = u[i - k] * taper[i] (one fp32 product); d = ref[i] - vt, ref the tapered
+ *                          reference (synthetics factor as the comparator applies it: 1.f ref[i] - syn_factor vt); ONE fp64
+ *                          accumulator per offset: d^2 | |d|.  A sample outside the window contributes nothing, also where u is
+ *                          not finite
+ *   slot misfit            (float) sqrt(dt acc) | (float) (dt acc); the slot norm factors do not depend on k
+ *   outer fold             kiwi_hip_waveform_candidates', per (group, offset)
+ *   best_index, best_misfit [ngroup][nk]   per offset: NaN passed over, then the value, then the lowest index; -1, NaN if none
+ *   best_offset [ngroup]   the index j of the smallest best_misfit in the same order; -1 if none
+ *   status [ngroup]        0 evaluated; 1 no receiver counts; 2 a basis source of the group failed to discretise
+ *   cand_misfit  double, cand_offset  int [ngroup][ncand] or NULL: per candidate the first smallest misfit over the offsets and its
+ *                          index j (NaN, -1 where every offset is NaN); cand_offset needs cand_misfit
+ *   misfit                 [ngroup][nk][ncand] or NULL
+ *   slot_misfit  float [ngroup][nk][ncand][nmis], slot_norm  float [ngroup][nmis]: with nk x ncand read as sources the pair
+ *                          kiwi_hip_outer_misfits takes -- the bootstrap over mechanism and origin time jointly; slot_misfit needs
+ *                          slot_norm
+ *   rows  float [ngroup][K][row_stride] or NULL: row_a of every basis source, slot m's wlen + 2 S samples from row_offset[m], extended
+ *                          sample e at row_offset[m] + S + e (kiwi_hip_waveform_candidates_time_scan_rows); zeros for a group with
+ *                          status 2
+ * This is the combined source read k samples earlier under the receiver's taper: what kiwi_hip_time_scan would compare for a source
+ * with tensor x.  It is NOT kiwi_hip_waveform_candidates bit for bit at offset 0: that call tapers every basis trace before
+ * combining (x_a fl(row_a taper)), this one combines first and tapers once, which is what the offsets share; the two agree to
+ * rounding.  Two relations are exact: a unit candidate e_a (and K = 1, x = [1]) gives u = row_a, so its slot misfit at offset k is
+ * kiwi_hip_time_scan's for basis source a up to the order of the fp64 sum; and the answer does not depend on tiles, passes, chunking
+ * (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.  Afterwards the context is what kiwi_hip_eval of the basis sources
+ * leaves (offset 0's plain evaluation; the halo is put back).  Refused with a message that starts with
+ * "waveform_candidates_time_scan:", nothing approximated: everything kiwi_hip_waveform_candidates refuses; what kiwi_hip_time_scan
+ * refuses of the offsets (nk, kstep, the largest shift); an enabled receiver with a misfit filter (the taper sits in front of the
+ * filter, so every candidate and offset would need a transform of its own); cand_offset without cand_misfit; slot_misfit without
+ * slot_norm or the reverse; null mandatory arrays (best_offset is one). */
+int kiwi_hip_waveform_candidates_time_scan(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                           const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                           int *best_offset, int *best_index, double *best_misfit, int *status, double *cand_misfit,
+                                           int *cand_offset, double *misfit, float *slot_misfit, float *slot_norm, float *rows);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_waveform_candidates_params cuts it */
+int kiwi_hip_waveform_candidates_time_scan_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                  int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                  const double *receiver_weight, int anarchy, int *best_offset, int *best_index,
+                                                  double *best_misfit, int *status, double *cand_misfit, int *cand_offset, double *misfit,
+                                                  float *slot_misfit, float *slot_norm, float *rows);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the rows and scan kernels, ms[2] the fold
+ * kernels, ms[3] downloads.  The host's tables of a chunk and their upload lie between ms[0] and ms[1], in neither */
+int kiwi_hip_get_waveform_candidates_time_scan_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the kernel walks its work: *candidates_per_workgroup (one per lane), *samples_per_stage of extended samples per LDS stage, and
+ * *offsets_per_pass whose accumulators a lane holds in registers at once; answers without a device.  Non-zero for K outside
+ * 1 .. kiwi_hip_linear_fit_max_basis() */
+int kiwi_hip_waveform_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *offsets_per_pass);
+/* the layout of `rows` for these offsets on this context's receivers: *shift_halo = S, *row_stride floats per basis source, and
+ * row_offset [nmis] (or NULL) where each misfit slot's wlen + 2 S samples begin */
+int kiwi_hip_waveform_candidates_time_scan_rows(kiwi_hip_ctx *ctx, int k0, int kstep, int nk, int *shift_halo, int *row_stride,
+                                                int *row_offset);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

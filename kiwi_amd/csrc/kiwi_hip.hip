@@ -295,6 +295,12 @@ struct kiwi_hip_ctx {
         DevBuf<short> shift, cshift;
         DevBuf<int> best_shift;
     } wavecand_float_bufs;
+    float wavecand_scan_ms[4] = { 0.f, 0.f, 0.f, 0.f };       // evaluation, rows + scan kernel, fold kernels, downloads of the last kiwi_hip_waveform_candidates_time_scan
+    struct WaveCandScanBufs : WaveCandBufs {          // device buffers of kiwi_hip_waveform_candidates_time_scan, grown only
+        DevBuf<float> rows;
+        DevBuf<double> cand_misfit;
+        DevBuf<int> rofs, status_j, best_offset, cand_offset;
+    } wavecand_scan_bufs;
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
     float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
@@ -1558,6 +1564,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_spectral_candidates.hpp"
 #include "kiwi_waveform_candidates.hpp"
 #include "kiwi_waveform_candidates_floating.hpp"
+#include "kiwi_waveform_candidates_timescan.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2944,13 +2951,17 @@ struct WaveCandCall { int K; const double *weight; int anarchy; waveform_candida
 // (kiwi_hip_waveform_candidates_floating_params the same with `wavefloat` set: a piece is evaluated by
 // waveform_candidates_floating::run)
 struct WaveCandFloatCall { int K; const double *weight; int anarchy; waveform_candidates_floating::Call call; };
+// (kiwi_hip_waveform_candidates_time_scan_params the same with `wavescan` set: a piece is evaluated by
+// waveform_candidates_timescan::run)
+struct WaveCandScanCall { int K; const double *weight; int anarchy; waveform_candidates_timescan::Call call; timescan::Offsets of; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
                            const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
                            const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
                            const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr,
-                           const WaveCandCall *wavecand = nullptr, const WaveCandFloatCall *wavefloat = nullptr)
+                           const WaveCandCall *wavecand = nullptr, const WaveCandFloatCall *wavefloat = nullptr,
+                           const WaveCandScanCall *wavescan = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2968,13 +2979,21 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (candboot) linfit_candidates_bootstrap::check_setup(c, candboot->K, candboot->of, candboot->weight, candboot->boot);
     if (wavecand) waveform_candidates::check_setup(c, wavecand->K, wavecand->call);
     if (wavefloat) waveform_candidates_floating::check_setup(c, wavefloat->K, wavefloat->call);
+    if (wavescan) waveform_candidates_timescan::check_setup(c, wavescan->K, wavescan->of, wavescan->call);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : wavescan ? wavescan->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
                                                 "(the device comparator evaluates norms over the taper span, comparator.f90:782-792)");
     const size_t nmis = (size_t)c->nmis;
+    // (the rows of the waveform scan: the same layout on every device and in every piece)
+    const size_t scan_rstride = wavescan ? waveform_candidates_timescan::row_stride(c, wavescan->of.max_abs()) : 0;
+    auto sub_wavescan = [&](int s0) {
+        WaveCandScanCall w = *wavescan;
+        w.call = wavescan->call.at((size_t)(s0 / unit), nmis, (size_t)wavescan->of.nk, (size_t)unit, scan_rstride);
+        return w;
+    };
     if (!c->mates.empty() && nsrc / unit >= 2) {
         // ---- multi-device context: contiguous shards in list order (Source.grid order), shard 0 here -- this context keeps the
         // HEAD of the list as in the one-device case --, the others each in a thread of their own on their device
@@ -3017,6 +3036,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             const bool wavefloating = wavefloat != nullptr;
             WaveCandFloatCall mine_wavefloat{};
             if (wavefloating) { mine_wavefloat = *wavefloat; mine_wavefloat.call = wavefloat->call.at(s0 / unit, (int)nmis, nrec_all); }
+            const bool wavescanning = wavescan != nullptr;
+            const WaveCandScanCall mine_wavescan = wavescanning ? sub_wavescan(s0) : WaveCandScanCall{};
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
@@ -3024,12 +3045,13 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                                        fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
                                        candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
                                        speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr,
-                                       wavecanding ? &mine_wavecand : nullptr, wavefloating ? &mine_wavefloat : nullptr);
+                                       wavecanding ? &mine_wavecand : nullptr, wavefloating ? &mine_wavefloat : nullptr,
+                                       wavescanning ? &mine_wavescan : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat, wavescan);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3174,6 +3196,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (candboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), candboot->boot.at((size_t)(s0 / unit)));
             if (wavecand) waveform_candidates::fill_failed(n / unit, (int)nmis, wavecand->call.at(s0 / unit, (int)nmis));
             if (wavefloat) waveform_candidates_floating::fill_failed(n / unit, (int)nmis, nrec_all, wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
+            if (wavescan) waveform_candidates_timescan::fill_failed((size_t)(n / unit), nmis, (size_t)wavescan->of.nk, (size_t)unit, scan_rstride, sub_wavescan(s0).call);
             continue;
         }
         upload_batch(c, hb);
@@ -3200,6 +3223,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         else if (wavefloat)
             waveform_candidates_floating::run(c, 0, n / unit, unit, wavefloat->weight, wavefloat->anarchy,
                                               wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
+        else if (wavescan)
+            waveform_candidates_timescan::run(c, 0, n / unit, unit, wavescan->of, wavescan->weight, wavescan->anarchy, sub_wavescan(s0).call);
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3721,6 +3746,81 @@ int kiwi_hip_waveform_candidates_floating_shape(int K, int *candidates_per_workg
     *samples_per_stage = waveform_candidates_floating::kStage;
     *shifts_per_pass = waveform_candidates_floating::shifts_per_pass(K);
     return 0;
+}
+
+// The candidate evaluation under l1norm and l2norm at many origin times from one synthesis of the basis: the combined untapered trace
+// read k samples earlier under the receiver's taper (kiwi_waveform_candidates_timescan.hpp)
+int kiwi_hip_waveform_candidates_time_scan(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                           const double *candidates, int outer_norm, const double *receiver_weight, int anarchy,
+                                           int *best_offset, int *best_index, double *best_misfit, int *status, double *cand_misfit,
+                                           int *cand_offset, double *misfit, float *slot_misfit, float *slot_norm, float *rows)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->wavecand_scan_ms) t = 0.f;
+    const waveform_candidates_timescan::Call cl{ candidates, ncand, outer_norm, best_offset, best_index, best_misfit, status, cand_misfit,
+                                                 cand_offset, misfit, slot_misfit, slot_norm, rows };
+    waveform_candidates_timescan::run(c, isrc0, ngroup, K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, cl);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_waveform_candidates_time_scan_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece, int k0,
+                                                  int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                  const double *receiver_weight, int anarchy, int *best_offset, int *best_index,
+                                                  double *best_misfit, int *status, double *cand_misfit, int *cand_offset, double *misfit,
+                                                  float *slot_misfit, float *slot_norm, float *rows)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
+        return fail(c, "waveform_candidates_time_scan: K = " + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "waveform_candidates_time_scan: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->wavecand_scan_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_scan_ms) t = 0.f;
+    const WaveCandScanCall wavescan{ K, receiver_weight, anarchy,
+                                     waveform_candidates_timescan::Call{ candidates, ncand, outer_norm, best_offset, best_index, best_misfit,
+                                                                         status, cand_misfit, cand_offset, misfit, slot_misfit, slot_norm, rows },
+                                     timescan::Offsets{ k0, kstep, nk } };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &wavescan);
+}
+
+int kiwi_hip_get_waveform_candidates_time_scan_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_scan_ms[i];
+    return 0;
+}
+
+int kiwi_hip_waveform_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *offsets_per_pass)
+{
+    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis || !candidates_per_workgroup || !samples_per_stage || !offsets_per_pass) return 1;
+    *candidates_per_workgroup = waveform_candidates_timescan::kThreads;
+    *samples_per_stage = waveform_candidates_timescan::kStage;
+    *offsets_per_pass = waveform_candidates_timescan::offsets_per_pass(K);
+    return 0;
+}
+
+// where the `rows` array of the scan keeps what: S = max |k|, the floats of one basis source's rows, and per misfit slot where its
+// wlen + 2 S samples begin (extended sample e at row_offset[slot] + S + e)
+int kiwi_hip_waveform_candidates_time_scan_rows(kiwi_hip_ctx *c, int k0, int kstep, int nk, int *shift_halo, int *row_stride, int *row_offset)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    if (!shift_halo || !row_stride) throw std::runtime_error("waveform_candidates_time_scan: null argument");
+    refusing("waveform_candidates_time_scan", [&] { timescan::check_setup(c, k0, kstep, nk); });
+    const timescan::Offsets of{ k0, kstep, nk };
+    std::vector<int> ofs;
+    const size_t n = waveform_candidates_timescan::row_stride(c, of.max_abs(), &ofs);
+    if (n > 0x7fffffffULL) throw std::runtime_error("waveform_candidates_time_scan: a source's rows do not fit an int");
+    *shift_halo = of.max_abs();
+    *row_stride = (int)n;
+    if (row_offset) std::copy(ofs.begin(), ofs.begin() + c->nmis, row_offset);
+    return 0;
+    GUARD_END(c)
 }
 
 // The candidate evaluation at many origin times from one synthesis of the basis (kiwi_linfit_candidates_timescan.hpp).  The free fit

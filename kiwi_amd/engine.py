@@ -34,6 +34,9 @@ SpectralCandidateScan = collections.namedtuple("SpectralCandidateScan", "best_in
 WaveformCandidateScan = collections.namedtuple("WaveformCandidateScan", "best_index best_misfit status misfit slot_misfit slot_norm")
 WaveformCandidateFloatingScan = collections.namedtuple("WaveformCandidateFloatingScan",
                                                        "best_index best_misfit status best_shift misfit cand_shift slot_misfit slot_norm")
+WaveformCandidateTimeScan = collections.namedtuple("WaveformCandidateTimeScan",
+                                                   "best_offset best_index best_misfit status cand_misfit cand_offset misfit slot_misfit "
+                                                   "slot_norm rows shift_halo row_offset")
 WideFit = collections.namedtuple("WideFit", "coef misfit status pivot_min normal by_receiver npositive nsolves")
 
 GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int32), ("wfrac", np.float32),
@@ -1315,6 +1318,106 @@ class Engine:
         kernels, downloads); the host's tables of a chunk and their upload lie between the first two, in neither."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_waveform_candidates_floating_ms(self.h, _fp(ms)), "get_waveform_candidates_floating_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ l1norm / l2norm candidates at many origin times (kiwi_hip_waveform_candidates_time_scan)
+    def waveform_candidates_time_scan_shape(self, K):
+        """(candidates per workgroup, extended samples per LDS stage, offsets per pass) of `waveform_candidates_time_scan` for K
+        basis sources; needs no device."""
+        c, s, j = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_waveform_candidates_time_scan_shape(int(K), _ip(c), _ip(s), _ip(j)):
+            raise KiwiHipError("waveform_candidates_time_scan: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(s[0]), int(j[0])
+
+    def waveform_candidates_time_scan_rows(self, k0, kstep, nk):
+        """The layout of the `rows` array of `waveform_candidates_time_scan` for these offsets: (S = max |k|, floats per basis
+        source, row_offset[nmis]); extended sample e of slot m lies at row_offset[m] + S + e."""
+        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+        S, stride, ofs = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(max(nmis, 1), np.int32)
+        self._ck(self.L.kiwi_hip_waveform_candidates_time_scan_rows(self.h, int(k0), int(kstep), int(nk), _ip(S), _ip(stride), _ip(ofs)),
+                 "waveform_candidates_time_scan")
+        return int(S[0]), int(stride[0]), ofs[:nmis].copy()
+
+    def _waveform_candidate_time_scan_arrays(self, ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, cand_misfit, cand_offset,
+                                             misfit, slot_misfit, rows):
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        K, ng, nk = int(K), int(ngroup), int(nk)
+        if not 1 <= K <= self.linear_fit_max_basis():
+            raise KiwiHipError("waveform_candidates_time_scan: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != K:
+            raise KiwiHipError("waveform_candidates_time_scan: candidates must be [ncand, K = %d]" % K)
+        nc, nrec = len(x), len(self.components)
+        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+        w = None
+        if receiver_weights is not None:
+            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        nj = max(nk, 0)                              # (a bad nk is refused by the library, by name)
+        S, row_offset, rows_a = 0, None, None
+        if rows:
+            S, stride, row_offset = self.waveform_candidates_time_scan_rows(k0, kstep, nk)
+            rows_a = np.zeros((ng, K, stride), np.float32)
+        out = WaveformCandidateTimeScan(np.zeros(ng, np.int32), np.zeros((ng, nj), np.int32), np.zeros((ng, nj)), np.zeros(ng, np.int32),
+                                        np.zeros((ng, nc)) if cand_misfit else None, np.zeros((ng, nc), np.int32) if cand_offset else None,
+                                        np.zeros((ng, nj, nc)) if misfit else None,
+                                        np.zeros((ng, nj, nc, nmis), np.float32) if slot_misfit else None,
+                                        np.zeros((ng, nmis), np.float32) if slot_misfit else None, rows_a, S, row_offset)
+        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
+        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
+        ip = lambda a: None if a is None else _ip(a)                            # noqa: E731
+        tail = (int(k0), int(kstep), nk, nc, dp(x), code, dp(w))
+        outs = lambda: (_ip(out.best_offset), _ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.cand_misfit),      # noqa: E731
+                        ip(out.cand_offset), dp(out.misfit), fp(out.slot_misfit), fp(out.slot_norm), fp(out.rows))
+        return tail, out, outs, (x, w)
+
+    def waveform_candidates_time_scan(self, isrc0, ngroup, K, k0, kstep, nk, candidates, outer_norm="l1norm", receiver_weights=None,
+                                      anarchy=False, cand_misfit=True, cand_offset=True, misfit=False, slot_misfit=False, rows=False):
+        """`waveform_candidates` at the nk origin-time offsets k0 + j kstep samples from ONE synthesis of the basis
+        (kiwi_hip_waveform_candidates_time_scan): the combined untapered trace of a candidate is read k samples earlier under the
+        receiver's fixed taper, against the tapered reference.  Returns a `WaveformCandidateTimeScan`: best_offset[ngroup] (an index j;
+        -1: none), best_index[ngroup, nk], best_misfit[ngroup, nk], status[ngroup], cand_misfit and cand_offset[ngroup, ncand] (per
+        candidate the first smallest misfit over the offsets and its index), misfit[ngroup, nk, ncand] (misfit=True),
+        slot_misfit[ngroup, nk, ncand, nmis] and slot_norm[ngroup, nmis] float32 (slot_misfit=True: with nk x ncand read as sources
+        what `outer_misfits_slots` takes), rows[ngroup, K, row_stride] with shift_halo and row_offset (rows=True: the folded, scaled,
+        untapered rows of the basis sources, `waveform_candidates_time_scan_rows`).  Offset 0 agrees with `waveform_candidates` to
+        rounding, not bit for bit (this call combines, then tapers)."""
+        tail, out, outs, keep = self._waveform_candidate_time_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights,
+                                                                          cand_misfit, cand_offset, misfit, slot_misfit, rows)
+        self._ck(self.L.kiwi_hip_waveform_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0, *outs()),
+                 "waveform_candidates_time_scan")
+        return out
+
+    def waveform_candidates_time_scan_params(self, sourcetype, params, K, k0, kstep, nk, candidates, outer_norm="l1norm",
+                                             receiver_weights=None, anarchy=False, cand_misfit=True, cand_offset=True, misfit=False,
+                                             slot_misfit=False, rows=False, piece=0):
+        """`waveform_candidates_time_scan` for a parameter list of any length (kiwi_hip_waveform_candidates_time_scan_params), cut
+        into pieces and over devices as `waveform_candidates_params` cuts it.  Afterwards the engine holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("waveform_candidates_time_scan: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("waveform_candidates_time_scan: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        tail, out, outs, keep = self._waveform_candidate_time_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights,
+                                                                          cand_misfit, cand_offset, misfit, slot_misfit, rows)
+        try:
+            self._ck(self.L.kiwi_hip_waveform_candidates_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
+                                                                          1 if anarchy else 0, *outs()), "waveform_candidates_time_scan")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def waveform_candidates_time_scan_ms(self):
+        """HIP-event durations [ms] of the last `waveform_candidates_time_scan`: (evaluation, the rows and scan kernels, the fold
+        kernels, downloads); the host's tables of a chunk and their upload lie between the first two, in neither."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_waveform_candidates_time_scan_ms(self.h, _fp(ms)), "get_waveform_candidates_time_scan_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)

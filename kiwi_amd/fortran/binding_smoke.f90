@@ -54,6 +54,10 @@ program binding_smoke
     if (kiwi_hip_waveform_candidates_floating_shape( 6_c_int, per_group, per_stage, per_pass ) /= 0) stop 25
     if (per_group < 64 .or. per_stage < 1 .or. per_pass < 1) stop 26
 
+    ! and of their scan over origin times: the offsets a lane holds accumulators for at once
+    if (kiwi_hip_waveform_candidates_time_scan_shape( 6_c_int, per_group, per_stage, per_pass ) /= 0) stop 27
+    if (per_group < 64 .or. per_stage < 1 .or. per_pass < 8) stop 28
+
     ! the joint bootstrap of a candidate search: candidates per workgroup, draws per tile, the most receivers its LDS holds
     if (kiwi_hip_linear_fit_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 15
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 16

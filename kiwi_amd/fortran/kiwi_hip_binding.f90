@@ -890,6 +890,66 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, samples_per_stage, shifts_per_pass
         end function
 
+        ! the candidate evaluation under l1norm / l2norm at many origin times: kiwi_hip_waveform_candidates x kiwi_hip_time_scan
+        integer(c_int) function kiwi_hip_waveform_candidates_time_scan( ctx, isrc0, ngroup, k, k0, kstep, nk, ncand, &
+                candidates, outer_norm, receiver_weight, anarchy, best_offset, best_index, best_misfit, status, cand_misfit, &
+                cand_offset, misfit, slot_misfit, slot_norm, rows ) bind(C, name='kiwi_hip_waveform_candidates_time_scan')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, k0, kstep, nk, ncand, outer_norm, anarchy      ! isrc0 0-based; k0 + j kstep
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            integer(c_int), intent(out) :: best_offset(*) ! (ngroup): 0-based index of the best offset, -1 if none
+            integer(c_int), intent(out) :: best_index(*)  ! (nk, ngroup): 0-based candidate, -1 if none
+            real(c_double), intent(out) :: best_misfit(*) ! (nk, ngroup)
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: cand_misfit             ! c_loc of real(c_double) (ncand, ngroup), or c_null_ptr
+            type(c_ptr), value :: cand_offset             ! c_loc of integer(c_int) (ncand, ngroup), or c_null_ptr; with cand_misfit
+            type(c_ptr), value :: misfit                  ! c_loc of real(c_double) (ncand, nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_misfit             ! c_loc of real(c_float) (nmis, ncand, nk, ngroup), or c_null_ptr
+            type(c_ptr), value :: slot_norm               ! c_loc of real(c_float) (nmis, ngroup), or c_null_ptr
+            type(c_ptr), value :: rows                    ! c_loc of real(c_float) (row_stride, k, ngroup), or c_null_ptr
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_time_scan_params( ctx, sourcetype, ngroup, k, params, piece, k0, &
+                kstep, nk, ncand, candidates, outer_norm, receiver_weight, anarchy, best_offset, best_index, best_misfit, status, &
+                cand_misfit, cand_offset, misfit, slot_misfit, slot_norm, rows ) &
+                bind(C, name='kiwi_hip_waveform_candidates_time_scan_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, k0, kstep, nk, ncand, outer_norm, anarchy
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*)
+            type(c_ptr), value :: receiver_weight
+            integer(c_int), intent(out) :: best_offset(*), best_index(*), status(*)
+            real(c_double), intent(out) :: best_misfit(*)
+            type(c_ptr), value :: cand_misfit, cand_offset, misfit, slot_misfit, slot_norm, rows      ! as in the call above
+        end function
+
+        integer(c_int) function kiwi_hip_get_waveform_candidates_time_scan_ms( ctx, ms ) &
+                bind(C, name='kiwi_hip_get_waveform_candidates_time_scan_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, rows + scan kernel, fold kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_waveform_candidates_time_scan_shape( k, candidates_per_workgroup, samples_per_stage, &
+                offsets_per_pass ) bind(C, name='kiwi_hip_waveform_candidates_time_scan_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, samples_per_stage, offsets_per_pass
+        end function
+
+        ! the layout of `rows`: S = max |offset|, floats per basis source, where each misfit slot's wlen + 2 S samples begin
+        integer(c_int) function kiwi_hip_waveform_candidates_time_scan_rows( ctx, k0, kstep, nk, shift_halo, row_stride, &
+                row_offset ) bind(C, name='kiwi_hip_waveform_candidates_time_scan_rows')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: k0, kstep, nk
+            integer(c_int), intent(out) :: shift_halo, row_stride
+            type(c_ptr), value :: row_offset              ! c_loc of integer(c_int) (nmis), or c_null_ptr
+        end function
+
         integer(c_int) function kiwi_hip_effective_cpus() bind(C, name='kiwi_hip_effective_cpus')
             import :: c_int
         end function

@@ -398,3 +398,41 @@ def scan_double_couples_waveform_floating(engine, sourcetype, rows, strikes, dip
                 bm[g], bi[g] = bv, np.where(bv == bv, ix, -1)
         out["boot_misfit"], out["boot_index"] = bm, bi
     return out
+
+
+def scan_double_couples_waveform_time_scan(engine, sourcetype, rows, strikes, dips, rakes, moment, k0, kstep, nk, outer_norm="l1norm",
+                                           unit=1e18, receiver_weights=None, anarchy=False, piece=0, cube=False, slot_misfit=False):
+    """`scan_double_couples_waveform` at the nk origin times (k0 + j kstep) dt later than the rows' own, from the SIX syntheses of
+    a row (`Engine.waveform_candidates_time_scan_params`): the best double couple, depth and origin time under l1norm inside and
+    outside.  The engine's misfit method is l1norm (or l2norm); a receiver with a misfit filter is refused.  moment [N m] is a
+    number or a sequence (mechanisms x moments, the moment fastest); moment=None is refused as in
+    `scan_double_couples_waveform`.  Returns a dict: strike, dip, rake, moment, misfit [N] of the best (candidate, offset) (NaN
+    where there is none), offset [N] its index j (-1: none) and time_shift [N] = (k0 + j kstep) dt in seconds, index [N] the
+    candidate's row (-1: none), status [N] (0 evaluated, 1 no receiver counts, 2 the row failed to discretise), offsets_misfit
+    [N, nk] the best misfit at every offset, scan: the `WaveformCandidateTimeScan`; cube=True adds cube [N, nk, ns, nd, nr]
+    ([N, nk, ns, nd, nr, nmoment] where moment is a sequence), every candidate's misfit at every offset."""
+    if moment is None:
+        raise KiwiHipError("scan_double_couples_waveform_time_scan: moment=None (the best moment per mechanism) has no closed form under "
+                           "l1norm; give a moment, or a sequence of moments as a further axis of candidates")
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    s, d, r = list(strikes), list(dips), list(rakes)
+    moments = np.atleast_1d(np.asarray(moment, np.float64))
+    mech, sdr = double_couple_candidates(s, d, r, 1.0)
+    cand = (mech[:, None, :] * (moments / float(unit))[None, :, None]).reshape(-1, 6)
+    scan = engine.waveform_candidates_time_scan_params(sourcetype, elementary_params(sourcetype, p, unit), 6, k0, kstep, nk, cand,
+                                                       outer_norm=outer_norm, receiver_weights=receiver_weights, anarchy=anarchy,
+                                                       cand_misfit=False, cand_offset=False, misfit=cube, slot_misfit=slot_misfit, piece=piece)
+    has = scan.best_offset >= 0
+    jb = np.where(has, scan.best_offset, 0)
+    n = np.arange(len(p))
+    index = np.where(has, scan.best_index[n, jb], -1)
+    at = np.where(has, index, 0)
+    pick = np.where(has[:, None], sdr[at // len(moments)], np.nan)
+    out = dict(strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=np.where(has, moments[at % len(moments)], np.nan),
+               misfit=np.where(has, scan.best_misfit[n, jb], np.nan), offset=scan.best_offset,
+               time_shift=np.where(has, (int(k0) + jb * int(kstep)) * float(engine.dt), np.nan), index=index, status=scan.status,
+               offsets_misfit=scan.best_misfit, scan=scan)
+    if cube:
+        shape = (len(p), int(nk), len(s), len(d), len(r)) + ((len(moments),) if np.ndim(moment) else ())
+        out["cube"] = scan.misfit.reshape(shape)
+    return out

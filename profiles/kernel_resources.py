@@ -5,11 +5,12 @@ linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation, 
 evaluation's time scan (both kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp), of
 its joint bootstrap (kiwi_linfit_candidates_bootstrap.hpp) and
 under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), the time-domain norms (kiwi_waveform_candidates.hpp) and the
-floating time-domain norms (kiwi_waveform_candidates_floating.hpp), from the
+floating time-domain norms (kiwi_waveform_candidates_floating.hpp) and the time-domain norms at many origin times
+(kiwi_waveform_candidates_timescan.hpp), from the
 compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
 --text adds the kernels' text sizes in bytes (accumulate families: `make co`, the symbol sizes of the device code object).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating|waveform_candidates_timescan]"""
 import json
 import os
 import re
@@ -23,7 +24,7 @@ FAMILIES = {1: "direct", 2: "grouped", 3: "multi", 4: "cell"}
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::").replace("void linfit_candidates_bootstrap::", "linfit_candidates_bootstrap::").replace("void spectral_candidates::", "spectral_candidates::").replace("void waveform_candidates::", "waveform_candidates::").replace("void waveform_candidates_floating::", "waveform_candidates_floating::") for o in out]
+    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::").replace("void linfit_candidates_bootstrap::", "linfit_candidates_bootstrap::").replace("void spectral_candidates::", "spectral_candidates::").replace("void waveform_candidates::", "waveform_candidates::").replace("void waveform_candidates_floating::", "waveform_candidates_floating::").replace("void waveform_candidates_timescan::", "waveform_candidates_timescan::") for o in out]
 
 
 KEYS = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"),
@@ -46,7 +47,8 @@ def collect_outer():
                                 ("_ZN26linfit_candidates_floating", "linfit_candidates_floating"),
                                 ("_ZN27linfit_candidates_bootstrap", "linfit_candidates_bootstrap"),
                                 ("_ZN19spectral_candidates", "spectral_candidates"), ("_ZN19waveform_candidates", "waveform_candidates"),
-                                ("_ZN28waveform_candidates_floating", "waveform_candidates_floating")):
+                                ("_ZN28waveform_candidates_floating", "waveform_candidates_floating"),
+                                ("_ZN28waveform_candidates_timescan", "waveform_candidates_timescan")):
                 if m.group(1).startswith(prefix):
                     cur = {"family": fam, "arith": "exact", "mangled": m.group(1)}
                     rows.append(cur)
