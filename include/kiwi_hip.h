@@ -961,6 +961,54 @@ int kiwi_hip_waveform_candidates_time_scan_shape(int K, int *candidates_per_work
  * row_offset [nmis] (or NULL) where each misfit slot's wlen + 2 S samples begin */
 int kiwi_hip_waveform_candidates_time_scan_rows(kiwi_hip_ctx *ctx, int k0, int kstep, int nk, int *shift_halo, int *row_stride,
                                                 int *row_offset);
+/* ---- the JOINT BOOTSTRAP of a WAVEFORM candidate search (l1norm or l2norm inside) over group (location), origin time and candidate
+ * (mechanism) on the device (kiwi_amd/csrc/kiwi_waveform_candidates_bootstrap.hpp): the [candidate][slot] array never leaves the
+ * device.  Nothing new is defined.  Groups, K (1 .. 8), candidates [ncand][K], receiver_weight, anarchy and the offsets k0 + j kstep,
+ * j < nk, are kiwi_hip_waveform_candidates_time_scan's (nk = 1 with k0 = 0 is the plain case: that call's offset 0, which is not
+ * kiwi_hip_waveform_candidates bit for bit, see there); draw_weights [ndraw][nrec] and outer_norm are kiwi_hip_outer_misfits'.  The
+ * context's method must be l1norm or l2norm.  There is no free scale.
+ * The equality that defines every output: call kiwi_hip_waveform_candidates_time_scan on the same context with the same arguments,
+ * slot_misfit and slot_norm requested; read slot_misfit [ngroup][nk][ncand][nmis] as nsrc = ngroup nk ncand sources of nmis slots,
+ * slot_receiver[m] the receiver of slot m, the norm row of group g repeated for each of its sources; call kiwi_hip_outer_misfits
+ * with the same outer_norm, receiver_weight, anarchy and draw_weights.  Then
+ *   best_value  [ndraw]    is that call's best_value[d], bit for bit
+ *   best_group, best_offset, best_cand [ndraw]   are its best_index[d] taken apart as (g nk + j) ncand + c.  A draw with every source
+ *                          excluded answers NaN and -1, -1, -1 (kiwi_hip_outer_misfits writes index 0 there: the one deliberate
+ *                          difference)
+ *   group_value, group_offset, group_cand [ngroup][ndraw], all three or all NULL: the same per group -- kiwi_hip_outer_misfits on
+ *                          group g's nk ncand sources alone
+ *   status      [ngroup]   the scan call's 0 / 1 / 2; groups with status 1 or 2 have zero norms and are excluded from every draw
+ * Operation by operation (outer_prepare_kernel and outer_draw_kernel of kiwi_outer.hpp): per receiver, its slots ascending,
+ * M = M + mv under outer l1norm, M = M + mv mv with the root behind the slots under l2norm, mv the slot misfit as a float, widened;
+ * N likewise from the slot norms; rw = w_r, under anarchy q = rw / (N != 0 ? N : -1), rw = q where q > 0 or q is NaN, else 0;
+ * a = M rw, b = N rw, both squared under l2norm; ms = ms + a c, ns = ns + b c from zero, receivers ascending, every product and sum
+ * rounded on its own; g = ms / ns, the root under l2norm; a source is excluded where ns > 0 fails or g >= 0 fails.  Order of
+ * "best": excluded last, then the value, then the lowest (g, j, c).  This order is total, so nothing depends on tiles, draw passes,
+ * chunks (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.
+ * Refused with a message that starts with "waveform_candidates_bootstrap:", nothing approximated: everything
+ * kiwi_hip_waveform_candidates_time_scan refuses, a misfit filter included; ndraw < 1; null draw_weights, best_* or status; a
+ * draw_weights or receiver_weight entry that is not finite; more receivers than max_receivers of the shape call (a candidate's
+ * column of all receivers stays in LDS); only some of the three group_* arrays.  Afterwards the context is what
+ * kiwi_hip_waveform_candidates_time_scan leaves: the halo put back, the basis sources evaluated plain. */
+int kiwi_hip_waveform_candidates_bootstrap(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                           const double *candidates, int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                           const double *draw_weights, double *best_value, int *best_group, int *best_offset,
+                                           int *best_cand, int *status, double *group_value, int *group_offset, int *group_cand);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it; the per-draw bests of pieces and devices are combined on the host in the same total order,
+ * with the group index of the whole list */
+int kiwi_hip_waveform_candidates_bootstrap_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                  int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                  const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                                  double *best_value, int *best_group, int *best_offset, int *best_cand, int *status,
+                                                  double *group_value, int *group_offset, int *group_cand);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the rows and scan kernels, ms[2] the fold
+ * kernels, ms[3] bootstrap kernels, ms[4] downloads */
+int kiwi_hip_get_waveform_candidates_bootstrap_ms(kiwi_hip_ctx *ctx, float ms[5]);
+/* how the bootstrap kernel walks its work: *candidates_per_workgroup (one per lane), *draws_per_tile weight rows per LDS tile,
+ * *max_receivers the most receivers its LDS layout holds (the same for every K); answers without a device.  Non-zero for K outside
+ * 1 .. kiwi_hip_linear_fit_max_basis() or a null pointer */
+int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

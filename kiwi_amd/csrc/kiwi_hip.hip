@@ -304,6 +304,8 @@ struct kiwi_hip_ctx {
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
     float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
+    bool wavecand_boot_attr = false;                  // wavecand_bootstrap_kernel may take its dynamic LDS (kiwi_waveform_candidates_bootstrap.hpp)
+    float wavecand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };  // evaluation, rows + scan kernels, fold kernels, bootstrap kernels, downloads of the last kiwi_hip_waveform_candidates_bootstrap
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
     unsigned prepare_gen = 0;                         // counts the runs of prepare(): derived tables kept elsewhere are stale when it moves
     int eik_solver = 0;                               // where the eikonal discretisers solve: 0 host, 1 device (kiwi_hip_set_eikonal_solver; env KIWI_HIP_EIK_DEVICE)
@@ -1565,6 +1567,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_waveform_candidates.hpp"
 #include "kiwi_waveform_candidates_floating.hpp"
 #include "kiwi_waveform_candidates_timescan.hpp"
+#include "kiwi_waveform_candidates_bootstrap.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -2954,6 +2957,9 @@ struct WaveCandFloatCall { int K; const double *weight; int anarchy; waveform_ca
 // (kiwi_hip_waveform_candidates_time_scan_params the same with `wavescan` set: a piece is evaluated by
 // waveform_candidates_timescan::run)
 struct WaveCandScanCall { int K; const double *weight; int anarchy; waveform_candidates_timescan::Call call; timescan::Offsets of; };
+// (kiwi_hip_waveform_candidates_bootstrap_params the same with `waveboot` set: a piece is evaluated by
+// waveform_candidates_bootstrap::run, which folds its per-draw bests into those of the call)
+struct WaveCandBootCall { int K; const double *weight; int anarchy; linfit_candidates_bootstrap::Boot boot; timescan::Offsets of; };
 
 static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                            float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
@@ -2961,7 +2967,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                            const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
                            const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr,
                            const WaveCandCall *wavecand = nullptr, const WaveCandFloatCall *wavefloat = nullptr,
-                           const WaveCandScanCall *wavescan = nullptr)
+                           const WaveCandScanCall *wavescan = nullptr, const WaveCandBootCall *waveboot = nullptr)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
@@ -2980,8 +2986,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
     if (wavecand) waveform_candidates::check_setup(c, wavecand->K, wavecand->call);
     if (wavefloat) waveform_candidates_floating::check_setup(c, wavefloat->K, wavefloat->call);
     if (wavescan) waveform_candidates_timescan::check_setup(c, wavescan->K, wavescan->of, wavescan->call);
+    if (waveboot) waveform_candidates_bootstrap::check_setup(c, waveboot->K, waveboot->of, waveboot->weight, waveboot->boot);
     const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : wavescan ? wavescan->K : 1;            // shards and pieces are whole multiples of it
+    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : wavescan ? wavescan->K : waveboot ? waveboot->K : 1;            // shards and pieces are whole multiples of it
     const int nrec_all = (int)c->recv.size();
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
@@ -3038,6 +3045,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (wavefloating) { mine_wavefloat = *wavefloat; mine_wavefloat.call = wavefloat->call.at(s0 / unit, (int)nmis, nrec_all); }
             const bool wavescanning = wavescan != nullptr;
             const WaveCandScanCall mine_wavescan = wavescanning ? sub_wavescan(s0) : WaveCandScanCall{};
+            const bool wavebooting = waveboot != nullptr;
+            WaveCandBootCall mine_waveboot{};
+            if (wavebooting) { mine_waveboot = *waveboot; mine_waveboot.boot = waveboot->boot.at((size_t)(s0 / unit)); }
             th.push_back(std::async(std::launch::async, [=] {
                 return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
                                        norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
@@ -3046,12 +3056,12 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                                        candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
                                        speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr,
                                        wavecanding ? &mine_wavecand : nullptr, wavefloating ? &mine_wavefloat : nullptr,
-                                       wavescanning ? &mine_wavescan : nullptr);
+                                       wavescanning ? &mine_wavescan : nullptr, wavebooting ? &mine_waveboot : nullptr);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat, wavescan);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat, wavescan, waveboot);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3197,6 +3207,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (wavecand) waveform_candidates::fill_failed(n / unit, (int)nmis, wavecand->call.at(s0 / unit, (int)nmis));
             if (wavefloat) waveform_candidates_floating::fill_failed(n / unit, (int)nmis, nrec_all, wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
             if (wavescan) waveform_candidates_timescan::fill_failed((size_t)(n / unit), nmis, (size_t)wavescan->of.nk, (size_t)unit, scan_rstride, sub_wavescan(s0).call);
+            if (waveboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), waveboot->boot.at((size_t)(s0 / unit)));
             continue;
         }
         upload_batch(c, hb);
@@ -3225,6 +3236,8 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
                                               wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
         else if (wavescan)
             waveform_candidates_timescan::run(c, 0, n / unit, unit, wavescan->of, wavescan->weight, wavescan->anarchy, sub_wavescan(s0).call);
+        else if (waveboot)
+            waveform_candidates_bootstrap::run(c, 0, n / unit, unit, waveboot->of, waveboot->weight, waveboot->anarchy, waveboot->boot.at((size_t)(s0 / unit)));
         else eval_impl(c, 0, n, c->keep_which);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
@@ -3821,6 +3834,73 @@ int kiwi_hip_waveform_candidates_time_scan_rows(kiwi_hip_ctx *c, int k0, int kst
     if (row_offset) std::copy(ofs.begin(), ofs.begin() + c->nmis, row_offset);
     return 0;
     GUARD_END(c)
+}
+
+// The joint bootstrap of a waveform candidate search over group, origin time and candidate (kiwi_waveform_candidates_bootstrap.hpp)
+static const char *const kWaveBootBasis = "waveform_candidates_bootstrap: K = ";
+
+int kiwi_hip_waveform_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int k0, int kstep, int nk, int ncand,
+                                           const double *candidates, int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                           const double *draw_weights, double *best_value, int *best_group, int *best_offset,
+                                           int *best_cand, int *status, double *group_value, int *group_offset, int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    for (float &t : c->wavecand_boot_ms) t = 0.f;
+    for (float &t : c->wavecand_scan_ms) t = 0.f;
+    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
+        throw std::runtime_error(kWaveBootBasis + std::to_string(K) + " basis sources per group; 1 to " +
+                                 std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
+    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
+                                                status, group_value, group_offset, group_cand, 0, nullptr };
+    const timescan::Offsets of{ k0, kstep, nk };
+    waveform_candidates_bootstrap::check_setup(c, K, of, receiver_weight, bt);
+    bt.begin();
+    waveform_candidates_bootstrap::run(c, isrc0, ngroup, K, of, receiver_weight, anarchy, bt);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_waveform_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                  int k0, int kstep, int nk, int ncand, const double *candidates, int outer_norm,
+                                                  const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                                  double *best_value, int *best_group, int *best_offset, int *best_cand, int *status,
+                                                  double *group_value, int *group_offset, int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
+        return fail(c, kWaveBootBasis + std::to_string(K) + " basis sources per group; 1 to " +
+                           std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
+    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
+        return fail(c, "waveform_candidates_bootstrap: need at least one group (and at most INT_MAX sources)");
+    for (float &t : c->wavecand_boot_ms) t = 0.f;
+    for (float &t : c->wavecand_scan_ms) t = 0.f;
+    for (kiwi_hip_ctx *m : c->mates) { for (float &t : m->wavecand_boot_ms) t = 0.f; for (float &t : m->wavecand_scan_ms) t = 0.f; }
+    std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
+    const WaveCandBootCall waveboot{ K, receiver_weight, anarchy,
+                                     linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group,
+                                                                        best_offset, best_cand, status, group_value, group_offset, group_cand, 0, &mu },
+                                     timescan::Offsets{ k0, kstep, nk } };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) waveboot.boot.begin();      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &waveboot);
+}
+
+int kiwi_hip_get_waveform_candidates_bootstrap_ms(kiwi_hip_ctx *c, float ms[5])
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    for (int i = 0; i < 5; i++) ms[i] = c->wavecand_boot_ms[i];
+    return 0;
+}
+
+int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
+{
+    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
+    *candidates_per_workgroup = waveform_candidates_bootstrap::kThreads;
+    *draws_per_tile = waveform_candidates_bootstrap::kTileD;
+    *max_receivers = waveform_candidates_bootstrap::kMaxRec;
+    return 0;
 }
 
 // The candidate evaluation at many origin times from one synthesis of the basis (kiwi_linfit_candidates_timescan.hpp).  The free fit

@@ -307,10 +307,21 @@ static void launch(kiwi_hip_ctx *c, const ScanArgs &a, int ng)
     HIPCHECK(hipGetLastError());
 }
 
+// what a call built on this one (kiwi_waveform_candidates_bootstrap.hpp) adds to every chunk: its device bytes per group, its bound
+// on the groups of a chunk, and its kernels on the chunk's slab and norm rows [(group nk + j)][slot], launched behind the fold kernels
+// and in front of the downloads; their HIP-event time is added to ms[0]
+struct ChunkHook {
+    size_t per_group = 0;
+    int max_groups = std::numeric_limits<int>::max();
+    float *ms = nullptr;
+    virtual void after_fold(int g0, int ng, const float *slab, const float *norm) = 0;
+    virtual ~ChunkHook() = default;
+};
+
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch, on waveform_candidates::run's skeleton inside linfit_timescan::run's
 // halo; adds its HIP-event times to c->wavecand_scan_ms: evaluation (run_chunk), rows + scan kernel, the fold kernels, the downloads
 static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy,
-                const Call &cl)
+                const Call &cl, ChunkHook *hook = nullptr)
 {
     check_setup(c, K, of, cl);
     check_group_range("waveform_candidates_time_scan", c, isrc0, ngroup, K);
@@ -348,7 +359,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     if (nmis > 0) HIPCHECK(hipMemcpyAsync(B.info.p, info.data(), (size_t)nmis * sizeof(SlotInfo), hipMemcpyHostToDevice, c->stream));
     HIPCHECK(hipMemcpyAsync(B.rofs.p, rofs.data(), rofs.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
 
-    const PooledEvents<6> ev(c);                           // (ev[5]: immediately in front of the rows kernel)
+    const PooledEvents<7> ev(c);                           // (ev[5]: immediately in front of the rows kernel; ev[6]: behind the hook)
     std::vector<float> norm_h;
     std::vector<int> ok_h;
     // per group: the rows, and at every offset the slab of slot misfits, the norm factors, the tiles' bests, the outputs
@@ -356,11 +367,12 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
                              (size_t)nk * ((size_t)nmis * cl.ncand * sizeof(float) + (size_t)nmis * sizeof(float) + 2 * sizeof(int) +
                                            ntile * (sizeof(double) + sizeof(int)) + sizeof(double) + sizeof(int) +
                                            (size_t)cl.ncand * ((want_misfit ? sizeof(double) : 0) + (cl.slot_misfit ? (size_t)nmis * sizeof(float) : 0))) +
-                             (size_t)cl.ncand * ((cl.cand_misfit ? sizeof(double) : 0) + (cl.cand_offset ? sizeof(int) : 0)) + 2 * sizeof(int);
+                             (size_t)cl.ncand * ((cl.cand_misfit ? sizeof(double) : 0) + (cl.cand_offset ? sizeof(int) : 0)) + 2 * sizeof(int) +
+                             (hook ? hook->per_group : 0);
     int g0 = 0;
     while (g0 < ngroup) {
         // (at most 65535 / nk groups: groups x offsets is a grid dimension of the fold, groups x passes one of the scan)
-        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 1, per_group, K * (65535 / nk));
+        const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 1, per_group, K * std::min(65535 / nk, hook ? hook->max_groups : 65535));
         const int s0 = isrc0 + g0 * K;
         HIPCHECK(hipEventRecord(ev[0], c->stream));
         run_chunk(c, s0, ng * K, 0);
@@ -415,6 +427,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
                            B.status.p);
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipEventRecord(ev[3], c->stream));
+        if (hook) hook->after_fold(g0, ng, B.slab.p, B.norm.p);
+        HIPCHECK(hipEventRecord(ev[6], c->stream));
         const Call o = cl.at((size_t)g0, (size_t)nmis, (size_t)nk, (size_t)K, rstride);
         auto down = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream)); };
         down(o.best_offset, B.best_offset.p, (size_t)ng * sizeof(int));
@@ -434,7 +448,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
         ev.add_elapsed(c->wavecand_scan_ms, 0, 0, 1);
         ev.add_elapsed(c->wavecand_scan_ms, 1, 5, 2);
         ev.add_elapsed(c->wavecand_scan_ms, 2, 2, 3);
-        ev.add_elapsed(c->wavecand_scan_ms, 3, 3, 4);
+        ev.add_elapsed(c->wavecand_scan_ms, 3, 6, 4);
+        if (hook) ev.add_elapsed(hook->ms, 0, 3, 6);
         g0 += ng;
     }
     leave_evaluated(c, isrc0, ngroup * K, 0);              // the plain evaluation of the basis sources -- offset 0 -- was made on the way

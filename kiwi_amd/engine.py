@@ -1420,6 +1420,62 @@ class Engine:
         self._ck(self.L.kiwi_hip_get_waveform_candidates_time_scan_ms(self.h, _fp(ms)), "get_waveform_candidates_time_scan_ms")
         return tuple(float(x) for x in ms)
 
+    # ------------------------------------------------------------------ joint bootstrap of a waveform candidate search (kiwi_hip_waveform_candidates_bootstrap)
+    def waveform_candidates_bootstrap_shape(self, K):
+        """(candidates per workgroup, draws per tile, the most receivers) of the waveform bootstrap kernel for K basis sources; no
+        device needed."""
+        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_waveform_candidates_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
+            raise KiwiHipError("waveform_candidates_bootstrap: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(t[0]), int(r[0])
+
+    def waveform_candidates_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, k0=0, kstep=1, nk=1, outer_norm="l1norm",
+                                      receiver_weights=None, anarchy=False, per_group=False):
+        """The bootstrap over the receivers of a waveform candidate search (l1norm or l2norm inside), joint over group, origin-time
+        offset and candidate, on the device (kiwi_hip_waveform_candidates_bootstrap): what
+        `waveform_candidates_time_scan(..., slot_misfit=True)` followed by `outer_misfits_slots` with `draw_weights[ndraw, nrec]`
+        answers, bit for bit, without the [candidate, slot] array leaving the device.  Returns a `CandidateBootstrap`:
+        best_value[ndraw], best_group, best_offset, best_cand[ndraw] (NaN and -1 where every source of a draw is excluded),
+        status[ngroup]; per_group=True adds group_value, group_offset and group_cand[ngroup, ndraw], the same per group.  A row of
+        ones as draw 0 gives the plain winner."""
+        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
+                                                           "waveform_candidates_bootstrap")
+        self._ck(self.L.kiwi_hip_waveform_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *head,
+                                                               1 if anarchy else 0, *tail()), "waveform_candidates_bootstrap")
+        return out
+
+    def waveform_candidates_bootstrap_params(self, sourcetype, params, K, candidates, draw_weights, k0=0, kstep=1, nk=1,
+                                             outer_norm="l1norm", receiver_weights=None, anarchy=False, per_group=False, piece=0):
+        """`waveform_candidates_bootstrap` for a parameter list of any length, cut into pieces and over the devices at group
+        boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine holds
+        the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("waveform_candidates_bootstrap: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("waveform_candidates_bootstrap: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
+                                                           "waveform_candidates_bootstrap")
+        try:
+            self._ck(self.L.kiwi_hip_waveform_candidates_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep),
+                                                                          int(nk), *head, 1 if anarchy else 0, *tail()),
+                     "waveform_candidates_bootstrap")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def waveform_candidates_bootstrap_ms(self):
+        """HIP-event durations [ms] of the last `waveform_candidates_bootstrap`: (evaluation, the rows and scan kernels, the fold
+        kernels, bootstrap kernels, downloads)."""
+        ms = np.zeros(5, np.float32)
+        self._ck(self.L.kiwi_hip_get_waveform_candidates_bootstrap_ms(self.h, _fp(ms)), "get_waveform_candidates_bootstrap_ms")
+        return tuple(float(x) for x in ms)
+
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)
     def linear_fit_candidates_time_scan_shape(self, K):
         """(candidates per workgroup, receivers per LDS stage) of the candidate-scan kernel for K basis sources."""
@@ -1512,18 +1568,19 @@ class Engine:
             raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
         return int(c[0]), int(t[0]), int(r[0])
 
-    def _candidate_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group):
+    def _candidate_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
+                                    name="linear_fit_candidates_bootstrap"):
         code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
         if code is None:
             raise KiwiHipError("unknown norm method: %s" % outer_norm)
         w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
         x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
         if x.ndim != 2 or x.shape[1] != int(K):
-            raise KiwiHipError("linear_fit_candidates_bootstrap: candidates must be [ncand, K = %d]" % int(K))
+            raise KiwiHipError("%s: candidates must be [ncand, K = %d]" % (name, int(K)))
         nrec = len(self.components)
         dw = np.ascontiguousarray(np.asarray(draw_weights, np.float64))
         if dw.ndim != 2 or dw.shape[1] != nrec:
-            raise KiwiHipError("linear_fit_candidates_bootstrap: draw_weights must be [ndraw, %d]" % nrec)
+            raise KiwiHipError("%s: draw_weights must be [ndraw, %d]" % (name, nrec))
         ng, nd = int(ngroup), len(dw)
         grp = (ng, nd) if per_group else None
         out = CandidateBootstrap(np.zeros(nd), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros(ng, np.int32),

@@ -62,6 +62,10 @@ program binding_smoke
     if (kiwi_hip_linear_fit_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 15
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 16
 
+    ! and of a waveform candidate search: a candidate's fp64 column per receiver stays in LDS
+    if (kiwi_hip_waveform_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 29
+    if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 30
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

@@ -436,3 +436,42 @@ def scan_double_couples_waveform_time_scan(engine, sourcetype, rows, strikes, di
         shape = (len(p), int(nk), len(s), len(d), len(r)) + ((len(moments),) if np.ndim(moment) else ())
         out["cube"] = scan.misfit.reshape(shape)
     return out
+
+
+def bootstrap_double_couples_waveform(engine, sourcetype, rows, strikes, dips, rakes, moment, draw_weights, k0=0, kstep=1, nk=1,
+                                      outer_norm="l1norm", unit=1e18, receiver_weights=None, anarchy=False, piece=0, per_group=False):
+    """The bootstrap over the receivers of `scan_double_couples_waveform_time_scan`, joint over the rows of rows[N, nparams]
+    (locations), the origin-time offsets (k0 + j kstep) dt, j < nk, and the grid strikes x dips x rakes (x moments), in ONE call on
+    the device (`Engine.waveform_candidates_bootstrap_params`): l1norm inside and outside under resampling, the slot misfits never
+    leaving the device.  The engine's misfit method is l1norm (or l2norm).  moment [N m] is a number or a sequence (mechanisms x
+    moments, the moment fastest); moment=None is refused as in `scan_double_couples_waveform`.  draw_weights [ndraw, nrec] as
+    `engine.bootstrap_draw_weights` makes them; put a row of ones in front to get the plain winner as draw 0.  Returns a dict of
+    arrays [ndraw]: row (index into `rows`), strike, dip, rake, moment, offset (index j), time_shift [s], index (the candidate's
+    row) and misfit of the best (row, offset, candidate) of every draw -- -1 and NaN for a draw that excludes everything --; status
+    [N]; boot: the `CandidateBootstrap`.  per_group=True adds rows_strike, rows_dip, rows_rake, rows_moment, rows_offset, rows_index
+    and rows_misfit [N, ndraw]: the same per row, the depth profile under resampling."""
+    if moment is None:
+        raise KiwiHipError("bootstrap_double_couples_waveform: moment=None (the best moment per mechanism) has no closed form under "
+                           "l1norm; give a moment, or a sequence of moments as a further axis of candidates")
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    moments = np.atleast_1d(np.asarray(moment, np.float64))
+    mech, sdr = double_couple_candidates(list(strikes), list(dips), list(rakes), 1.0)
+    cand = (mech[:, None, :] * (moments / float(unit))[None, :, None]).reshape(-1, 6)
+    boot = engine.waveform_candidates_bootstrap_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, draw_weights, k0, kstep,
+                                                       nk, outer_norm=outer_norm, receiver_weights=receiver_weights, anarchy=anarchy,
+                                                       per_group=per_group, piece=piece)
+
+    def picked(cand_index):
+        has = cand_index >= 0
+        at = np.where(has, cand_index, 0)
+        return np.where(has[..., None], sdr[at // len(moments)], np.nan), np.where(has, moments[at % len(moments)], np.nan)
+    pick, mom = picked(boot.best_cand)
+    has = boot.best_offset >= 0
+    out = dict(row=boot.best_group, strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=mom, offset=boot.best_offset,
+               time_shift=np.where(has, (int(k0) + np.where(has, boot.best_offset, 0) * int(kstep)) * float(engine.dt), np.nan),
+               index=boot.best_cand, misfit=boot.best_value, status=boot.status, boot=boot)
+    if per_group:
+        pick, mom = picked(boot.group_cand)
+        out.update(rows_strike=pick[..., 0], rows_dip=pick[..., 1], rows_rake=pick[..., 2], rows_moment=mom, rows_offset=boot.group_offset,
+                   rows_index=boot.group_cand, rows_misfit=boot.group_value)
+    return out
