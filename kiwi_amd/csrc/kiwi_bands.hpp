@@ -562,4 +562,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Out &out)
     leave_evaluated(c, isrc0, nsrc, 0);                    // the context's own method and filters were evaluated on the way
 }
 
+// kiwi_hip_band_misfits_for_params piece by piece (PieceCall, kiwi_group_run.hpp): plain sources
+static PieceCall piece_call(const Out &out)
+{
+    return PieceCall{ 1,
+        [](kiwi_hip_ctx *c) { check_setup(c); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { fill_failed((size_t)n, c->bands.size(), (size_t)c->nmis, out.at((size_t)s0, c->bands.size(), (size_t)c->nmis)); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n, out.at((size_t)s0, c->bands.size(), (size_t)c->nmis)); } };
+}
+
 } // namespace bands

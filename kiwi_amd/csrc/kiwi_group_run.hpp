@@ -1,6 +1,7 @@
 // kiwi_group_run.hpp -- the host steps that every call built on run_chunk repeats: the range check, the receiver weights, events
 // from the context's pool, the greedy chunk of whole groups, what an evaluation leaves behind, the groups whose basis failed, the
-// dispatch on the number of basis sources.  Host code only.  Included by kiwi_hip.hip in front of eval_impl and the call headers.
+// dispatch on the number of basis sources, what a _params call does with a piece of its list.  Host code only.  Included by
+// kiwi_hip.hip in front of eval_impl and the call headers.
 
 // f(std::integral_constant<int, k>{}) with k = K for K = 1 .. 7 and k = 8 for everything else (the callers have refused other K)
 template <class F>
@@ -130,3 +131,15 @@ static void for_each_failed_group(const kiwi_hip_ctx *c, int isrc0, int ngroup, 
         if (bad) f(g);
     }
 }
+
+// What a kiwi_hip_*_params call does with a piece of its list; everything else -- shards, pieces, the discretiser ahead of the device,
+// upload, download -- is for_params_impl's, which knows no call by name.  Each call header makes its own (piece_call), from the
+// caller's arrays for the WHOLE list.  One object serves the threads of all shards: the callables change nothing but those arrays.
+// s0 counts from the head of the caller's list, in every shard, so a callable forms call.at(s0 / unit, ...) once; the sizes at()
+// takes -- nmis, the receivers, the bands -- are read from ctx, which is prepared and has every mate's settings.
+struct PieceCall {
+    int unit;                                                   // sources per group: shards and pieces are whole multiples of it
+    std::function<void(kiwi_hip_ctx *ctx)> check;               // the call's check_setup, on every context the call reaches
+    std::function<void(kiwi_hip_ctx *ctx, int s0, int n)> fill_failed;      // the answer for list sources [s0, s0 + n), none of which could be discretised
+    std::function<void(kiwi_hip_ctx *ctx, int s0, int n)> run;  // evaluate list sources [s0, s0 + n): sources 0 .. n - 1 of ctx, just uploaded
+};

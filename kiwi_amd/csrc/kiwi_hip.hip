@@ -29,6 +29,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <future>
 #include <mutex>
 #include <thread>
@@ -1594,6 +1595,35 @@ __global__ __launch_bounds__(256) void read_in_order_kernel(const read_u4 *__res
     if ((x ^ y ^ z ^ w) == 0x9e3779b9u) sink[blockIdx.x] = x;        // (never true for the fill pattern: keeps the loads)
 }
 
+// ---- what the entries of the C section repeat (in front of it: a template cannot have C linkage)
+// what a call says of a bad basis or group count, under its message prefix ("linear_fit: K = ", kCandScanBasis, ...); "" where
+// both are fine.  ngroup: null in the plain calls, whose groups check_group_range checks
+static std::string bad_basis(const char *prefix, int K, int kmax, const int *ngroup = nullptr)
+{
+    if (K < 1 || K > kmax) return prefix + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(kmax) + " are supported";
+    if (ngroup && (*ngroup < 1 || (long long)*ngroup * K > 0x7fffffffLL))
+        return std::string(prefix, std::strchr(prefix, ':')) + ": need at least one group (and at most INT_MAX sources)";
+    return "";
+}
+
+// the timings of the last call of a family: zeroed in front of a call, on the other devices of a multi-device context too where
+// `mates`; handed out by the family's kiwi_hip_get_*_ms
+template <size_t N>
+static void zero_ms(kiwi_hip_ctx *c, float (kiwi_hip_ctx::*ms)[N], bool mates = false)
+{
+    std::fill(c->*ms, c->*ms + N, 0.f);
+    if (mates) for (kiwi_hip_ctx *m : c->mates) std::fill(m->*ms, m->*ms + N, 0.f);
+}
+
+template <size_t N>
+static int get_ms(kiwi_hip_ctx *c, float (kiwi_hip_ctx::*from)[N], float *ms)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (!ms) return fail(c, "null argument");
+    std::copy(c->*from, c->*from + N, ms);
+    return 0;
+}
+
 extern "C" {
 
 int kiwi_hip_init(int device, kiwi_hip_ctx **out)
@@ -2909,98 +2939,54 @@ int kiwi_hip_get_global_misfits_device(kiwi_hip_ctx *c, int isrc0, int nsrc, con
     GUARD_END(c)
 }
 
+// the pieces [first, first + count) of a list of nsrc sources, in list order, each a whole multiple of unit
+static std::vector<std::pair<int, int>> cut_pieces(int nsrc, int piece, int unit, bool eikonal)
+{
+    // (default piece: 128 eikonal solves keep the discretiser team busy for one device evaluation; for the closed-form source types the
+    // host is a few per cent of a piece and larger launches fill the device better -- cfg3, 4096 trials: 31.1 k evals/s at 1024, 32.5 k at 2048)
+    if (piece <= 0) piece = eikonal ? 128 : 2048;
+    if (unit > 1) piece = std::max(unit, piece - piece % unit);
+    // Eikonal types: the LAST piece of the list -- the first one worked on, the one whose discretisation nothing hides -- is cut
+    // into a ramp of an eighth, an eighth, a quarter and half a piece, so that the device starts after an eighth of a piece's
+    // fast-marching solves (one per discretiser thread at the default 128 on 16 CPUs) instead of a whole one (512 cfg4-nukl trials:
+    // 137 ms of the call's 1066 were that wait).
+    std::vector<std::pair<int, int>> pieces;
+    for (int s0 = 0; s0 < nsrc; s0 += piece) pieces.emplace_back(s0, std::min(piece, nsrc - s0));
+    if (eikonal && pieces.size() >= 2 && pieces.back().second / unit >= 8) {
+        const std::pair<int, int> last = pieces.back();
+        pieces.pop_back();
+        const int e = last.second / unit / 8 * unit, q = last.second / unit / 4 * unit, h = last.second - 2 * e - q;
+        pieces.emplace_back(last.first, h);
+        pieces.emplace_back(last.first + h, q);
+        pieces.emplace_back(last.first + h + q, e);
+        pieces.emplace_back(last.first + h + q + e, e);
+    }
+    return pieces;
+}
+
 // make_misfits_for_sources for a whole trial list in one call (seismosizer.py:682-722), host and device overlapped: the
 // list is cut into pieces; while the device evaluates one piece, a second host thread discretises the next.  Per piece
 // the calls are exactly kiwi_hip_set_sources_params + kiwi_hip_eval + kiwi_hip_get_misfits + kiwi_hip_get_source_status,
 // so results do not depend on `piece` (a source's evaluation does not depend on its batch: tests).
-// (kiwi_hip_linear_fit_params goes through the same pieces with `fit` set: the list is then groups of fit->K consecutive basis
-// sources, shards and pieces are cut at group boundaries, and a piece is evaluated by linfit::run instead of eval_impl)
-// (kiwi_hip_band_misfits_for_params the same with `band` set: a piece is evaluated by bands::run, which fills the band arrays)
-struct LinFitCall { int K; const double *weight; int anarchy; linfit::Out out; const linfit::Robust *robust; const linfit::Wide *wide; };
-// (kiwi_hip_time_scan_for_params the same with `scan` set: a piece is evaluated by timescan::run, which fills the scan arrays)
-struct BandCall { bands::Out out; };
-struct ScanCall { timescan::Out out; timescan::Offsets of; };
-// (kiwi_hip_linear_fit_time_scan_params the same with `fitscan` set: groups of K basis sources as for `fit`, a piece is evaluated by
-// linfit_timescan::run)
-struct FitScanCall { int K; const double *weight; int anarchy; linfit_timescan::Out out; timescan::Offsets of; };
-// (kiwi_hip_linear_fit_candidates_params the same with `cand` set: groups of K basis sources as for `fit`, a piece is evaluated by
-// linfit::run with the candidates behind its l2 kernels)
-struct CandCall { int K; const double *weight; int anarchy; linfit::Out out; linfit::Candidates cand; };
-// (kiwi_hip_linear_fit_candidates_time_scan_params the same with `candscan` set: groups of K basis sources as for `fit`, a piece is
-// evaluated by linfit_candidates_timescan::run)
-struct CandScanCall {
-    int K; const double *weight; int anarchy; linfit_timescan::Out out; linfit_candidates_timescan::Scan scan; timescan::Offsets of;
-    CandScanCall at(size_t g, size_t nrec) const
-    {
-        CandScanCall s = *this;
-        s.out = out.at(g, (size_t)K, (size_t)of.nk);
-        s.scan = scan.at(g, (size_t)of.nk, nrec);
-        return s;
-    }
-};
-
-// (kiwi_hip_linear_fit_candidates_floating_params the same with `candfloat` set: groups of K basis sources as for `fit`, a piece is
-// evaluated by linfit_candidates_floating::run)
-struct CandFloatCall { int K; const double *weight; int anarchy; linfit_candidates_floating::Floating fl; };
-// (kiwi_hip_spectral_candidates_params the same with `speccand` set: groups of K basis sources as for `fit`, a piece is evaluated by
-// spectral_candidates::run)
-struct SpecCandCall { int K; const double *weight; int anarchy; spectral_candidates::Call call; };
-// (kiwi_hip_linear_fit_candidates_bootstrap_params the same with `candboot` set: groups of K basis sources as for `fit`, a piece is
-// evaluated by linfit_candidates_bootstrap::run, which folds its per-draw bests into those of the call)
-struct CandBootCall { int K; const double *weight; int anarchy; linfit_candidates_bootstrap::Boot boot; timescan::Offsets of; };
-// (kiwi_hip_waveform_candidates_params the same with `wavecand` set: groups of K basis sources as for `fit`, a piece is evaluated by
-// waveform_candidates::run)
-struct WaveCandCall { int K; const double *weight; int anarchy; waveform_candidates::Call call; };
-// (kiwi_hip_waveform_candidates_floating_params the same with `wavefloat` set: a piece is evaluated by
-// waveform_candidates_floating::run)
-struct WaveCandFloatCall { int K; const double *weight; int anarchy; waveform_candidates_floating::Call call; };
-// (kiwi_hip_waveform_candidates_time_scan_params the same with `wavescan` set: a piece is evaluated by
-// waveform_candidates_timescan::run)
-struct WaveCandScanCall { int K; const double *weight; int anarchy; waveform_candidates_timescan::Call call; timescan::Offsets of; };
-// (kiwi_hip_waveform_candidates_bootstrap_params the same with `waveboot` set: a piece is evaluated by
-// waveform_candidates_bootstrap::run, which folds its per-draw bests into those of the call)
-struct WaveCandBootCall { int K; const double *weight; int anarchy; linfit_candidates_bootstrap::Boot boot; timescan::Offsets of; };
-
-static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
-                           float *misfit, float *norm, float *global, int *status, const LinFitCall *fit, const BandCall *band = nullptr,
-                           const ScanCall *scan = nullptr, const FitScanCall *fitscan = nullptr, const CandCall *cand = nullptr,
-                           const CandScanCall *candscan = nullptr, const CandFloatCall *candfloat = nullptr,
-                           const SpecCandCall *speccand = nullptr, const CandBootCall *candboot = nullptr,
-                           const WaveCandCall *wavecand = nullptr, const WaveCandFloatCall *wavefloat = nullptr,
-                           const WaveCandScanCall *wavescan = nullptr, const WaveCandBootCall *waveboot = nullptr)
+// Every kiwi_hip_*_params call goes through the same pieces with a PieceCall of its own (kiwi_group_run.hpp): the list is then
+// groups of call.unit consecutive sources, shards and pieces are cut at group boundaries, and a piece is evaluated by call.run in
+// place of eval_impl.  status, misfit, norm, global: the discretiser's status and the arrays of kiwi_hip_get_misfits, each may be
+// null (the other calls' arrays are in their PieceCall).  base: where this list begins in the caller's -- a shard's offset; params and
+// the four arrays come re-based
+static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece, const PieceCall &call,
+                           int *status = nullptr, float *misfit = nullptr, float *norm = nullptr, float *global = nullptr, int base = 0)
 {
     GUARD_BEGIN
     const int np = nparams_any(sourcetype);
     if (np < 0) throw std::runtime_error("source type not supported by the host discretiser");
     if (nsrc < 1) throw std::runtime_error("need at least one source");
     HIPCHECK(hipSetDevice(c->device));
-    if (fit) linfit::check_setup(c, fit->K, fit->out, fit->robust, fit->wide);
-    if (band) bands::check_setup(c);
-    if (scan) timescan::check_setup(c, scan->of.k0, scan->of.kstep, scan->of.nk);
-    if (fitscan) linfit_timescan::check_setup(c, fitscan->K, fitscan->of, fitscan->out);
-    if (cand) { linfit::check_candidates(cand->cand, cand->K); linfit::check_setup(c, cand->K, cand->out); }
-    if (candscan) linfit_candidates_timescan::check_setup(c, candscan->K, candscan->of, candscan->out, candscan->scan);
-    if (candfloat) linfit_candidates_floating::check_setup(c, candfloat->K, candfloat->fl);
-    if (speccand) spectral_candidates::check_setup(c, speccand->K, speccand->call);
-    if (candboot) linfit_candidates_bootstrap::check_setup(c, candboot->K, candboot->of, candboot->weight, candboot->boot);
-    if (wavecand) waveform_candidates::check_setup(c, wavecand->K, wavecand->call);
-    if (wavefloat) waveform_candidates_floating::check_setup(c, wavefloat->K, wavefloat->call);
-    if (wavescan) waveform_candidates_timescan::check_setup(c, wavescan->K, wavescan->of, wavescan->call);
-    if (waveboot) waveform_candidates_bootstrap::check_setup(c, waveboot->K, waveboot->of, waveboot->weight, waveboot->boot);
-    const size_t nband = c->bands.size();
-    const int unit = fit ? fit->K : fitscan ? fitscan->K : cand ? cand->K : candscan ? candscan->K : candfloat ? candfloat->K : speccand ? speccand->K : candboot ? candboot->K : wavecand ? wavecand->K : wavefloat ? wavefloat->K : wavescan ? wavescan->K : waveboot ? waveboot->K : 1;            // shards and pieces are whole multiples of it
-    const int nrec_all = (int)c->recv.size();
+    call.check(c);
+    const int unit = call.unit;
     prepare(c);
     if (c->synth_only) throw std::runtime_error("misfits need a reference seismogram and a misfit taper for every enabled receiver component "
                                                 "(the device comparator evaluates norms over the taper span, comparator.f90:782-792)");
     const size_t nmis = (size_t)c->nmis;
-    // (the rows of the waveform scan: the same layout on every device and in every piece)
-    const size_t scan_rstride = wavescan ? waveform_candidates_timescan::row_stride(c, wavescan->of.max_abs()) : 0;
-    auto sub_wavescan = [&](int s0) {
-        WaveCandScanCall w = *wavescan;
-        w.call = wavescan->call.at((size_t)(s0 / unit), nmis, (size_t)wavescan->of.nk, (size_t)unit, scan_rstride);
-        return w;
-    };
     if (!c->mates.empty() && nsrc / unit >= 2) {
         // ---- multi-device context: contiguous shards in list order (Source.grid order), shard 0 here -- this context keeps the
         // HEAD of the list as in the one-device case --, the others each in a thread of their own on their device
@@ -3010,58 +2996,18 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
         std::vector<std::future<int>> th;
         std::vector<int> rc((size_t)ndev, 0);
         auto bound = [&](int i) { return unit * (int)((long long)(nsrc / unit) * i / ndev); };
-        auto sub_fit = [&](int s0) { LinFitCall f = *fit; f.out = fit->out.at(s0 / unit, unit, nrec_all); return f; };
         for (int i = 1; i < ndev; i++) {
             kiwi_hip_ctx *m = c->mates[(size_t)i - 1];
             const int s0 = bound(i), n = bound(i + 1) - s0;
-            const bool fitting = fit != nullptr;
-            const LinFitCall mine = fitting ? sub_fit(s0) : LinFitCall{};
-            const bool banding = band != nullptr;
-            const BandCall mine_band = banding ? BandCall{ band->out.at((size_t)s0, nband, nmis) } : BandCall{};
-            const bool scanning = scan != nullptr;
-            const ScanCall mine_scan = scanning ? ScanCall{ scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis), scan->of } : ScanCall{};
-            const bool fitscanning = fitscan != nullptr;
-            FitScanCall mine_fitscan{};
-            if (fitscanning) { mine_fitscan = *fitscan; mine_fitscan.out = fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk); }
-            const bool canding = cand != nullptr;
-            CandCall mine_cand{};
-            if (canding) { mine_cand = *cand; mine_cand.out = cand->out.at(s0 / unit, unit, nrec_all); mine_cand.cand = cand->cand.at(s0 / unit, nrec_all); }
-            const bool candscanning = candscan != nullptr;
-            const CandScanCall mine_candscan = candscanning ? candscan->at((size_t)(s0 / unit), (size_t)nrec_all) : CandScanCall{};
-            const bool candfloating = candfloat != nullptr;
-            CandFloatCall mine_candfloat{};
-            if (candfloating) { mine_candfloat = *candfloat; mine_candfloat.fl = candfloat->fl.at(s0 / unit, nrec_all); }
-            const bool speccanding = speccand != nullptr;
-            SpecCandCall mine_speccand{};
-            if (speccanding) { mine_speccand = *speccand; mine_speccand.call = speccand->call.at(s0 / unit, (int)nmis, unit); }
-            const bool candbooting = candboot != nullptr;
-            CandBootCall mine_candboot{};
-            if (candbooting) { mine_candboot = *candboot; mine_candboot.boot = candboot->boot.at((size_t)(s0 / unit)); }
-            const bool wavecanding = wavecand != nullptr;
-            WaveCandCall mine_wavecand{};
-            if (wavecanding) { mine_wavecand = *wavecand; mine_wavecand.call = wavecand->call.at(s0 / unit, (int)nmis); }
-            const bool wavefloating = wavefloat != nullptr;
-            WaveCandFloatCall mine_wavefloat{};
-            if (wavefloating) { mine_wavefloat = *wavefloat; mine_wavefloat.call = wavefloat->call.at(s0 / unit, (int)nmis, nrec_all); }
-            const bool wavescanning = wavescan != nullptr;
-            const WaveCandScanCall mine_wavescan = wavescanning ? sub_wavescan(s0) : WaveCandScanCall{};
-            const bool wavebooting = waveboot != nullptr;
-            WaveCandBootCall mine_waveboot{};
-            if (wavebooting) { mine_waveboot = *waveboot; mine_waveboot.boot = waveboot->boot.at((size_t)(s0 / unit)); }
-            th.push_back(std::async(std::launch::async, [=] {
-                return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, misfit ? misfit + (size_t)s0 * nmis : nullptr,
-                                       norm ? norm + (size_t)s0 * nmis : nullptr, global ? global + s0 : nullptr, status ? status + s0 : nullptr,
-                                       fitting ? &mine : nullptr, banding ? &mine_band : nullptr, scanning ? &mine_scan : nullptr,
-                                       fitscanning ? &mine_fitscan : nullptr, canding ? &mine_cand : nullptr,
-                                       candscanning ? &mine_candscan : nullptr, candfloating ? &mine_candfloat : nullptr,
-                                       speccanding ? &mine_speccand : nullptr, candbooting ? &mine_candboot : nullptr,
-                                       wavecanding ? &mine_wavecand : nullptr, wavefloating ? &mine_wavefloat : nullptr,
-                                       wavescanning ? &mine_wavescan : nullptr, wavebooting ? &mine_waveboot : nullptr);
+            th.push_back(std::async(std::launch::async, [=, &call] {
+                return for_params_impl(m, sourcetype, n, params + (size_t)s0 * np, piece, call, status ? status + s0 : nullptr,
+                                       misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
+                                       global ? global + s0 : nullptr, base + s0);
             }));
         }
         std::vector<kiwi_hip_ctx *> keep;
         keep.swap(c->mates);                                  // (shard 0 through the one-device path of this very function)
-        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, misfit, norm, global, status, fit, band, scan, fitscan, cand, candscan, candfloat, speccand, candboot, wavecand, wavefloat, wavescan, waveboot);
+        rc[0] = for_params_impl(c, sourcetype, bound(1), params, piece, call, status, misfit, norm, global, base);
         keep.swap(c->mates);
         for (int i = 1; i < ndev; i++) rc[(size_t)i] = th[(size_t)i - 1].get();
         HIPCHECK(hipSetDevice(c->device));
@@ -3072,25 +3018,7 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             }
         return 0;
     }
-    // (default piece: 128 eikonal solves keep the discretiser team busy for one device evaluation; for the closed-form source types the
-    // host is a few per cent of a piece and larger launches fill the device better -- cfg3, 4096 trials: 31.1 k evals/s at 1024, 32.5 k at 2048)
-    if (piece <= 0) piece = source_nparams_eikonal(sourcetype) > 0 ? 128 : 2048;
-    if (unit > 1) piece = std::max(unit, piece - piece % unit);
-    // pieces [first, first + count) in list order.  Eikonal types: the LAST piece of the list -- the first one worked on, the one
-    // whose discretisation nothing hides -- is cut into a ramp of an eighth, an eighth, a quarter and half a piece, so that the
-    // device starts after an eighth of a piece's fast-marching solves (one per discretiser thread at the default 128 on 16 CPUs)
-    // instead of a whole one (512 cfg4-nukl trials: 137 ms of the call's 1066 were that wait).
-    std::vector<std::pair<int, int>> pieces;
-    for (int s0 = 0; s0 < nsrc; s0 += piece) pieces.emplace_back(s0, std::min(piece, nsrc - s0));
-    if (source_nparams_eikonal(sourcetype) > 0 && pieces.size() >= 2 && pieces.back().second / unit >= 8) {
-        const std::pair<int, int> last = pieces.back();
-        pieces.pop_back();
-        const int e = last.second / unit / 8 * unit, q = last.second / unit / 4 * unit, h = last.second - 2 * e - q;
-        pieces.emplace_back(last.first, h);
-        pieces.emplace_back(last.first + h, q);
-        pieces.emplace_back(last.first + h + q, e);
-        pieces.emplace_back(last.first + h + q + e, e);
-    }
+    const std::vector<std::pair<int, int>> pieces = cut_pieces(nsrc, piece, unit, source_nparams_eikonal(sourcetype) > 0);
     const int npieces = (int)pieces.size();
     auto work = [c, sourcetype, np, params, npieces, &pieces](int k) {
         HostBatch hb;
@@ -3187,58 +3115,12 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
             if (misfit) std::memset(misfit + (size_t)s0 * nmis, 0, (size_t)n * nmis * sizeof(float));
             if (norm) std::memset(norm + (size_t)s0 * nmis, 0, (size_t)n * nmis * sizeof(float));
             if (global) std::memset(global + s0, 0, (size_t)n * sizeof(float));
-            if (fit) linfit::fill_failed(n / unit, unit, nrec_all, fit->out.at(s0 / unit, unit, nrec_all));
-            if (band) bands::fill_failed((size_t)n, nband, nmis, band->out.at((size_t)s0, nband, nmis));
-            if (scan) timescan::fill_failed((size_t)n, (size_t)scan->of.nk, nmis, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
-            if (fitscan) linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)fitscan->of.nk,
-                                                      fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
-            if (cand) {
-                linfit::fill_failed(n / unit, unit, nrec_all, cand->out.at(s0 / unit, unit, nrec_all));
-                linfit_candidates_timescan::fill_failed((size_t)(n / unit), 1, (size_t)nrec_all, linfit_candidates_timescan::plain(cand->cand.at(s0 / unit, nrec_all)));
-            }
-            if (candscan) {
-                const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);
-                linfit_timescan::fill_failed((size_t)(n / unit), (size_t)unit, (size_t)mine.of.nk, mine.out);
-                linfit_candidates_timescan::fill_failed((size_t)(n / unit), (size_t)mine.of.nk, (size_t)nrec_all, mine.scan);
-            }
-            if (candfloat) linfit_candidates_floating::fill_failed(n / unit, nrec_all, candfloat->fl.at(s0 / unit, nrec_all));
-            if (speccand) spectral_candidates::fill_failed(n / unit, (int)nmis, unit, speccand->call.at(s0 / unit, (int)nmis, unit));
-            if (candboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), candboot->boot.at((size_t)(s0 / unit)));
-            if (wavecand) waveform_candidates::fill_failed(n / unit, (int)nmis, wavecand->call.at(s0 / unit, (int)nmis));
-            if (wavefloat) waveform_candidates_floating::fill_failed(n / unit, (int)nmis, nrec_all, wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
-            if (wavescan) waveform_candidates_timescan::fill_failed((size_t)(n / unit), nmis, (size_t)wavescan->of.nk, (size_t)unit, scan_rstride, sub_wavescan(s0).call);
-            if (waveboot) linfit_candidates_bootstrap::fill_failed((size_t)(n / unit), waveboot->boot.at((size_t)(s0 / unit)));
+            call.fill_failed(c, base + s0, n);
             continue;
         }
         upload_batch(c, hb);
         const double t_up = now();
-        if (fit) linfit::run(c, 0, n / unit, unit, fit->weight, fit->anarchy, fit->out.at(s0 / unit, unit, nrec_all), fit->robust, fit->wide);
-        else if (band) bands::run(c, 0, n, band->out.at((size_t)s0, nband, nmis));
-        else if (scan) timescan::run(c, 0, n, scan->of, scan->out.at((size_t)s0, (size_t)scan->of.nk, nmis));
-        else if (fitscan) linfit_timescan::run(c, 0, n / unit, unit, fitscan->of, fitscan->weight, fitscan->anarchy,
-                                               fitscan->out.at((size_t)(s0 / unit), (size_t)unit, (size_t)fitscan->of.nk));
-        else if (cand) {
-            const linfit::Candidates mine = cand->cand.at(s0 / unit, nrec_all);
-            linfit::run(c, 0, n / unit, unit, cand->weight, cand->anarchy, cand->out.at(s0 / unit, unit, nrec_all), nullptr, nullptr, &mine);
-        } else if (candscan) {
-            const CandScanCall mine = candscan->at((size_t)(s0 / unit), (size_t)nrec_all);
-            linfit_candidates_timescan::run(c, 0, n / unit, unit, mine.of, mine.weight, mine.anarchy, mine.out, mine.scan);
-        } else if (candfloat)
-            linfit_candidates_floating::run(c, 0, n / unit, unit, candfloat->weight, candfloat->anarchy, candfloat->fl.at(s0 / unit, nrec_all));
-        else if (speccand)
-            spectral_candidates::run(c, 0, n / unit, unit, speccand->weight, speccand->anarchy, speccand->call.at(s0 / unit, (int)nmis, unit));
-        else if (candboot)
-            linfit_candidates_bootstrap::run(c, 0, n / unit, unit, candboot->of, candboot->weight, candboot->anarchy, candboot->boot.at((size_t)(s0 / unit)));
-        else if (wavecand)
-            waveform_candidates::run(c, 0, n / unit, unit, wavecand->weight, wavecand->anarchy, wavecand->call.at(s0 / unit, (int)nmis));
-        else if (wavefloat)
-            waveform_candidates_floating::run(c, 0, n / unit, unit, wavefloat->weight, wavefloat->anarchy,
-                                              wavefloat->call.at(s0 / unit, (int)nmis, nrec_all));
-        else if (wavescan)
-            waveform_candidates_timescan::run(c, 0, n / unit, unit, wavescan->of, wavescan->weight, wavescan->anarchy, sub_wavescan(s0).call);
-        else if (waveboot)
-            waveform_candidates_bootstrap::run(c, 0, n / unit, unit, waveboot->of, waveboot->weight, waveboot->anarchy, waveboot->boot.at((size_t)(s0 / unit)));
-        else eval_impl(c, 0, n, c->keep_which);
+        call.run(c, base + s0, n);
         if (kiwi_hip_get_misfits(c, 0, n, misfit ? misfit + (size_t)s0 * nmis : nullptr, norm ? norm + (size_t)s0 * nmis : nullptr,
                                  global ? global + s0 : nullptr)) throw std::runtime_error(c->err);
         if (trace) {
@@ -3255,7 +3137,9 @@ static int for_params_impl(kiwi_hip_ctx *c, int sourcetype, int nsrc, const floa
 int kiwi_hip_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, const float *params, int piece,
                                 float *misfit, float *norm, float *global, int *status)
 {
-    return for_params_impl(c, sourcetype, nsrc, params, piece, misfit, norm, global, status, nullptr);
+    const PieceCall plain{ 1, [](kiwi_hip_ctx *) {}, [](kiwi_hip_ctx *, int, int) {},
+                           [](kiwi_hip_ctx *m, int, int n) { eval_impl(m, 0, n, m->keep_which); } };
+    return for_params_impl(c, sourcetype, nsrc, params, piece, plain, status, misfit, norm, global);
 }
 
 // Least-squares coefficients of K basis sources per group under l2norm (kiwi_linfit.hpp), for groups of the uploaded batch ...
@@ -3264,7 +3148,7 @@ int kiwi_hip_linear_fit(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const dou
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
     linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver });
     return 0;
     GUARD_END(c)
@@ -3276,12 +3160,10 @@ int kiwi_hip_linear_fit_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int 
                                double *normal, double *normal_by_receiver)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
-    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver }, nullptr };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
+    const linfit::Out out{ coef, misfit, status, pivot_min, normal, normal_by_receiver };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, linfit::piece_call(K, receiver_weight, anarchy, out));
 }
 
 int kiwi_hip_linear_fit_max_basis(void) { return linfit::kMaxBasis; }
@@ -3295,8 +3177,8 @@ int kiwi_hip_linear_fit_wide(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, cons
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
-    c->linfit_wide_ms[0] = c->linfit_wide_ms[1] = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
+    zero_ms(c, &kiwi_hip_ctx::linfit_wide_ms);
     const linfit::Wide wd{ nonneg, penalty, penalty_relative ? 1 : 0 };
     linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy,
                 linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves }, nullptr, &wd);
@@ -3306,10 +3188,7 @@ int kiwi_hip_linear_fit_wide(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, cons
 
 int kiwi_hip_get_linear_fit_wide_ms(kiwi_hip_ctx *c, float ms[2])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    ms[0] = c->linfit_wide_ms[0]; ms[1] = c->linfit_wide_ms[1];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_wide_ms, ms);
 }
 
 int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
@@ -3318,15 +3197,12 @@ int kiwi_hip_linear_fit_wide_params(kiwi_hip_ctx *c, int sourcetype, int ngroup,
                                     double *normal, double *normal_by_receiver)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kWideMaxBasis)
-        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kWideMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
-    c->linfit_wide_ms[0] = c->linfit_wide_ms[1] = 0.f;
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kWideMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
+    zero_ms(c, &kiwi_hip_ctx::linfit_wide_ms);
     const linfit::Wide wd{ nonneg, penalty, penalty_relative ? 1 : 0 };
-    const LinFitCall fit{ K, receiver_weight, anarchy,
-                          linfit::Out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves }, nullptr, &wd };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+    const linfit::Out out{ coef, misfit, status, pivot_min, normal, normal_by_receiver, nullptr, 0, npositive, nsolves };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, linfit::piece_call(K, receiver_weight, anarchy, out, nullptr, &wd));
 }
 
 // Misfits in several frequency bands and norms from one synthesis (kiwi_bands.hpp)
@@ -3371,7 +3247,7 @@ int kiwi_hip_band_misfits(kiwi_hip_ctx *c, int isrc0, int nsrc, float *misfit, f
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->bands_ms[0] = c->bands_ms[1] = c->bands_ms[2] = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::bands_ms);
     bands::run(c, isrc0, nsrc, bands::Out{ misfit, norm, global });
     return 0;
     GUARD_END(c)
@@ -3381,18 +3257,13 @@ int kiwi_hip_band_misfits_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, 
                                      float *global, int *status)
 {
     if (!c) return fail(nullptr, "null context");
-    c->bands_ms[0] = c->bands_ms[1] = c->bands_ms[2] = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) m->bands_ms[0] = m->bands_ms[1] = m->bands_ms[2] = 0.f;
-    const BandCall band{ bands::Out{ misfit, norm, global } };
-    return for_params_impl(c, sourcetype, nsrc, params, piece, nullptr, nullptr, nullptr, status, nullptr, &band);
+    zero_ms(c, &kiwi_hip_ctx::bands_ms, true);
+    return for_params_impl(c, sourcetype, nsrc, params, piece, bands::piece_call(bands::Out{ misfit, norm, global }), status);
 }
 
 int kiwi_hip_get_band_misfits_ms(kiwi_hip_ctx *c, float ms[3])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 3; i++) ms[i] = c->bands_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::bands_ms, ms);
 }
 
 // Misfits at many origin times from one synthesis (kiwi_timescan.hpp)
@@ -3403,7 +3274,7 @@ int kiwi_hip_time_scan(kiwi_hip_ctx *c, int isrc0, int nsrc, int k0, int kstep, 
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->timescan_ms[0] = c->timescan_ms[1] = c->timescan_ms[2] = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::timescan_ms);
     timescan::run(c, isrc0, nsrc, timescan::Offsets{ k0, kstep, nk }, timescan::Out{ misfit, norm, global, best });
     return 0;
     GUARD_END(c)
@@ -3413,18 +3284,14 @@ int kiwi_hip_time_scan_for_params(kiwi_hip_ctx *c, int sourcetype, int nsrc, con
                                   float *misfit, float *norm, float *global, int *best, int *status)
 {
     if (!c) return fail(nullptr, "null context");
-    c->timescan_ms[0] = c->timescan_ms[1] = c->timescan_ms[2] = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) m->timescan_ms[0] = m->timescan_ms[1] = m->timescan_ms[2] = 0.f;
-    const ScanCall scan{ timescan::Out{ misfit, norm, global, best }, timescan::Offsets{ k0, kstep, nk } };
-    return for_params_impl(c, sourcetype, nsrc, params, piece, nullptr, nullptr, nullptr, status, nullptr, nullptr, &scan);
+    zero_ms(c, &kiwi_hip_ctx::timescan_ms, true);
+    return for_params_impl(c, sourcetype, nsrc, params, piece,
+                           timescan::piece_call(timescan::Offsets{ k0, kstep, nk }, timescan::Out{ misfit, norm, global, best }), status);
 }
 
 int kiwi_hip_get_time_scan_ms(kiwi_hip_ctx *c, float ms[3])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 3; i++) ms[i] = c->timescan_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::timescan_ms, ms);
 }
 
 // The linear fit at many origin times from one synthesis of the basis (kiwi_linfit_timescan.hpp)
@@ -3433,7 +3300,7 @@ int kiwi_hip_linear_fit_time_scan(kiwi_hip_ctx *c, int isrc0, int ngroup, int K,
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->linfit_timescan_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::linfit_timescan_ms);
     linfit_timescan::run(c, isrc0, ngroup, K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy,
                          linfit_timescan::Out{ coef, misfit, status, pivot_min, best, normal });
     return 0;
@@ -3445,14 +3312,11 @@ int kiwi_hip_linear_fit_time_scan_params(kiwi_hip_ctx *c, int sourcetype, int ng
                                          double *pivot_min, int *best, double *normal)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->linfit_timescan_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_timescan_ms) t = 0.f;
-    const FitScanCall fitscan{ K, receiver_weight, anarchy, linfit_timescan::Out{ coef, misfit, status, pivot_min, best, normal },
-                               timescan::Offsets{ k0, kstep, nk } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &fitscan);
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_timescan_ms, true);
+    const linfit_timescan::Out out{ coef, misfit, status, pivot_min, best, normal };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           linfit_timescan::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, out));
 }
 
 int kiwi_hip_linear_fit_time_scan_shape(int K, int *per_pass, int *tile)
@@ -3465,10 +3329,7 @@ int kiwi_hip_linear_fit_time_scan_shape(int K, int *per_pass, int *tile)
 
 int kiwi_hip_get_linear_fit_time_scan_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->linfit_timescan_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_timescan_ms, ms);
 }
 
 // The misfits of given coefficient vectors from the kept normal equations (kiwi_linfit_candidates.hpp).  The free fit of the same
@@ -3492,9 +3353,8 @@ int kiwi_hip_linear_fit_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
-    if (K < 1 || K > linfit::kMaxBasis)
-        throw std::runtime_error("linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
     const linfit::Candidates cd{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale, receiver_misfit,
                                  receiver_norm };
     CandFitArrays fa;
@@ -3509,24 +3369,18 @@ int kiwi_hip_linear_fit_candidates_params(kiwi_hip_ctx *c, int sourcetype, int n
                                           float *receiver_misfit, float *receiver_norm, double *fit_coef, double *fit_misfit)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) m->linfit_ms[0] = m->linfit_ms[1] = m->linfit_ms[2] = m->linfit_ms[3] = 0.f;
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms, true);
     CandFitArrays fa;
-    const CandCall cand{ K, receiver_weight, anarchy, fa.out(ngroup, K, fit_coef, fit_misfit),
-                         linfit::Candidates{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale,
-                                             receiver_misfit, receiver_norm } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &cand);
+    const linfit::Candidates cd{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale, receiver_misfit,
+                                 receiver_norm };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           linfit::candidates_piece_call(K, receiver_weight, anarchy, fa.out(ngroup, K, fit_coef, fit_misfit), cd));
 }
 
 int kiwi_hip_get_linear_fit_candidates_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->linfit_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_ms, ms);
 }
 
 int kiwi_hip_linear_fit_candidates_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage)
@@ -3550,7 +3404,7 @@ int kiwi_hip_linear_fit_candidates_floating(kiwi_hip_ctx *c, int isrc0, int ngro
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->linfit_cand_floating_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_floating_ms);
     if (free_scale != 0) throw std::runtime_error(kCandFloatFreeScale);
     const linfit_candidates_floating::Floating fl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
                                                    cand_shift, receiver_misfit, receiver_norm };
@@ -3567,26 +3421,16 @@ int kiwi_hip_linear_fit_candidates_floating_params(kiwi_hip_ctx *c, int sourcety
 {
     if (!c) return fail(nullptr, "null context");
     if (free_scale != 0) return fail(c, kCandFloatFreeScale);
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, "linear_fit_candidates_floating: K = " + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "linear_fit_candidates_floating: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->linfit_cand_floating_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_floating_ms) t = 0.f;
-    const CandFloatCall candfloat{ K, receiver_weight, anarchy,
-                                   linfit_candidates_floating::Floating{ candidates, ncand, outer_norm, best_index, best_misfit, status,
-                                                                         best_shift, misfit, cand_shift, receiver_misfit, receiver_norm } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, &candfloat);
+    if (const std::string bad = bad_basis("linear_fit_candidates_floating: K = ", K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_floating_ms, true);
+    const linfit_candidates_floating::Floating fl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
+                                                   cand_shift, receiver_misfit, receiver_norm };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, linfit_candidates_floating::piece_call(K, receiver_weight, anarchy, fl));
 }
 
 int kiwi_hip_get_linear_fit_candidates_floating_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->linfit_cand_floating_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_cand_floating_ms, ms);
 }
 
 int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_workgroup, int *shifts_per_pass, int *shifts_per_stage)
@@ -3606,7 +3450,7 @@ int kiwi_hip_spectral_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, 
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->speccand_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::speccand_ms);
     const spectral_candidates::Call cl{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale,
                                         slot_misfit, slot_norm, spectra_bins, spectra, spectra_range, spectra_ref };
     spectral_candidates::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
@@ -3621,26 +3465,16 @@ int kiwi_hip_spectral_candidates_params(kiwi_hip_ctx *c, int sourcetype, int ngr
                                         float *spectra_ref)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > spectral_candidates::kMaxBasis)
-        return fail(c, "spectral_candidates: K = " + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(spectral_candidates::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "spectral_candidates: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->speccand_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->speccand_ms) t = 0.f;
-    const SpecCandCall speccand{ K, receiver_weight, anarchy,
-                                 spectral_candidates::Call{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit,
-                                                            scale, slot_misfit, slot_norm, spectra_bins, spectra, spectra_range, spectra_ref } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, &speccand);
+    if (const std::string bad = bad_basis("spectral_candidates: K = ", K, spectral_candidates::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::speccand_ms, true);
+    const spectral_candidates::Call cl{ candidates, ncand, outer_norm, free_scale, best_index, best_misfit, status, misfit, scale,
+                                        slot_misfit, slot_norm, spectra_bins, spectra, spectra_range, spectra_ref };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, spectral_candidates::piece_call(K, receiver_weight, anarchy, cl));
 }
 
 int kiwi_hip_get_spectral_candidates_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->speccand_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::speccand_ms, ms);
 }
 
 // (c may be null: the two kernel shapes need no device; with a context, spectra_bins is the row length of its spectra arrays)
@@ -3665,7 +3499,7 @@ int kiwi_hip_waveform_candidates(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, 
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->wavecand_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::wavecand_ms);
     const waveform_candidates::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, misfit, slot_misfit, slot_norm };
     waveform_candidates::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
     return 0;
@@ -3678,26 +3512,15 @@ int kiwi_hip_waveform_candidates_params(kiwi_hip_ctx *c, int sourcetype, int ngr
                                         float *slot_norm)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > waveform_candidates::kMaxBasis)
-        return fail(c, "waveform_candidates: K = " + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(waveform_candidates::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "waveform_candidates: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->wavecand_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_ms) t = 0.f;
-    const WaveCandCall wavecand{ K, receiver_weight, anarchy,
-                                 waveform_candidates::Call{ candidates, ncand, outer_norm, best_index, best_misfit, status, misfit,
-                                                            slot_misfit, slot_norm } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, &wavecand);
+    if (const std::string bad = bad_basis("waveform_candidates: K = ", K, waveform_candidates::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_ms, true);
+    const waveform_candidates::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, misfit, slot_misfit, slot_norm };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, waveform_candidates::piece_call(K, receiver_weight, anarchy, cl));
 }
 
 int kiwi_hip_get_waveform_candidates_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::wavecand_ms, ms);
 }
 
 int kiwi_hip_waveform_candidates_shape(int K, int *candidates_per_workgroup, int *samples_per_stage)
@@ -3716,7 +3539,7 @@ int kiwi_hip_waveform_candidates_floating(kiwi_hip_ctx *c, int isrc0, int ngroup
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->wavecand_float_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::wavecand_float_ms);
     const waveform_candidates_floating::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
                                                  cand_shift, slot_misfit, slot_norm };
     waveform_candidates_floating::run(c, isrc0, ngroup, K, receiver_weight, anarchy, cl);
@@ -3730,26 +3553,16 @@ int kiwi_hip_waveform_candidates_floating_params(kiwi_hip_ctx *c, int sourcetype
                                                  double *misfit, short *cand_shift, float *slot_misfit, float *slot_norm)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > waveform_candidates_floating::kMaxBasis)
-        return fail(c, "waveform_candidates_floating: K = " + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(waveform_candidates_floating::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "waveform_candidates_floating: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->wavecand_float_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_float_ms) t = 0.f;
-    const WaveCandFloatCall wavefloat{ K, receiver_weight, anarchy,
-                                       waveform_candidates_floating::Call{ candidates, ncand, outer_norm, best_index, best_misfit, status,
-                                                                           best_shift, misfit, cand_shift, slot_misfit, slot_norm } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &wavefloat);
+    if (const std::string bad = bad_basis("waveform_candidates_floating: K = ", K, waveform_candidates_floating::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_float_ms, true);
+    const waveform_candidates_floating::Call cl{ candidates, ncand, outer_norm, best_index, best_misfit, status, best_shift, misfit,
+                                                 cand_shift, slot_misfit, slot_norm };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, waveform_candidates_floating::piece_call(K, receiver_weight, anarchy, cl));
 }
 
 int kiwi_hip_get_waveform_candidates_floating_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_float_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::wavecand_float_ms, ms);
 }
 
 int kiwi_hip_waveform_candidates_floating_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *shifts_per_pass)
@@ -3770,7 +3583,7 @@ int kiwi_hip_waveform_candidates_time_scan(kiwi_hip_ctx *c, int isrc0, int ngrou
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->wavecand_scan_ms) t = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms);
     const waveform_candidates_timescan::Call cl{ candidates, ncand, outer_norm, best_offset, best_index, best_misfit, status, cand_misfit,
                                                  cand_offset, misfit, slot_misfit, slot_norm, rows };
     waveform_candidates_timescan::run(c, isrc0, ngroup, K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, cl);
@@ -3785,27 +3598,17 @@ int kiwi_hip_waveform_candidates_time_scan_params(kiwi_hip_ctx *c, int sourcetyp
                                                   float *slot_misfit, float *slot_norm, float *rows)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
-        return fail(c, "waveform_candidates_time_scan: K = " + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "waveform_candidates_time_scan: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->wavecand_scan_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->wavecand_scan_ms) t = 0.f;
-    const WaveCandScanCall wavescan{ K, receiver_weight, anarchy,
-                                     waveform_candidates_timescan::Call{ candidates, ncand, outer_norm, best_offset, best_index, best_misfit,
-                                                                         status, cand_misfit, cand_offset, misfit, slot_misfit, slot_norm, rows },
-                                     timescan::Offsets{ k0, kstep, nk } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &wavescan);
+    if (const std::string bad = bad_basis("waveform_candidates_time_scan: K = ", K, waveform_candidates_timescan::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms, true);
+    const waveform_candidates_timescan::Call cl{ candidates, ncand, outer_norm, best_offset, best_index, best_misfit, status, cand_misfit,
+                                                 cand_offset, misfit, slot_misfit, slot_norm, rows };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           waveform_candidates_timescan::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, cl));
 }
 
 int kiwi_hip_get_waveform_candidates_time_scan_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->wavecand_scan_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::wavecand_scan_ms, ms);
 }
 
 int kiwi_hip_waveform_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *samples_per_stage, int *offsets_per_pass)
@@ -3846,11 +3649,9 @@ int kiwi_hip_waveform_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngrou
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->wavecand_boot_ms) t = 0.f;
-    for (float &t : c->wavecand_scan_ms) t = 0.f;
-    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
-        throw std::runtime_error(kWaveBootBasis + std::to_string(K) + " basis sources per group; 1 to " +
-                                 std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
+    zero_ms(c, &kiwi_hip_ctx::wavecand_boot_ms);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms);
+    if (const std::string bad = bad_basis(kWaveBootBasis, K, waveform_candidates_timescan::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
     const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
                                                 status, group_value, group_offset, group_cand, 0, nullptr };
     const timescan::Offsets of{ k0, kstep, nk };
@@ -3868,30 +3669,20 @@ int kiwi_hip_waveform_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetyp
                                                   double *group_value, int *group_offset, int *group_cand)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > waveform_candidates_timescan::kMaxBasis)
-        return fail(c, kWaveBootBasis + std::to_string(K) + " basis sources per group; 1 to " +
-                           std::to_string(waveform_candidates_timescan::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "waveform_candidates_bootstrap: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->wavecand_boot_ms) t = 0.f;
-    for (float &t : c->wavecand_scan_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) { for (float &t : m->wavecand_boot_ms) t = 0.f; for (float &t : m->wavecand_scan_ms) t = 0.f; }
+    if (const std::string bad = bad_basis(kWaveBootBasis, K, waveform_candidates_timescan::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_boot_ms, true);
+    zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    const WaveCandBootCall waveboot{ K, receiver_weight, anarchy,
-                                     linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group,
-                                                                        best_offset, best_cand, status, group_value, group_offset, group_cand, 0, &mu },
-                                     timescan::Offsets{ k0, kstep, nk } };
-    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) waveboot.boot.begin();      // (what is missing is refused below)
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &waveboot);
+    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
+                                                status, group_value, group_offset, group_cand, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin();      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           waveform_candidates_bootstrap::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, bt));
 }
 
 int kiwi_hip_get_waveform_candidates_bootstrap_ms(kiwi_hip_ctx *c, float ms[5])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 5; i++) ms[i] = c->wavecand_boot_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::wavecand_boot_ms, ms);
 }
 
 int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
@@ -3930,9 +3721,8 @@ int kiwi_hip_linear_fit_candidates_time_scan(kiwi_hip_ctx *c, int isrc0, int ngr
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->linfit_cand_timescan_ms) t = 0.f;
-    if (K < 1 || K > linfit::kMaxBasis)
-        throw std::runtime_error(kCandScanBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_timescan_ms);
+    if (const std::string bad = bad_basis(kCandScanBasis, K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
     const linfit_candidates_timescan::Scan sc{ candidates, ncand, outer_norm, free_scale, best_offset, best_index, best_misfit, best_scale,
                                                status, cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm };
     CandScanFitArrays fa;
@@ -3951,28 +3741,19 @@ int kiwi_hip_linear_fit_candidates_time_scan_params(kiwi_hip_ctx *c, int sourcet
                                                     int *fit_status)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, kCandScanBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "linear_fit_candidates_time_scan: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->linfit_cand_timescan_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_timescan_ms) t = 0.f;
+    if (const std::string bad = bad_basis(kCandScanBasis, K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_timescan_ms, true);
     CandScanFitArrays fa;
-    const CandScanCall candscan{ K, receiver_weight, anarchy, fa.out(ngroup, K, nk, fit_coef, fit_misfit, fit_status),
-                                 linfit_candidates_timescan::Scan{ candidates, ncand, outer_norm, free_scale, best_offset, best_index,
-                                                                   best_misfit, best_scale, status, cand_misfit, cand_offset, cand_scale,
-                                                                   misfit, scale, receiver_misfit, receiver_norm },
-                                 timescan::Offsets{ k0, kstep, nk } };
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, &candscan);
+    const linfit_candidates_timescan::Scan sc{ candidates, ncand, outer_norm, free_scale, best_offset, best_index, best_misfit, best_scale,
+                                               status, cand_misfit, cand_offset, cand_scale, misfit, scale, receiver_misfit, receiver_norm };
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           linfit_candidates_timescan::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy,
+                                                                  fa.out(ngroup, K, nk, fit_coef, fit_misfit, fit_status), sc));
 }
 
 int kiwi_hip_get_linear_fit_candidates_time_scan_ms(kiwi_hip_ctx *c, float ms[5])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 5; i++) ms[i] = c->linfit_cand_timescan_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_cand_timescan_ms, ms);
 }
 
 int kiwi_hip_linear_fit_candidates_time_scan_shape(int K, int *candidates_per_workgroup, int *receivers_per_stage)
@@ -3993,9 +3774,8 @@ int kiwi_hip_linear_fit_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngr
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    for (float &t : c->linfit_cand_boot_ms) t = 0.f;
-    if (K < 1 || K > linfit::kMaxBasis)
-        throw std::runtime_error(kCandBootBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_boot_ms);
+    if (const std::string bad = bad_basis(kCandBootBasis, K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
     const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
                                                 status, group_value, group_offset, group_cand, 0, nullptr };
     const timescan::Offsets of{ k0, kstep, nk };
@@ -4013,28 +3793,19 @@ int kiwi_hip_linear_fit_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcet
                                                     double *group_value, int *group_offset, int *group_cand)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, kCandBootBasis + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL)
-        return fail(c, "linear_fit_candidates_bootstrap: need at least one group (and at most INT_MAX sources)");
-    for (float &t : c->linfit_cand_boot_ms) t = 0.f;
-    for (kiwi_hip_ctx *m : c->mates) for (float &t : m->linfit_cand_boot_ms) t = 0.f;
+    if (const std::string bad = bad_basis(kCandBootBasis, K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_boot_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    const CandBootCall candboot{ K, receiver_weight, anarchy,
-                                 linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group,
-                                                                    best_offset, best_cand, status, group_value, group_offset, group_cand, 0, &mu },
-                                 timescan::Offsets{ k0, kstep, nk } };
-    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) candboot.boot.begin();      // (what is missing is refused below)
-    return for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, &candboot);
+    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
+                                                status, group_value, group_offset, group_cand, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin();      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           linfit_candidates_bootstrap::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, bt));
 }
 
 int kiwi_hip_get_linear_fit_candidates_bootstrap_ms(kiwi_hip_ctx *c, float ms[5])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 5; i++) ms[i] = c->linfit_cand_boot_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_cand_boot_ms, ms);
 }
 
 int kiwi_hip_linear_fit_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
@@ -4082,7 +3853,7 @@ int kiwi_hip_linear_fit_robust(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, in
 {
     if (!c) return fail(nullptr, "null context");
     GUARD_BEGIN_DEV(c)
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
     const int mode = robust_mode(c, outer_norm, niter, eps);
     if (mode == 0) {
         linfit::run(c, isrc0, ngroup, K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status });
@@ -4100,26 +3871,20 @@ int kiwi_hip_linear_fit_robust_params(kiwi_hip_ctx *c, int sourcetype, int ngrou
                                       int *status, double *trace)
 {
     if (!c) return fail(nullptr, "null context");
-    if (K < 1 || K > linfit::kMaxBasis)
-        return fail(c, "linear_fit: K = " + std::to_string(K) + " basis sources per group; 1 to " + std::to_string(linfit::kMaxBasis) + " are supported");
-    if (ngroup < 1 || (long long)ngroup * K > 0x7fffffffLL) return fail(c, "linear_fit: need at least one group (and at most INT_MAX sources)");
-    c->linfit_ms[0] = c->linfit_ms[1] = c->linfit_ms[2] = c->linfit_ms[3] = 0.f;
+    if (const std::string bad = bad_basis("linear_fit: K = ", K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_ms);
     int mode = 0;
     try { mode = robust_mode(c, outer_norm, niter, eps); } catch (const std::exception &e) { return fail(c, e.what()); }
     const linfit::Robust rb{ mode, niter, eps };
-    const LinFitCall fit{ K, receiver_weight, anarchy, linfit::Out{ coef, misfit, status, nullptr, nullptr, nullptr, mode ? trace : nullptr, niter + 1 },
-                          mode ? &rb : nullptr };
-    const int rc = for_params_impl(c, sourcetype, ngroup * K, params, piece, nullptr, nullptr, nullptr, nullptr, &fit);
+    const linfit::Out out{ coef, misfit, status, nullptr, nullptr, nullptr, mode ? trace : nullptr, niter + 1 };
+    const int rc = for_params_impl(c, sourcetype, ngroup * K, params, piece, linfit::piece_call(K, receiver_weight, anarchy, out, mode ? &rb : nullptr));
     if (rc == 0 && mode == 0) robust_forwarded_trace(ngroup, niter, misfit, trace);
     return rc;
 }
 
 int kiwi_hip_get_linear_fit_robust_ms(kiwi_hip_ctx *c, float ms[4])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 4; i++) ms[i] = c->linfit_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::linfit_ms, ms);
 }
 
 int kiwi_hip_get_synthetics(kiwi_hip_ctx *c, int isrc, int irec, int icomp, int which, int *first, int *n,
@@ -4537,10 +4302,7 @@ int kiwi_hip_outer_misfits(kiwi_hip_ctx *c, int nsrc, int nmis, int nrec, const 
 
 int kiwi_hip_get_outer_ms(kiwi_hip_ctx *c, float ms[3])
 {
-    if (!c) return fail(nullptr, "null context");
-    if (!ms) return fail(c, "null argument");
-    for (int i = 0; i < 3; i++) ms[i] = c->outer_ms[i];
-    return 0;
+    return get_ms(c, &kiwi_hip_ctx::outer_ms, ms);
 }
 
 int kiwi_hip_outer_max_receivers(void) { return outer::kMaxRec; }

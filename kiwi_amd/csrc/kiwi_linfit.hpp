@@ -513,4 +513,13 @@ static void fill_failed(int ngroup, int K, int nrec, const Out &out)
     if (out.by_receiver) std::memset(out.by_receiver, 0, (size_t)ngroup * nrec * nn * sizeof(double));
 }
 
+// kiwi_hip_linear_fit_params, _robust_params and _wide_params piece by piece (PieceCall, kiwi_group_run.hpp): rb and wd as in run()
+static PieceCall piece_call(int K, const double *receiver_weight, int anarchy, const Out &out, const Robust *rb = nullptr, const Wide *wd = nullptr)
+{
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, out, rb, wd); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { fill_failed(n / K, K, (int)c->recv.size(), out.at(s0 / K, K, (int)c->recv.size())); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n / K, K, receiver_weight, anarchy, out.at(s0 / K, K, (int)c->recv.size()), rb, wd); } };
+}
+
 } // namespace linfit

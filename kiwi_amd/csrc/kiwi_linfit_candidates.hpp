@@ -60,4 +60,22 @@ static void check_candidates(const Candidates &cd, int K)
                 throw std::runtime_error("linear_fit_candidates: entry " + std::to_string(p % K) + " of candidate " + std::to_string(p / K) + " is not finite");
 }
 
+// kiwi_hip_linear_fit_candidates_params piece by piece (PieceCall, kiwi_group_run.hpp): linfit::run with the candidates behind its
+// l2 kernels; out: the free fit made on the way
+static PieceCall candidates_piece_call(int K, const double *receiver_weight, int anarchy, const Out &out, const Candidates &cd)
+{
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_candidates(cd, K); check_setup(c, K, out); },
+        [=](kiwi_hip_ctx *c, int s0, int n) {
+            const int nrec = (int)c->recv.size();
+            fill_failed(n / K, K, nrec, out.at(s0 / K, K, nrec));
+            linfit_candidates_timescan::fill_failed((size_t)(n / K), 1, (size_t)nrec, linfit_candidates_timescan::plain(cd.at(s0 / K, nrec)));
+        },
+        [=](kiwi_hip_ctx *c, int s0, int n) {
+            const int nrec = (int)c->recv.size();
+            const Candidates mine = cd.at(s0 / K, nrec);
+            run(c, 0, n / K, K, receiver_weight, anarchy, out.at(s0 / K, K, nrec), nullptr, nullptr, &mine);
+        } };
+}
+
 } // namespace linfit

@@ -430,4 +430,16 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     leave_evaluated(c, isrc0, ngroup * K, 0);              // the plain evaluation of the basis sources was made on the way
 }
 
+// kiwi_hip_linear_fit_candidates_bootstrap_params piece by piece (PieceCall, kiwi_group_run.hpp): every piece's and device's run
+// folds its bests into those of the call under bt.mu.  check_fn, run_fn: kiwi_waveform_candidates_bootstrap.hpp passes its own, the
+// rest is the same
+static PieceCall piece_call(int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const Boot &bt,
+                            decltype(&check_setup) check_fn = &check_setup, decltype(&run) run_fn = &run)
+{
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_fn(c, K, of, receiver_weight, bt); },
+        [=](kiwi_hip_ctx *, int s0, int n) { fill_failed((size_t)(n / K), bt.at((size_t)(s0 / K))); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run_fn(c, 0, n / K, K, of, receiver_weight, anarchy, bt.at((size_t)(s0 / K))); } };
+}
+
 } // namespace linfit_candidates_bootstrap

@@ -448,4 +448,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { fill_failed(1, nrec, fl.at(g, nrec)); });
 }
 
+// kiwi_hip_linear_fit_candidates_floating_params piece by piece (PieceCall, kiwi_group_run.hpp)
+static PieceCall piece_call(int K, const double *receiver_weight, int anarchy, const Floating &fl)
+{
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, fl); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { fill_failed(n / K, (int)c->recv.size(), fl.at(s0 / K, (int)c->recv.size())); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n / K, K, receiver_weight, anarchy, fl.at(s0 / K, (int)c->recv.size())); } };
+}
+
 } // namespace linfit_candidates_floating

@@ -415,4 +415,22 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     });
 }
 
+// kiwi_hip_linear_fit_candidates_time_scan_params piece by piece (PieceCall, kiwi_group_run.hpp); fit: the free fit made on the way
+static PieceCall piece_call(int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const linfit_timescan::Out &fit,
+                            const Scan &sc)
+{
+    const size_t nk = (size_t)of.nk;
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, of, fit, sc); },
+        [=](kiwi_hip_ctx *c, int s0, int n) {
+            const size_t g = (size_t)(s0 / K), ng = (size_t)(n / K), nrec = c->recv.size();
+            linfit_timescan::fill_failed(ng, (size_t)K, nk, fit.at(g, (size_t)K, nk));
+            fill_failed(ng, nk, nrec, sc.at(g, nk, nrec));
+        },
+        [=](kiwi_hip_ctx *c, int s0, int n) {
+            const size_t g = (size_t)(s0 / K);
+            run(c, 0, n / K, K, of, receiver_weight, anarchy, fit.at(g, (size_t)K, nk), sc.at(g, nk, c->recv.size()));
+        } };
+}
+
 } // namespace linfit_candidates_timescan

@@ -286,4 +286,14 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { mark_failed((size_t)g, (size_t)K, (size_t)nk, out); });
 }
 
+// kiwi_hip_linear_fit_time_scan_params piece by piece (PieceCall, kiwi_group_run.hpp)
+static PieceCall piece_call(int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const Out &out)
+{
+    auto mine = [=](int s0) { return out.at((size_t)(s0 / K), (size_t)K, (size_t)of.nk); };
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, of, out); },
+        [=](kiwi_hip_ctx *, int s0, int n) { fill_failed((size_t)(n / K), (size_t)K, (size_t)of.nk, mine(s0)); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n / K, K, of, receiver_weight, anarchy, mine(s0)); } };
+}
+
 } // namespace linfit_timescan

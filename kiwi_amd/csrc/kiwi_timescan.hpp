@@ -424,4 +424,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int nsrc, const Offsets &of, const O
     leave_evaluated(c, isrc0, nsrc, 0);                    // the plain evaluation -- offset 0 -- was made on the way
 }
 
+// kiwi_hip_time_scan_for_params piece by piece (PieceCall, kiwi_group_run.hpp): plain sources
+static PieceCall piece_call(const Offsets &of, const Out &out)
+{
+    return PieceCall{ 1,
+        [=](kiwi_hip_ctx *c) { check_setup(c, of.k0, of.kstep, of.nk); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { fill_failed((size_t)n, (size_t)of.nk, (size_t)c->nmis, out.at((size_t)s0, (size_t)of.nk, (size_t)c->nmis)); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n, of, out.at((size_t)s0, (size_t)of.nk, (size_t)c->nmis)); } };
+}
+
 } // namespace timescan

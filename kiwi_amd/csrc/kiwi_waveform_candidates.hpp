@@ -335,4 +335,13 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     for_each_failed_group(c, isrc0, ngroup, K, [&](int g) { fill_failed(1, nmis, cl.at(g, nmis)); });
 }
 
+// kiwi_hip_waveform_candidates_params piece by piece (PieceCall, kiwi_group_run.hpp)
+static PieceCall piece_call(int K, const double *receiver_weight, int anarchy, const Call &cl)
+{
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, cl); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { fill_failed(n / K, c->nmis, cl.at(s0 / K, c->nmis)); },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n / K, K, receiver_weight, anarchy, cl.at(s0 / K, c->nmis)); } };
+}
+
 } // namespace waveform_candidates

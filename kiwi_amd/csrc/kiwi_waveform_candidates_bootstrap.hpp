@@ -326,4 +326,10 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     linfit_candidates_bootstrap::merge(bt, rv.data(), rg.data(), rj.data(), rc.data());
 }
 
+// kiwi_hip_waveform_candidates_bootstrap_params piece by piece: the Gram sibling's PieceCall with this header's check_setup and run
+static PieceCall piece_call(int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const Boot &bt)
+{
+    return linfit_candidates_bootstrap::piece_call(K, of, receiver_weight, anarchy, bt, &check_setup, &run);
+}
+
 } // namespace waveform_candidates_bootstrap

@@ -458,4 +458,18 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     });
 }
 
+// kiwi_hip_waveform_candidates_time_scan_params piece by piece (PieceCall, kiwi_group_run.hpp); the rows have the same layout on
+// every device and in every piece
+static PieceCall piece_call(int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy, const Call &cl)
+{
+    const size_t nk = (size_t)of.nk;
+    auto mine = [=](const kiwi_hip_ctx *c, int s0) { return cl.at((size_t)(s0 / K), (size_t)c->nmis, nk, (size_t)K, row_stride(c, of.max_abs())); };
+    return PieceCall{ K,
+        [=](kiwi_hip_ctx *c) { check_setup(c, K, of, cl); },
+        [=](kiwi_hip_ctx *c, int s0, int n) {
+            fill_failed((size_t)(n / K), (size_t)c->nmis, nk, (size_t)K, row_stride(c, of.max_abs()), mine(c, s0));
+        },
+        [=](kiwi_hip_ctx *c, int s0, int n) { run(c, 0, n / K, K, of, receiver_weight, anarchy, mine(c, s0)); } };
+}
+
 } // namespace waveform_candidates_timescan

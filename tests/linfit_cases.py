@@ -1,5 +1,7 @@
 """Shared inputs of tests/test_linfit.py (CPU, oracle traces) and tests/test_linfit_gpu.py (device traces): the traces of
 groups of basis sources per misfit slot, in the layout tests/linfit_restatement.py takes.  Not a test module."""
+import os
+
 import numpy as np
 
 from kiwi_amd import mtfit, synthetic
@@ -180,3 +182,31 @@ def slots_as_receivers(receivers):
 
 def basis_rows(sourcetype, row):
     return mtfit.elementary_params(sourcetype, np.atleast_2d(row), UNIT)
+
+
+def eikonal_list_with_a_failed_piece(p, unit=2):
+    """For engine p: three groups of `unit` `mt_eikonal` sources, every source of the middle group failing to discretise ("Empty
+    rupture area": above the constraining planes).  In pieces of `unit` sources nothing is uploaded for the middle piece.
+    Returns (the list, the list without the middle group)."""
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eikonal_vectors.npz"))
+    p.set_source_crust(G["rupture_profile"], G["origin_profile"])
+    p.set_source_constraints(np.array([[0, 0, 6500.0], [0, 0, 15500.0]], np.float32), np.array([[0, 0, -1.0], [0, 0, 1.0]], np.float32))
+    eik = np.tile(np.array([0., 0., 0., 10500., 1.0, 80., 70., 100., -50., 2500., 500., 200., 0.8] + [0.] * 6 + [1.5], np.float32), (3 * unit, 1))
+    eik[:, 13:19] = np.random.default_rng(6).standard_normal((3 * unit, 6)) * 1e18
+    eik[unit:2 * unit, 3] = 500.0
+    return eik, np.concatenate([eik[:unit], eik[2 * unit:]])
+
+
+def assert_beside_a_failed_piece(got, alone, arith, what=""):
+    """the arrays of `got` -- three groups (or sources), the middle one failed -- at groups 0 and 2 against `alone`, the same call on
+    the list without the middle group, cut into the same pieces: the plain call's values on the same sources, bit for bit under the
+    exact contract and rtol = 1e-3 under fused"""
+    for i, (a, b) in enumerate(zip(got, alone)):
+        if not isinstance(a, np.ndarray) or a.ndim == 0 or len(a) != 3:
+            continue
+        a = a[[0, 2]]
+        assert a.shape == b.shape, (what, i)
+        if arith == "exact" or a.dtype.kind in "iu":
+            assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), (what, i)
+        else:
+            np.testing.assert_allclose(a, b, rtol=1e-3, equal_nan=True, err_msg="%s %d" % (what, i))

@@ -14,6 +14,7 @@ import pytest
 from kiwi_amd.lib import KiwiHipError
 from tests import common
 from tests.bands_cases import ALL_BANDS, COMPS, FILTER, TD_BANDS, assert_bands_equal, no_rise_list, separate, trial_list
+from tests.linfit_cases import eikonal_list_with_a_failed_piece
 from tests.test_linfit_gpu import build, multi_engine
 
 pytestmark = pytest.mark.gpu
@@ -340,3 +341,22 @@ def test_example_script_runs():
     assert "planted source recovered" in out.stdout, out.stdout
     if common.arith() == "exact":                             # (fused: the two routes' batches differ in shape, see the module's docstring)
         assert "equal the separate evaluations bit for bit: True" in out.stdout, out.stdout
+
+
+# ------------------------------------------------------------------------------------------------ a piece of which nothing is uploaded
+def test_a_piece_in_which_every_source_fails_to_discretise():
+    """three `mt_eikonal` sources in pieces of one, the middle one failing to discretise: nothing is uploaded for that piece.  It reads
+    as zeros, its neighbours as the call without it gives them"""
+    bands = [ALL_BANDS[i] for i in (0, 5, 8, 11)]
+    sc, p = build(None, planted=False)
+    try:
+        eik, good = eikonal_list_with_a_failed_piece(p, 1)
+        p.set_misfit_bands(bands)
+        m, n, g, failings = p.band_misfits_for_params("mt_eikonal", eik, piece=1)
+        assert failings == [1]
+        assert not np.any(m[1]) and not np.any(n[1]) and not np.any(g[1])
+        m2, n2, g2, none = p.band_misfits_for_params("mt_eikonal", good, piece=1)
+        assert none == []
+        assert_bands_equal((m[[0, 2]], n[[0, 2]], g[[0, 2]]), (m2, n2, g2), "sources beside a piece of which nothing is uploaded")
+    finally:
+        p.close()

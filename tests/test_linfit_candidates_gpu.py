@@ -17,7 +17,7 @@ from tests import common
 from tests import linfit_candidates_restatement as cr
 from tests import linfit_restatement as lr
 from tests.common import SYN_RTOL, Scenario, misfit_close
-from tests.linfit_cases import PLANTED, mt_row
+from tests.linfit_cases import PLANTED, assert_beside_a_failed_piece, eikonal_list_with_a_failed_piece, mt_row
 from tests.test_linfit_gpu import COMPS, build, colocated_groups, multi_engine, scattered_groups
 
 pytestmark = pytest.mark.gpu
@@ -335,3 +335,22 @@ def test_example_script_runs():
                          text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "planted mechanism found" in out.stdout and "syntheses saved" in out.stdout
+
+
+# ------------------------------------------------------------------------------------------------ a piece of which nothing is uploaded
+@pytest.mark.parametrize("norm", ["l1norm", "l2norm"])
+def test_a_piece_in_which_every_basis_source_fails_to_discretise(norm):
+    """three groups of two `mt_eikonal` basis sources in pieces of one group, both sources of the middle group failing to discretise:
+    nothing is uploaded for that piece.  Its group reads as a failed group does, its neighbours as the call without it gives them"""
+    sc, p = build(COMPS)
+    try:
+        eik, good = eikonal_list_with_a_failed_piece(p)
+        cand = np.random.default_rng(5).uniform(-1.0, 1.0, (5, 2))
+        kw = dict(outer_norm=norm, receiver_misfit=True, piece=2)
+        got = p.linear_fit_candidates_params("mt_eikonal", eik, 2, cand, **kw)
+        assert list(got.status) == [0, 2, 0]
+        assert got.best_index[1] == -1 and np.isnan(got.best_misfit[1]) and np.all(np.isnan(got.misfit[1]))
+        assert np.all(np.isnan(got.fit_coef[1])) and not np.any(got.receiver_misfit[1]) and not np.any(got.receiver_norm[1])
+        assert_beside_a_failed_piece(got, p.linear_fit_candidates_params("mt_eikonal", good, 2, cand, **kw), common.arith(), norm)
+    finally:
+        p.close()

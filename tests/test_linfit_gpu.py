@@ -16,7 +16,8 @@ from kiwi_amd.lib import KiwiHipError, c_double_p, c_int_p
 from tests import common
 from tests import linfit_restatement as lr
 from tests.common import SYN_RTOL, Scenario, misfit_close, same_bits
-from tests.linfit_cases import PLANTED, UNIT, device_traces, mt_row, slots_as_receivers
+from tests.linfit_cases import (PLANTED, UNIT, assert_beside_a_failed_piece, device_traces, eikonal_list_with_a_failed_piece, mt_row,
+                                slots_as_receivers)
 
 pytestmark = pytest.mark.gpu
 
@@ -448,3 +449,20 @@ def test_example_script_runs():
                          timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "best grid point" in out.stdout
+
+
+# ------------------------------------------------------------------------------------------------ a piece of which nothing is uploaded
+def test_a_piece_in_which_every_basis_source_fails_to_discretise():
+    """three groups of two `mt_eikonal` basis sources in pieces of one group, both sources of the middle group failing to discretise:
+    nothing is uploaded for that piece.  Its group reads as a failed group does, its neighbours as the call without it gives them"""
+    sc, p = build(None, planted=False)
+    try:
+        eik, good = eikonal_list_with_a_failed_piece(p)
+        kw = dict(normal=True, by_receiver=True, piece=2)
+        got = p.linear_fit_params("mt_eikonal", eik, 2, **kw)
+        assert list(got.status) == [0, 2, 0]
+        assert np.all(np.isnan(got.coef[1])) and np.isnan(got.misfit[1])
+        assert got.pivot_min[1] == 0.0 and not np.any(got.normal[1]) and not np.any(got.by_receiver[1])
+        assert_beside_a_failed_piece(got, p.linear_fit_params("mt_eikonal", good, 2, **kw), common.arith())
+    finally:
+        p.close()

@@ -16,6 +16,7 @@ from kiwi_amd.lib import KiwiHipError
 from tests import common
 from tests import timescan_cases as tc
 from tests.bands_cases import ALL_BANDS, assert_bands_equal, separate, trial_list
+from tests.linfit_cases import eikonal_list_with_a_failed_piece
 from tests.test_linfit_gpu import build, multi_engine
 
 pytestmark = pytest.mark.gpu
@@ -355,3 +356,21 @@ def test_example_script_runs():
                          env=env, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "planted time found" in out.stdout and "syntheses saved" in out.stdout, out.stdout
+
+
+# ------------------------------------------------------------------------------------------------ a piece of which nothing is uploaded
+def test_a_piece_in_which_every_source_fails_to_discretise():
+    """three `mt_eikonal` sources in pieces of one, the middle one failing to discretise: nothing is uploaded for that piece.  It reads
+    as zeros with best = -1, its neighbours as the call without it gives them"""
+    sc, p = build(None, planted=False)
+    try:
+        eik, good = eikonal_list_with_a_failed_piece(p, 1)
+        m, n, g, b, failings = p.time_scan_for_params("mt_eikonal", eik, *tc.OFFSETS, piece=1)
+        assert failings == [1] and b[1] == -1
+        assert not np.any(m[1]) and not np.any(n[1]) and not np.any(g[1])
+        m2, n2, g2, b2, none = p.time_scan_for_params("mt_eikonal", good, *tc.OFFSETS, piece=1)
+        assert none == []
+        tc.assert_scan_equal((m[[0, 2]], n[[0, 2]], g[[0, 2]]), (m2, n2, g2), "sources beside a piece of which nothing is uploaded")
+        assert np.array_equal(b[[0, 2]], b2)
+    finally:
+        p.close()

@@ -16,7 +16,7 @@ from kiwi_amd.lib import KiwiHipError, c_double_p, c_float_p, c_int_p
 from tests import common
 from tests import waveform_candidates_restatement as wr
 from tests.common import MISFIT_RTOL, SYN_RTOL, Scenario, misfit_close
-from tests.linfit_cases import UNIT, device_traces, mt_row
+from tests.linfit_cases import UNIT, assert_beside_a_failed_piece, device_traces, eikonal_list_with_a_failed_piece, mt_row
 from tests.test_linfit_gpu import COMPS, build, colocated_groups, multi_engine, scattered_groups
 
 pytestmark = pytest.mark.gpu
@@ -541,3 +541,23 @@ def test_example_script_runs():
                          text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     assert "planted mechanism and depth found" in out.stdout
+
+
+# ------------------------------------------------------------------------------------------------ a piece of which nothing is uploaded
+@pytest.mark.parametrize("method,norm", [(2, "l1norm"), (1, "l2norm")])
+def test_a_piece_in_which_every_basis_source_fails_to_discretise(method, norm):
+    """three groups of two `mt_eikonal` basis sources in pieces of one group, both sources of the middle group failing to discretise:
+    nothing is uploaded for that piece.  Its group reads as a failed group does, its neighbours as the call without it gives them"""
+    sc, p = build(COMPS)
+    try:
+        p.set_misfit_method(NAMES[method])
+        eik, good = eikonal_list_with_a_failed_piece(p)
+        cand = np.random.default_rng(5).uniform(-1.0, 1.0, (5, 2))
+        kw = dict(outer_norm=norm, slot_misfit=True, piece=2)
+        got = p.waveform_candidates_params("mt_eikonal", eik, 2, cand, **kw)
+        assert list(got.status) == [0, 2, 0]
+        assert got.best_index[1] == -1 and np.isnan(got.best_misfit[1]) and np.all(np.isnan(got.misfit[1]))
+        assert not np.any(got.slot_misfit[1]) and not np.any(got.slot_norm[1])
+        assert_beside_a_failed_piece(got, p.waveform_candidates_params("mt_eikonal", good, 2, cand, **kw), common.arith(), norm)
+    finally:
+        p.close()
