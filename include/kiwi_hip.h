@@ -1009,6 +1009,48 @@ int kiwi_hip_get_waveform_candidates_bootstrap_ms(kiwi_hip_ctx *ctx, float ms[5]
  * *max_receivers the most receivers its LDS layout holds (the same for every K); answers without a device.  Non-zero for K outside
  * 1 .. kiwi_hip_linear_fit_max_basis() or a null pointer */
 int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers);
+/* ---- the JOINT BOOTSTRAP of a SPECTRAL candidate search (ampspec_l2norm or ampspec_l1norm inside) over group (location) and
+ * candidate (mechanism) on the device (kiwi_amd/csrc/kiwi_spectral_candidates_bootstrap.hpp): the [candidate][slot] array never
+ * leaves the device.  Nothing new is defined.  Groups, K (1 .. 8), candidates [ncand][K], receiver_weight and anarchy are
+ * kiwi_hip_spectral_candidates'; draw_weights [ndraw][nrec] and outer_norm are kiwi_hip_outer_misfits'.  The context's method must be
+ * ampspec_l2norm or ampspec_l1norm; a misfit filter on a receiver is allowed, as in kiwi_hip_spectral_candidates.  There is no
+ * free scale.
+ * The equality that defines every output: call kiwi_hip_spectral_candidates on the same context with the same arguments, free_scale
+ * 0, slot_misfit and slot_norm requested; read slot_misfit [ngroup][ncand][nmis] as nsrc = ngroup ncand sources of nmis slots,
+ * slot_receiver[m] the receiver of slot m, the norm row of group g repeated for each of its sources; call kiwi_hip_outer_misfits
+ * with the same outer_norm, receiver_weight, anarchy and draw_weights.  Then
+ *   best_value  [ndraw]    is that call's best_value[d], bit for bit
+ *   best_group, best_cand [ndraw]   are its best_index[d] taken apart as g ncand + c.  A draw with every source excluded answers NaN
+ *                          and -1, -1 (kiwi_hip_outer_misfits writes index 0 there: the one deliberate difference)
+ *   group_value, group_cand [ngroup][ndraw], both or both NULL: the same per group -- kiwi_hip_outer_misfits on group g's ncand
+ *                          sources alone
+ *   status      [ngroup]   kiwi_hip_spectral_candidates' 0 / 1 / 2; groups with status 1 or 2 are excluded from every draw
+ * Operation by operation the slot misfits are kiwi_hip_spectral_candidates' and the fold is kiwi_hip_waveform_candidates_bootstrap's
+ * (see there).  Order of "best": excluded last, then the value, then the lowest (g, c).  This order is total, so nothing depends on
+ * tiles, draw passes, chunks (KIWI_HIP_CHUNK_MB), isrc0, piece or the number of devices.
+ * Refused with a message that starts with "spectral_candidates_bootstrap:", nothing approximated: everything
+ * kiwi_hip_spectral_candidates refuses of the set-up; ndraw < 1; null draw_weights, best_* or status; a draw_weights or
+ * receiver_weight entry that is not finite; more receivers than max_receivers of the shape call (a candidate's column of all
+ * receivers stays in LDS); one of the two group_* arrays without the other.  Afterwards the context is what
+ * kiwi_hip_spectral_candidates leaves. */
+int kiwi_hip_spectral_candidates_bootstrap(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                           int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                           const double *draw_weights, double *best_value, int *best_group, int *best_cand, int *status,
+                                           double *group_value, int *group_cand);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it; the per-draw bests of pieces and devices are combined on the host in the same total order,
+ * with the group index of the whole list */
+int kiwi_hip_spectral_candidates_bootstrap_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                  int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                  int anarchy, int ndraw, const double *draw_weights, double *best_value,
+                                                  int *best_group, int *best_cand, int *status, double *group_value, int *group_cand);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] the spectra kernel, ms[2] the slot kernel,
+ * ms[3] bootstrap kernels, ms[4] downloads */
+int kiwi_hip_get_spectral_candidates_bootstrap_ms(kiwi_hip_ctx *ctx, float ms[5]);
+/* how the kernels walk their work: *candidates_per_workgroup (one per lane, of the slot kernel and of the bootstrap kernel),
+ * *draws_per_tile weight rows per LDS tile, *max_receivers the most receivers the bootstrap kernel's LDS layout holds (the same for
+ * every K); answers without a device.  Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() or a null pointer */
+int kiwi_hip_spectral_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers);
 /* the most basis sources per group of the wide fit (one lane of a wavefront per row of the solve): 64; answers without a device */
 int kiwi_hip_linear_fit_wide_max_basis(void);
 /* per (source, receiver, centroid) geometry record of the last eval, 20 floats/ints each

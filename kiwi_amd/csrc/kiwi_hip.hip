@@ -350,6 +350,8 @@ struct kiwi_hip_ctx {
 
     std::vector<EventPair> events;
     std::vector<hipEvent_t> event_pool;
+    // (behind everything else: the members in front keep the places they had before this call came)
+    float speccand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };  // evaluation, spectra kernel, slot kernel, bootstrap kernels, downloads of the last kiwi_hip_spectral_candidates_bootstrap
 
     hipEvent_t get_event()
     {
@@ -1569,6 +1571,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_waveform_candidates_floating.hpp"
 #include "kiwi_waveform_candidates_timescan.hpp"
 #include "kiwi_waveform_candidates_bootstrap.hpp"
+#include "kiwi_spectral_candidates_bootstrap.hpp"
 
 // ================================================================================================
 // pure-read microbenchmark kernels (kiwi_hip_measure_read_bandwidth)
@@ -3691,6 +3694,74 @@ int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_work
     *candidates_per_workgroup = waveform_candidates_bootstrap::kThreads;
     *draws_per_tile = waveform_candidates_bootstrap::kTileD;
     *max_receivers = waveform_candidates_bootstrap::kMaxRec;
+    return 0;
+}
+
+// The joint bootstrap of a candidate search under the amplitude-spectrum norms over group and candidate
+// (kiwi_spectral_candidates_bootstrap.hpp).  The siblings' Boot has arrays for an origin-time offset; here they are the entry's own
+static const char *const kSpecBootBasis = "spectral_candidates_bootstrap: K = ";
+struct SpecBootOffsets {
+    std::vector<int> best, group;
+    SpecBootOffsets(int ngroup, int ndraw, bool per_group)
+        : best((size_t)std::max(ndraw, 1), -1), group(per_group ? (size_t)std::max(ngroup, 0) * (size_t)std::max(ndraw, 0) + 1 : 0, -1) {}
+    linfit_candidates_bootstrap::Boot boot(int ncand, const double *candidates, int outer_norm, int ndraw, const double *draw_weights,
+                                           double *best_value, int *best_group, int *best_cand, int *status, double *group_value,
+                                           int *group_cand, std::mutex *mu)
+    {
+        return linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best.data(), best_cand,
+                                                  status, group_value, group.empty() ? nullptr : group.data(), group_cand, 0, mu };
+    }
+};
+
+int kiwi_hip_spectral_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
+                                           const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                           double *best_value, int *best_group, int *best_cand, int *status, double *group_value,
+                                           int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    zero_ms(c, &kiwi_hip_ctx::speccand_boot_ms);
+    zero_ms(c, &kiwi_hip_ctx::speccand_ms);
+    if (const std::string bad = bad_basis(kSpecBootBasis, K, spectral_candidates::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
+    SpecBootOffsets ofs(ngroup, ndraw, group_value && group_cand);
+    const linfit_candidates_bootstrap::Boot bt = ofs.boot(ncand, candidates, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
+                                                          status, group_value, group_cand, nullptr);
+    const timescan::Offsets none{ 0, 1, 1 };
+    spectral_candidates_bootstrap::check_setup(c, K, none, receiver_weight, bt);
+    bt.begin();
+    spectral_candidates_bootstrap::run(c, isrc0, ngroup, K, none, receiver_weight, anarchy, bt);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_spectral_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                  int ncand, const double *candidates, int outer_norm, const double *receiver_weight,
+                                                  int anarchy, int ndraw, const double *draw_weights, double *best_value, int *best_group,
+                                                  int *best_cand, int *status, double *group_value, int *group_cand)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (const std::string bad = bad_basis(kSpecBootBasis, K, spectral_candidates::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::speccand_boot_ms, true);
+    zero_ms(c, &kiwi_hip_ctx::speccand_ms, true);
+    std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
+    SpecBootOffsets ofs(ngroup, ndraw, group_value && group_cand);
+    const linfit_candidates_bootstrap::Boot bt = ofs.boot(ncand, candidates, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
+                                                          status, group_value, group_cand, &mu);
+    if (ndraw >= 1 && best_value && best_group && best_cand) bt.begin();      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece, spectral_candidates_bootstrap::piece_call(K, receiver_weight, anarchy, bt));
+}
+
+int kiwi_hip_get_spectral_candidates_bootstrap_ms(kiwi_hip_ctx *c, float ms[5])
+{
+    return get_ms(c, &kiwi_hip_ctx::speccand_boot_ms, ms);
+}
+
+int kiwi_hip_spectral_candidates_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
+{
+    if (K < 1 || K > spectral_candidates::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
+    *candidates_per_workgroup = spectral_candidates_bootstrap::kThreads;
+    *draws_per_tile = spectral_candidates_bootstrap::kTileD;
+    *max_receivers = spectral_candidates_bootstrap::kMaxRec;
     return 0;
 }
 

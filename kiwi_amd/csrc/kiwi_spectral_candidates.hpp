@@ -360,9 +360,23 @@ static void launch_any(kiwi_hip_ctx *c, int K, const Args &a, bool free_scale)
     by_basis(K, [&](auto k) { launch<k.value>(c, a, free_scale); });
 }
 
+// what a call built on this one (kiwi_spectral_candidates_bootstrap.hpp) puts in the place of the candidate and fold kernels of every
+// chunk: its device bytes per group; its own candidate kernel on the chunk's spectra, slot table [group][nmis], slot info and fp32
+// candidates; and behind it its kernels on what that one wrote, which also write status [group] (0 or 1).  sl: the host's copy of
+// the slot table.  With a hook speccand_kernel and speccand_fold_kernel are not launched, best_index and best_misfit stay as the
+// caller made them, and the third time of c->speccand_ms is the hook's candidate kernel; the time of its other kernels goes to ms[0]
+struct ChunkHook {
+    size_t per_group = 0;
+    float *ms = nullptr;
+    virtual void candidates(int ng, const float2 *spec, const SlotRec *slots, const SlotInfo *info, const float *x) = 0;
+    virtual void after_candidates(int g0, int ng, const std::vector<SlotRec> &sl, int *status) = 0;
+    virtual ~ChunkHook() = default;
+};
+
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch; adds its HIP-event times to c->speccand_ms: evaluation (run_chunk),
 // the spectra kernel alone, the candidate and fold kernels, the downloads
-static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Call &cl)
+static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Call &cl,
+                ChunkHook *hook = nullptr)
 {
     check_setup(c, K, cl);
     check_group_range("spectral_candidates", c, isrc0, ngroup, K);
@@ -404,7 +418,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         c->speccand_attr = true;
     }
 
-    const PooledEvents<6> ev(c);                           // (ev[5]: immediately in front of the spectra kernel)
+    const PooledEvents<7> ev(c);                           // (ev[5]: immediately in front of the spectra kernel; ev[6]: behind the hook)
     // the kept bins of (slot, variant): from the host mirror of the filter weights, made once per variant and call
     std::map<std::pair<int, int>, std::pair<int, int>> kept;
     auto kept_range = [&](int m, int ntrans, int specofs) {
@@ -428,7 +442,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
     std::vector<float2> spec_h;
     // per group: the spectra of the basis, the slot table, the candidate outputs
     const size_t per_group = c->spec_cplx_per_src * K * sizeof(float2) + (size_t)nmis * sizeof(SlotRec) + ntile * (sizeof(double) + sizeof(int)) +
-                             (size_t)cl.ncand * ((cl.misfit ? sizeof(double) : 0) + (cl.scale ? sizeof(double) : 0) + (cl.slot_misfit ? (size_t)nmis * sizeof(float) : 0));
+                             (size_t)cl.ncand * ((cl.misfit ? sizeof(double) : 0) + (cl.scale ? sizeof(double) : 0) + (cl.slot_misfit ? (size_t)nmis * sizeof(float) : 0)) +
+                             (hook ? hook->per_group : 0);
     int g0 = 0;
     while (g0 < ngroup) {
         const int ng = next_group_chunk(c, isrc0, g0, ngroup, K, 2, per_group, c->fft_cap);
@@ -490,13 +505,22 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         const Args a{ spec_d.p, (const SlotRec *)slots_d.p, (const SlotInfo *)info_d.p, w_d.p, x_d.p, ng, c->method, cl.outer_norm == 2 ? 1 : 0, anarchy ? 1 : 0, cl.ncand,
                       cl.misfit ? mis_d.p : (double *)nullptr, cl.scale ? sc_d.p : (double *)nullptr, cl.slot_misfit ? smis_d.p : (float *)nullptr,
                       tile_v.p, tile_i.p, st_d.p };
-        launch_any(c, K, a, cl.free_scale != 0);
-        hipLaunchKernelGGL(speccand_fold_kernel, dim3((unsigned)ng), dim3(64), 0, c->stream, tile_v.p, tile_i.p, (int)ntile, besti_d.p, bestv_d.p);
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipEventRecord(ev[3], c->stream));
+        if (hook) {
+            hook->candidates(ng, a.spec, a.slots, a.info, a.x);
+            HIPCHECK(hipEventRecord(ev[3], c->stream));
+            hook->after_candidates(g0, ng, sl, st_d.p);
+            HIPCHECK(hipEventRecord(ev[6], c->stream));
+        } else {
+            launch_any(c, K, a, cl.free_scale != 0);
+            hipLaunchKernelGGL(speccand_fold_kernel, dim3((unsigned)ng), dim3(64), 0, c->stream, tile_v.p, tile_i.p, (int)ntile, besti_d.p, bestv_d.p);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipEventRecord(ev[3], c->stream));
+        }
         const Call o = cl.at(g0, nmis, K);
-        HIPCHECK(hipMemcpyAsync(o.best_index, besti_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHECK(hipMemcpyAsync(o.best_misfit, bestv_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (!hook) {
+            HIPCHECK(hipMemcpyAsync(o.best_index, besti_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIPCHECK(hipMemcpyAsync(o.best_misfit, bestv_d.p, (size_t)ng * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHECK(hipMemcpyAsync(o.status, st_d.p, (size_t)ng * sizeof(int), hipMemcpyDeviceToHost, c->stream));
         if (cl.misfit) HIPCHECK(hipMemcpyAsync(o.misfit, mis_d.p, nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         if (cl.scale) HIPCHECK(hipMemcpyAsync(o.scale, sc_d.p, nc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -532,7 +556,8 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *rec
         ev.add_elapsed(c->speccand_ms, 0, 0, 1);
         ev.add_elapsed(c->speccand_ms, 1, 5, 2);
         ev.add_elapsed(c->speccand_ms, 2, 2, 3);
-        ev.add_elapsed(c->speccand_ms, 3, 3, 4);
+        ev.add_elapsed(c->speccand_ms, 3, hook ? 6 : 3, 4);
+        if (hook) ev.add_elapsed(hook->ms, 0, 3, 6);
         g0 += ng;
     }
     leave_evaluated(c, isrc0, ngroup * K, proc_which);

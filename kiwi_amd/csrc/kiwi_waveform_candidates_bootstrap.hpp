@@ -212,6 +212,50 @@ struct Hook : waveform_candidates_timescan::ChunkHook {
     DevBuf<int> first_d, failed_d, slabi_d, grpj_d, grpc_d, rung_d, runj_d, runc_d;
     Hook(kiwi_hip_ctx *ctx, const Boot &b) : c(ctx), bt(b) {}
 
+    // the arrays of the run: the receiver weights, the slots of every receiver, the draws, the running best (NaN, -1).  nrec, nmis
+    // are set
+    void begin(const double *receiver_weight)
+    {
+        const int ndraw = bt.ndraw;
+        const std::vector<double> w = receiver_weights(c, receiver_weight);
+        std::vector<int> rec_first((size_t)nrec + 1, 0);       // (the slots of a receiver lie side by side, receivers ascending)
+        for (int m = 0; m < nmis; m++) rec_first[(size_t)c->comps[(size_t)m].rec + 1]++;
+        for (int r = 0; r < nrec; r++) rec_first[(size_t)r + 1] += rec_first[(size_t)r];
+        const std::vector<double> nanv((size_t)ndraw, std::numeric_limits<double>::quiet_NaN());
+        const std::vector<int> nonev((size_t)ndraw, -1);
+        w_d.alloc((size_t)std::max(nrec, 1), &c->dev_bytes);
+        first_d.alloc((size_t)nrec + 1, &c->dev_bytes);
+        cw_d.alloc((size_t)ndraw * std::max(nrec, 1), &c->dev_bytes);
+        runv_d.alloc((size_t)ndraw, &c->dev_bytes); rung_d.alloc((size_t)ndraw, &c->dev_bytes);
+        runj_d.alloc((size_t)ndraw, &c->dev_bytes); runc_d.alloc((size_t)ndraw, &c->dev_bytes);
+        HIPCHECK(hipMemcpyAsync(w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(first_d.p, rec_first.data(), rec_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(cw_d.p, bt.draw_weights, (size_t)ndraw * nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipMemcpyAsync(runv_d.p, nanv.data(), (size_t)ndraw * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        for (int *p : { rung_d.p, runj_d.p, runc_d.p })
+            HIPCHECK(hipMemcpyAsync(p, nonev.data(), (size_t)ndraw * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(hipStreamSynchronize(c->stream));
+    }
+
+    // the running best of the run comes down and is folded into the bests of the call; the download's HIP-event time is added to
+    // *down_ms
+    void finish(float *down_ms)
+    {
+        const int ndraw = bt.ndraw;
+        std::vector<double> rv((size_t)ndraw);
+        std::vector<int> rg((size_t)ndraw), rj((size_t)ndraw), rc((size_t)ndraw);
+        const PooledEvents<2> ev(c);
+        HIPCHECK(hipEventRecord(ev[0], c->stream));
+        HIPCHECK(hipMemcpyAsync(rv.data(), runv_d.p, (size_t)ndraw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(rg.data(), rung_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(rj.data(), runj_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipMemcpyAsync(rc.data(), runc_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHECK(hipEventRecord(ev[1], c->stream));
+        HIPCHECK(hipStreamSynchronize(c->stream));
+        ev.add_elapsed(down_ms, 0, 0, 1);
+        linfit_candidates_bootstrap::merge(bt, rv.data(), rg.data(), rj.data(), rc.data());
+    }
+
     void after_fold(int g0, int ng, const float *slab, const float *norm) override
     {
         const int ndraw = bt.ndraw;
@@ -284,24 +328,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     float boot_ms = 0.f;
     h.ms = &boot_ms;
 
-    const std::vector<double> w = receiver_weights(c, receiver_weight);
-    std::vector<int> rec_first((size_t)nrec + 1, 0);       // (the slots of a receiver lie side by side, receivers ascending)
-    for (int m = 0; m < nmis; m++) rec_first[(size_t)c->comps[(size_t)m].rec + 1]++;
-    for (int r = 0; r < nrec; r++) rec_first[(size_t)r + 1] += rec_first[(size_t)r];
-    const std::vector<double> nanv((size_t)ndraw, std::numeric_limits<double>::quiet_NaN());
-    const std::vector<int> nonev((size_t)ndraw, -1);
-    h.w_d.alloc((size_t)std::max(nrec, 1), &c->dev_bytes);
-    h.first_d.alloc((size_t)nrec + 1, &c->dev_bytes);
-    h.cw_d.alloc((size_t)ndraw * std::max(nrec, 1), &c->dev_bytes);
-    h.runv_d.alloc((size_t)ndraw, &c->dev_bytes); h.rung_d.alloc((size_t)ndraw, &c->dev_bytes);
-    h.runj_d.alloc((size_t)ndraw, &c->dev_bytes); h.runc_d.alloc((size_t)ndraw, &c->dev_bytes);
-    HIPCHECK(hipMemcpyAsync(h.w_d.p, w.data(), (size_t)nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipMemcpyAsync(h.first_d.p, rec_first.data(), rec_first.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipMemcpyAsync(h.cw_d.p, bt.draw_weights, (size_t)ndraw * nrec * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipMemcpyAsync(h.runv_d.p, nanv.data(), (size_t)ndraw * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    for (int *p : { h.rung_d.p, h.runj_d.p, h.runc_d.p })
-        HIPCHECK(hipMemcpyAsync(p, nonev.data(), (size_t)ndraw * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
+    h.begin(receiver_weight);
 
     float scan_ms[4];
     std::copy(c->wavecand_scan_ms, c->wavecand_scan_ms + 4, scan_ms);
@@ -312,18 +339,7 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     c->wavecand_boot_ms[3] += boot_ms;
     c->wavecand_boot_ms[4] += c->wavecand_scan_ms[3] - scan_ms[3];
 
-    std::vector<double> rv((size_t)ndraw);
-    std::vector<int> rg((size_t)ndraw), rj((size_t)ndraw), rc((size_t)ndraw);
-    const PooledEvents<2> ev(c);
-    HIPCHECK(hipEventRecord(ev[0], c->stream));
-    HIPCHECK(hipMemcpyAsync(rv.data(), h.runv_d.p, (size_t)ndraw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipMemcpyAsync(rg.data(), h.rung_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipMemcpyAsync(rj.data(), h.runj_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipMemcpyAsync(rc.data(), h.runc_d.p, (size_t)ndraw * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(hipEventRecord(ev[1], c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    ev.add_elapsed(c->wavecand_boot_ms, 4, 0, 1);
-    linfit_candidates_bootstrap::merge(bt, rv.data(), rg.data(), rj.data(), rc.data());
+    h.finish(c->wavecand_boot_ms + 4);
 }
 
 // kiwi_hip_waveform_candidates_bootstrap_params piece by piece: the Gram sibling's PieceCall with this header's check_setup and run

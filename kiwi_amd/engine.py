@@ -1164,6 +1164,75 @@ class Engine:
         self._ck(self.L.kiwi_hip_get_spectral_candidates_ms(self.h, _fp(ms)), "get_spectral_candidates_ms")
         return tuple(float(x) for x in ms)
 
+    # ------------------------------------------------------------------ joint bootstrap of a spectral candidate search (kiwi_hip_spectral_candidates_bootstrap)
+    def spectral_candidates_bootstrap_shape(self, K):
+        """(candidates per workgroup, draws per tile, the most receivers) of the spectral bootstrap kernels for K basis sources; no
+        device needed."""
+        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_spectral_candidates_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
+            raise KiwiHipError("spectral_candidates_bootstrap: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(t[0]), int(r[0])
+
+    def _spectral_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group):
+        """the siblings' arrays without the offsets, which this call does not have: best_offset and group_offset of the
+        `CandidateBootstrap` are filled afterwards (0 where there is a best, else -1)"""
+        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
+                                                           "spectral_candidates_bootstrap")
+
+        def args():
+            nd, dw, bv, bg, _, bc, st, gv, _, gc = tail()
+            return nd, dw, bv, bg, bc, st, gv, gc
+
+        def done():
+            out.best_offset[:] = np.where(out.best_cand >= 0, 0, -1)
+            if out.group_offset is not None:
+                out.group_offset[:] = np.where(out.group_cand >= 0, 0, -1)
+            return out
+        return head, args, done
+
+    def spectral_candidates_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, outer_norm="l1norm", receiver_weights=None,
+                                      anarchy=False, per_group=False):
+        """The bootstrap over the receivers of a candidate search under ampspec_l2norm / ampspec_l1norm, joint over group and
+        candidate, on the device (kiwi_hip_spectral_candidates_bootstrap): what `spectral_candidates(..., slot_misfit=True)`
+        followed by `outer_misfits_slots` with `draw_weights[ndraw, nrec]` answers, bit for bit, without the [candidate, slot]
+        array leaving the device.  Returns a `CandidateBootstrap`: best_value[ndraw], best_group, best_cand[ndraw] (NaN and -1
+        where every source of a draw is excluded; best_offset is 0 or -1: there are no offsets), status[ngroup]; per_group=True
+        adds group_value and group_cand[ngroup, ndraw], the same per group.  A row of ones as draw 0 gives the plain winner."""
+        head, args, done = self._spectral_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
+        self._ck(self.L.kiwi_hip_spectral_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *head, 1 if anarchy else 0, *args()),
+                 "spectral_candidates_bootstrap")
+        return done()
+
+    def spectral_candidates_bootstrap_params(self, sourcetype, params, K, candidates, draw_weights, outer_norm="l1norm",
+                                             receiver_weights=None, anarchy=False, per_group=False, piece=0):
+        """`spectral_candidates_bootstrap` for a parameter list of any length, cut into pieces and over the devices at group
+        boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine holds
+        the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("spectral_candidates_bootstrap: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("spectral_candidates_bootstrap: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        head, args, done = self._spectral_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
+        try:
+            self._ck(self.L.kiwi_hip_spectral_candidates_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), *head,
+                                                                          1 if anarchy else 0, *args()), "spectral_candidates_bootstrap")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return done()
+
+    def spectral_candidates_bootstrap_ms(self):
+        """HIP-event durations [ms] of the last `spectral_candidates_bootstrap`: (evaluation, the spectra kernel, the slot kernel,
+        bootstrap kernels, downloads)."""
+        ms = np.zeros(5, np.float32)
+        self._ck(self.L.kiwi_hip_get_spectral_candidates_bootstrap_ms(self.h, _fp(ms)), "get_spectral_candidates_bootstrap_ms")
+        return tuple(float(x) for x in ms)
+
     # ------------------------------------------------------------------ candidates under the time-domain l1norm / l2norm (kiwi_hip_waveform_candidates)
     def waveform_candidates_shape(self, K):
         """(candidates per workgroup, samples per LDS stage) of `waveform_candidates` for K basis sources; needs no device."""

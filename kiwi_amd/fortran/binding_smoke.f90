@@ -66,6 +66,10 @@ program binding_smoke
     if (kiwi_hip_waveform_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 29
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 30
 
+    ! and of a candidate search under the amplitude-spectrum norms: the same bootstrap kernel behind a kernel per slot
+    if (kiwi_hip_spectral_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 31
+    if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 32
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

@@ -237,6 +237,13 @@ def load():
                                                           c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p],
         "kiwi_hip_get_waveform_candidates_bootstrap_ms": [vp, c_float_p],
         "kiwi_hip_waveform_candidates_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
+        "kiwi_hip_spectral_candidates_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int,
+                                                   c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p],
+        "kiwi_hip_spectral_candidates_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int,
+                                                          c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p,
+                                                          c_double_p, c_int_p],
+        "kiwi_hip_get_spectral_candidates_bootstrap_ms": [vp, c_float_p],
+        "kiwi_hip_spectral_candidates_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_get_device_bytes": [vp, C.POINTER(C.c_longlong)],

@@ -475,3 +475,41 @@ def bootstrap_double_couples_waveform(engine, sourcetype, rows, strikes, dips, r
         out.update(rows_strike=pick[..., 0], rows_dip=pick[..., 1], rows_rake=pick[..., 2], rows_moment=mom, rows_offset=boot.group_offset,
                    rows_index=boot.group_cand, rows_misfit=boot.group_value)
     return out
+
+
+def bootstrap_double_couples_spectral(engine, sourcetype, rows, strikes, dips, rakes, moment, draw_weights, outer_norm="l1norm",
+                                      unit=1e18, receiver_weights=None, anarchy=False, piece=0, per_group=False):
+    """The bootstrap over the receivers of `scan_double_couples_spectral`, joint over the rows of rows[N, nparams] (locations) and
+    the grid strikes x dips x rakes (x moments), in ONE call on the device (`Engine.spectral_candidates_bootstrap_params`): the
+    amplitude-spectrum norm inside, `outer_norm` outside under resampling, the slot misfits never leaving the device.  The
+    engine's misfit method is ampspec_l2norm or ampspec_l1norm.  moment [N m] is a number or a sequence (mechanisms x moments, the
+    moment fastest: the moment axis is more candidates); moment=None is refused, the best moment of a direction belongs to one
+    fold, not to a resampled one.  Amplitude spectra leave the polarity open: a mechanism and its opposite (rake + 180) tie, the
+    lower grid index is returned.  draw_weights [ndraw, nrec] as `engine.bootstrap_draw_weights` makes them; put a row of ones in
+    front to get the plain winner as draw 0.  Returns a dict of arrays [ndraw]: row (index into `rows`), strike, dip, rake,
+    moment, index (the candidate's row) and misfit of the best (row, candidate) of every draw -- -1 and NaN for a draw that
+    excludes everything --; status [N]; boot: the `CandidateBootstrap`.  per_group=True adds rows_strike, rows_dip, rows_rake,
+    rows_moment, rows_index and rows_misfit [N, ndraw]: the same per row, the depth profile under resampling."""
+    if moment is None:
+        raise KiwiHipError("bootstrap_double_couples_spectral: moment=None (the best moment per mechanism) is not resampled; give a "
+                           "moment, or a sequence of moments as a further axis of candidates")
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    moments = np.atleast_1d(np.asarray(moment, np.float64))
+    mech, sdr = double_couple_candidates(list(strikes), list(dips), list(rakes), 1.0)
+    cand = (mech[:, None, :] * (moments / float(unit))[None, :, None]).reshape(-1, 6)
+    boot = engine.spectral_candidates_bootstrap_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, draw_weights,
+                                                       outer_norm=outer_norm, receiver_weights=receiver_weights, anarchy=anarchy,
+                                                       per_group=per_group, piece=piece)
+
+    def picked(cand_index):
+        has = cand_index >= 0
+        at = np.where(has, cand_index, 0)
+        return np.where(has[..., None], sdr[at // len(moments)], np.nan), np.where(has, moments[at % len(moments)], np.nan)
+    pick, mom = picked(boot.best_cand)
+    out = dict(row=boot.best_group, strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2], moment=mom, index=boot.best_cand,
+               misfit=boot.best_value, status=boot.status, boot=boot)
+    if per_group:
+        pick, mom = picked(boot.group_cand)
+        out.update(rows_strike=pick[..., 0], rows_dip=pick[..., 1], rows_rake=pick[..., 2], rows_moment=mom, rows_index=boot.group_cand,
+                   rows_misfit=boot.group_value)
+    return out

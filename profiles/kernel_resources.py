@@ -6,11 +6,12 @@ evaluation's time scan (both kiwi_linfit_candidates_timescan.hpp), with per-rece
 its joint bootstrap (kiwi_linfit_candidates_bootstrap.hpp) and
 under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), the time-domain norms (kiwi_waveform_candidates.hpp) and the
 floating time-domain norms (kiwi_waveform_candidates_floating.hpp) and the time-domain norms at many origin times
-(kiwi_waveform_candidates_timescan.hpp) and their joint bootstrap (kiwi_waveform_candidates_bootstrap.hpp), from the
+(kiwi_waveform_candidates_timescan.hpp) and their joint bootstrap (kiwi_waveform_candidates_bootstrap.hpp) and the joint bootstrap
+under the amplitude-spectrum norms (kiwi_spectral_candidates_bootstrap.hpp), from the
 compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
 --text adds the kernels' text sizes in bytes (accumulate families: `make co`, the symbol sizes of the device code object).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating|waveform_candidates_timescan|waveform_candidates_bootstrap]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating|waveform_candidates_timescan|waveform_candidates_bootstrap|spectral_candidates_bootstrap]"""
 import json
 import os
 import re
@@ -49,7 +50,8 @@ def collect_outer():
                                 ("_ZN19spectral_candidates", "spectral_candidates"), ("_ZN19waveform_candidates", "waveform_candidates"),
                                 ("_ZN28waveform_candidates_floating", "waveform_candidates_floating"),
                                 ("_ZN28waveform_candidates_timescan", "waveform_candidates_timescan"),
-                                ("_ZN29waveform_candidates_bootstrap", "waveform_candidates_bootstrap")):
+                                ("_ZN29waveform_candidates_bootstrap", "waveform_candidates_bootstrap"),
+                                ("_ZN29spectral_candidates_bootstrap", "spectral_candidates_bootstrap")):
                 if m.group(1).startswith(prefix):
                     cur = {"family": fam, "arith": "exact", "mangled": m.group(1)}
                     rows.append(cur)
