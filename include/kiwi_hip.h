@@ -771,6 +771,59 @@ int kiwi_hip_get_linear_fit_candidates_floating_ms(kiwi_hip_ctx *ctx, float ms[4
  * accumulators are registers), *shifts_per_stage rows of sums per LDS stage of the candidate kernel; answers without a device.
  * Non-zero for K outside 1 .. kiwi_hip_linear_fit_max_basis() */
 int kiwi_hip_linear_fit_candidates_floating_shape(int K, int *candidates_per_workgroup, int *shifts_per_pass, int *shifts_per_stage);
+/* ---- the JOINT BOOTSTRAP of a candidate search WITH PER-RECEIVER TIME SHIFTS over group (location) and candidate (mechanism) on the
+ * device, with the station delays of every draw's winner (kiwi_amd/csrc/kiwi_linfit_candidates_floating_bootstrap.hpp): neither the
+ * [candidate][receiver] misfits nor the [candidate][receiver] shifts are ever written.  Nothing new is defined.  Groups, K, candidates
+ * [ncand][K], receiver_weight, anarchy and the floating_l2norm set-up are kiwi_hip_linear_fit_candidates_floating's; draw_weights
+ * [ndraw][nrec] and outer_norm are kiwi_hip_outer_misfits'.  There is no origin-time axis and no free_scale.
+ * The equality that defines every output: call kiwi_hip_linear_fit_candidates_floating on the same context with the same arguments,
+ * misfit, cand_shift, receiver_misfit and receiver_norm requested; read receiver_misfit [ngroup][ncand][nrec] as nsrc = ngroup ncand
+ * sources of nmis = nrec slots with slot_receiver = 0 .. nrec - 1, the norm row of group g repeated for each of its sources; call
+ * kiwi_hip_outer_misfits with the same outer_norm, receiver_weight, anarchy and draw_weights.  Then
+ *   best_value  [ndraw]        is that call's best_value[d], bit for bit
+ *   best_group, best_cand [ndraw]   are its best_index[d] taken apart as g ncand + c.  A draw with every source excluded answers NaN,
+ *                              -1, -1 and a row of zero shifts (kiwi_hip_outer_misfits writes index 0 there: the one deliberate
+ *                              difference)
+ *   best_shift  int [ndraw][nrec]   the winner's row cand_shift[best_group][best_cand][.]: the shifts in samples, 0 for a receiver that
+ *                              is disabled or skipped.  An int: a shift range beyond 16 bits, which the parent refuses for its
+ *                              cand_shift array, is served here
+ *   group_value, group_cand [ngroup][ndraw], group_shift int [ngroup][ndraw][nrec], all three or all NULL: the same per group --
+ *                              kiwi_hip_outer_misfits on group g's ncand sources alone
+ *   status      [ngroup]       the parent call's 0 / 1 / 2; groups with status 1 or 2 have zero norms and never win a draw
+ * Operation by operation: m_r = sqrt(min_q val_q) of the parent call ROUNDED TO FLOAT and n_r ROUNDED TO FLOAT, both 0 for a receiver
+ * that is skipped; then kiwi_hip_outer_misfits' prepare step with one slot per receiver (under l2norm sqrt(m m), which is m for a
+ * float; the receiver weight, under anarchy w / N clipped at zero with N the float n_r widened; a = M rw, b = N rw, both squared under
+ * l2norm) and its draw sums ms = ms + a c, ns = ns + b c, receivers ascending from zero, every product and sum rounded on its own;
+ * g = ms / ns, the root under l2norm; excluded where ns <= 0, g < 0 or g is NaN.  The shift of a receiver is chosen per (candidate,
+ * receiver) before any weight is applied: the draws do not interact with the shift search.  Order of "best": excluded last, then the
+ * value, then the lowest (g, c).  This order is total, so nothing depends on tiles, draw passes, chunks (KIWI_HIP_CHUNK_MB), isrc0,
+ * piece or the number of devices.  With every range (0, 0) and outer_norm 1: bit for bit kiwi_hip_linear_fit_candidates_bootstrap
+ * with nk = 1 at offset 0 on a context under l2norm, and every shift 0.
+ * Refused with a message that starts with "linear_fit_candidates_floating_bootstrap:", nothing approximated: everything
+ * kiwi_hip_linear_fit_candidates_floating refuses of the set-up, K, ncand, candidates and outer_norm; ndraw < 1; null draw_weights,
+ * best_* or status; a draw_weights or receiver_weight entry that is not finite; more receivers than max_receivers of the shape call
+ * (a candidate's misfits of all receivers stay in LDS); only some of the three group_* arrays.  Afterwards the context is what
+ * kiwi_hip_linear_fit_candidates_floating leaves. */
+int kiwi_hip_linear_fit_candidates_floating_bootstrap(kiwi_hip_ctx *ctx, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                                      int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                                      const double *draw_weights, double *best_value, int *best_group, int *best_cand,
+                                                      int *best_shift, int *status, double *group_value, int *group_cand, int *group_shift);
+/* ... for a parameter list params[ngroup * K][nparams] of any length, cut into pieces and over devices at group boundaries as
+ * kiwi_hip_linear_fit_params cuts it; the per-draw bests of pieces and devices are combined on the host in the same total order,
+ * with the group index of the whole list, the winner's shift row carried along */
+int kiwi_hip_linear_fit_candidates_floating_bootstrap_params(kiwi_hip_ctx *ctx, int sourcetype, int ngroup, int K, const float *params,
+                                                             int piece, int ncand, const double *candidates, int outer_norm,
+                                                             const double *receiver_weight, int anarchy, int ndraw,
+                                                             const double *draw_weights, double *best_value, int *best_group,
+                                                             int *best_cand, int *best_shift, int *status, double *group_value,
+                                                             int *group_cand, int *group_shift);
+/* HIP-event durations [ms] of the last such call on this context: ms[0] evaluation, ms[1] Gram and cross-correlation kernels,
+ * ms[2] bootstrap kernels (norms, prepare, candidates, folds, shifts), ms[3] downloads */
+int kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms(kiwi_hip_ctx *ctx, float ms[4]);
+/* how the bootstrap kernel walks its work: *candidates_per_workgroup (one per lane), *draws_per_tile weight rows per LDS tile,
+ * *max_receivers the most receivers its LDS layout holds (the same for every K); answers without a device.  Non-zero for K outside
+ * 1 .. kiwi_hip_linear_fit_max_basis() or a null pointer */
+int kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers);
 /* The misfits of many GIVEN coefficient vectors per group under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp): the
  * mechanism grid of a location from its six syntheses where the users of the reference search first, ampspec_l2norm (3) or
  * ampspec_l1norm (4) inside a pass band.  The amplitude spectrum is not quadratic in the coefficients, but the complex spectrum is

@@ -305,6 +305,8 @@ struct kiwi_hip_ctx {
     bool speccand_attr = false;                       // speccand_spectra_kernel may take its dynamic LDS (kiwi_spectral_candidates.hpp)
     unsigned linfit_cand_boot_attr = 0;               // bit K: linfit_candidates_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_bootstrap.hpp)
     float linfit_cand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };       // evaluation, Gram-scan kernel, solve kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_bootstrap
+    unsigned linfit_cand_float_boot_attr = 0;         // bit K: linfit_candidates_float_bootstrap_kernel<K> may take its dynamic LDS (kiwi_linfit_candidates_floating_bootstrap.hpp)
+    float linfit_cand_float_boot_ms[4] = { 0.f, 0.f, 0.f, 0.f };      // evaluation, Gram + xcorr kernels, bootstrap kernels, downloads of the last kiwi_hip_linear_fit_candidates_floating_bootstrap
     bool wavecand_boot_attr = false;                  // wavecand_bootstrap_kernel may take its dynamic LDS (kiwi_waveform_candidates_bootstrap.hpp)
     float wavecand_boot_ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };  // evaluation, rows + scan kernels, fold kernels, bootstrap kernels, downloads of the last kiwi_hip_waveform_candidates_bootstrap
     unsigned linfit_timescan_attr = 0;                // bit K: linfit_scan_gram_kernel<K> may take its dynamic LDS (kiwi_linfit_timescan.hpp)
@@ -1566,6 +1568,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_linfit_timescan.hpp"
 #include "kiwi_linfit_candidates_timescan.hpp"
 #include "kiwi_linfit_candidates_bootstrap.hpp"
+#include "kiwi_linfit_candidates_floating_bootstrap.hpp"
 #include "kiwi_spectral_candidates.hpp"
 #include "kiwi_waveform_candidates.hpp"
 #include "kiwi_waveform_candidates_floating.hpp"
@@ -3885,6 +3888,59 @@ int kiwi_hip_linear_fit_candidates_bootstrap_shape(int K, int *candidates_per_wo
     *candidates_per_workgroup = linfit_candidates_bootstrap::kCandThreads;
     *draws_per_tile = linfit_candidates_bootstrap::kTileD;
     *max_receivers = linfit_candidates_bootstrap::kMaxRec;
+    return 0;
+}
+
+// The joint bootstrap of a candidate search under floating_l2norm over group and candidate, with the winner's shifts of every draw
+// (kiwi_linfit_candidates_floating_bootstrap.hpp)
+static const char *const kCandFloatBootBasis = "linear_fit_candidates_floating_bootstrap: K = ";
+
+int kiwi_hip_linear_fit_candidates_floating_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates,
+                                                      int outer_norm, const double *receiver_weight, int anarchy, int ndraw,
+                                                      const double *draw_weights, double *best_value, int *best_group, int *best_cand,
+                                                      int *best_shift, int *status, double *group_value, int *group_cand, int *group_shift)
+{
+    if (!c) return fail(nullptr, "null context");
+    GUARD_BEGIN_DEV(c)
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_float_boot_ms);
+    if (const std::string bad = bad_basis(kCandFloatBootBasis, K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
+    const linfit_candidates_floating_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
+                                                         best_shift, status, group_value, group_cand, group_shift, 0, nullptr };
+    linfit_candidates_floating_bootstrap::check_setup(c, K, receiver_weight, bt);
+    bt.begin(c->recv.size());
+    linfit_candidates_floating_bootstrap::run(c, isrc0, ngroup, K, receiver_weight, anarchy, bt);
+    return 0;
+    GUARD_END(c)
+}
+
+int kiwi_hip_linear_fit_candidates_floating_bootstrap_params(kiwi_hip_ctx *c, int sourcetype, int ngroup, int K, const float *params, int piece,
+                                                             int ncand, const double *candidates, int outer_norm,
+                                                             const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
+                                                             double *best_value, int *best_group, int *best_cand, int *best_shift, int *status,
+                                                             double *group_value, int *group_cand, int *group_shift)
+{
+    if (!c) return fail(nullptr, "null context");
+    if (const std::string bad = bad_basis(kCandFloatBootBasis, K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
+    zero_ms(c, &kiwi_hip_ctx::linfit_cand_float_boot_ms, true);
+    std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
+    const linfit_candidates_floating_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
+                                                         best_shift, status, group_value, group_cand, group_shift, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_cand && best_shift) bt.begin(c->recv.size());      // (what is missing is refused below)
+    return for_params_impl(c, sourcetype, ngroup * K, params, piece,
+                           linfit_candidates_floating_bootstrap::piece_call(K, receiver_weight, anarchy, bt));
+}
+
+int kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms(kiwi_hip_ctx *c, float ms[4])
+{
+    return get_ms(c, &kiwi_hip_ctx::linfit_cand_float_boot_ms, ms);
+}
+
+int kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(int K, int *candidates_per_workgroup, int *draws_per_tile, int *max_receivers)
+{
+    if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
+    *candidates_per_workgroup = linfit_candidates_floating_bootstrap::kThreads;
+    *draws_per_tile = linfit_candidates_floating_bootstrap::kTileD;
+    *max_receivers = linfit_candidates_floating_bootstrap::kMaxRec;
     return 0;
 }
 

@@ -29,6 +29,8 @@ CandidateTimeScan = collections.namedtuple("CandidateTimeScan", "best_offset bes
                                                                 "fit_status")
 CandidateBootstrap = collections.namedtuple("CandidateBootstrap", "best_value best_group best_offset best_cand status group_value group_offset "
                                             "group_cand")
+CandidateFloatingBootstrap = collections.namedtuple("CandidateFloatingBootstrap", "best_value best_group best_cand best_shift status group_value "
+                                                    "group_cand group_shift")
 SpectralCandidateScan = collections.namedtuple("SpectralCandidateScan", "best_index best_misfit status misfit scale slot_misfit slot_norm "
                                                                         "spectra spectra_range spectra_ref")
 WaveformCandidateScan = collections.namedtuple("WaveformCandidateScan", "best_index best_misfit status misfit slot_misfit slot_norm")
@@ -1070,6 +1072,89 @@ class Engine:
         candidate kernels, downloads)."""
         ms = np.zeros(4, np.float32)
         self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_ms(self.h, _fp(ms)), "get_linear_fit_candidates_floating_ms")
+        return tuple(float(x) for x in ms)
+
+    # ------------------------------------------------------------------ joint bootstrap of a candidate search with shifts (kiwi_hip_linear_fit_candidates_floating_bootstrap)
+    def linear_fit_candidates_floating_bootstrap_shape(self, K):
+        """(candidates per workgroup, draws per tile, the most receivers) of the bootstrap kernel under floating_l2norm for K basis
+        sources; no device needed."""
+        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        if self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
+            raise KiwiHipError("linear_fit_candidates_floating_bootstrap: K = %d basis sources per group; 1 to %d are supported"
+                               % (K, self.linear_fit_max_basis()))
+        return int(c[0]), int(t[0]), int(r[0])
+
+    def _candidate_floating_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group):
+        name = "linear_fit_candidates_floating_bootstrap"
+        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+        if code is None:
+            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != int(K):
+            raise KiwiHipError("%s: candidates must be [ncand, K = %d]" % (name, int(K)))
+        nrec = len(self.components)
+        dw = np.ascontiguousarray(np.asarray(draw_weights, np.float64))
+        if dw.ndim != 2 or dw.shape[1] != nrec:
+            raise KiwiHipError("%s: draw_weights must be [ndraw, %d]" % (name, nrec))
+        ng, nd = int(ngroup), len(dw)
+        grp = (ng, nd) if per_group else None
+        out = CandidateFloatingBootstrap(np.zeros(nd), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros((nd, nrec), np.int32),
+                                         np.zeros(ng, np.int32), np.zeros(grp) if grp else None, np.zeros(grp, np.int32) if grp else None,
+                                         np.zeros(grp + (nrec,), np.int32) if grp else None)
+        ipn = lambda a: None if a is None else _ip(a)                                  # noqa: E731
+        head = (len(x), dp(x), code, dp(w))
+        tail = lambda: (nd, dp(dw), dp(out.best_value), _ip(out.best_group), _ip(out.best_cand), _ip(out.best_shift), _ip(out.status),      # noqa: E731
+                        dp(out.group_value), ipn(out.group_cand), ipn(out.group_shift))
+        return head, out, tail
+
+    def linear_fit_candidates_floating_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, outer_norm="l1norm",
+                                                 receiver_weights=None, anarchy=False, per_group=False):
+        """The bootstrap over the receivers of a candidate search under floating_l2norm, joint over group and candidate, on the
+        device (kiwi_hip_linear_fit_candidates_floating_bootstrap): what `linear_fit_candidates_floating(..., cand_shift=True,
+        receiver_misfit=True)` followed by `outer_misfits` with `draw_weights[ndraw, nrec]` answers, bit for bit, without the
+        [candidate, receiver] matrices.  Returns a `CandidateFloatingBootstrap`: best_value[ndraw], best_group, best_cand[ndraw]
+        (NaN and -1 where every source of a draw is excluded), best_shift[ndraw, nrec] (the winner's shifts in SAMPLES, 0 for
+        receivers that do not count), status[ngroup]; per_group=True adds group_value, group_cand[ngroup, ndraw] and
+        group_shift[ngroup, ndraw, nrec], the same per group.  A row of ones as draw 0 gives the plain winner."""
+        head, out, tail = self._candidate_floating_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights,
+                                                                    per_group)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *head,
+                                                                          1 if anarchy else 0, *tail()),
+                 "linear_fit_candidates_floating_bootstrap")
+        return out
+
+    def linear_fit_candidates_floating_bootstrap_params(self, sourcetype, params, K, candidates, draw_weights, outer_norm="l1norm",
+                                                        receiver_weights=None, anarchy=False, per_group=False, piece=0):
+        """`linear_fit_candidates_floating_bootstrap` for a parameter list of any length, cut into pieces and over the devices at
+        group boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine
+        holds the head of the list."""
+        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
+        st = SOURCE_TYPES.get(sourcetype, sourcetype)
+        K = int(K)
+        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
+            raise KiwiHipError("set_source_params: wrong number of source parameters")
+        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
+            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
+        ngroup = p.shape[0] // K
+        head, out, tail = self._candidate_floating_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights,
+                                                                    per_group)
+        try:
+            self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), *head,
+                                                                                     1 if anarchy else 0, *tail()),
+                     "linear_fit_candidates_floating_bootstrap")
+        except KiwiHipError:
+            self.nsrc = 0
+            raise
+        self.nsrc = self._uploaded_sources(len(p))
+        return out
+
+    def linear_fit_candidates_floating_bootstrap_ms(self):
+        """HIP-event durations [ms] of the last `linear_fit_candidates_floating_bootstrap`: (evaluation, Gram and cross-correlation
+        kernels, bootstrap kernels, downloads)."""
+        ms = np.zeros(4, np.float32)
+        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms(self.h, _fp(ms)),
+                 "get_linear_fit_candidates_floating_bootstrap_ms")
         return tuple(float(x) for x in ms)
 
     # ------------------------------------------------------------------ candidates under the amplitude-spectrum norms (kiwi_hip_spectral_candidates)

@@ -70,6 +70,10 @@ program binding_smoke
     if (kiwi_hip_spectral_candidates_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 31
     if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 32
 
+    ! and of a candidate search with per-receiver shifts: a candidate's float column per receiver stays in LDS
+    if (kiwi_hip_linear_fit_candidates_floating_bootstrap_shape( 6_c_int, per_group, per_pass, per_stage ) /= 0) stop 33
+    if (per_group < 64 .or. per_pass < 1 .or. per_stage < 64) stop 34
+
     rc = kiwi_hip_init( 0_c_int, ctx )
     if (rc == 0) then
         print '(a)', 'device context ok'

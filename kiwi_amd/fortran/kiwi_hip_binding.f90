@@ -845,6 +845,55 @@ module kiwi_hip_binding
             integer(c_int), intent(out) :: candidates_per_workgroup, shifts_per_pass, shifts_per_stage
         end function
 
+        ! the bootstrap over the receivers of a candidate search under floating_l2norm, joint over group and candidate, on the device,
+        ! with the shifts of every draw's winner
+        integer(c_int) function kiwi_hip_linear_fit_candidates_floating_bootstrap( ctx, isrc0, ngroup, k, ncand, candidates, &
+                outer_norm, receiver_weight, anarchy, ndraw, draw_weights, best_value, best_group, best_cand, best_shift, status, &
+                group_value, group_cand, group_shift ) bind(C, name='kiwi_hip_linear_fit_candidates_floating_bootstrap')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: isrc0, ngroup, k, ncand, outer_norm, anarchy, ndraw      ! isrc0 0-based
+            real(c_double), intent(in) :: candidates(*)   ! (k, ncand)
+            type(c_ptr), value :: receiver_weight         ! c_loc of real(c_double) (nrec), or c_null_ptr = ones
+            real(c_double), intent(in) :: draw_weights(*) ! (nrec, ndraw)
+            real(c_double), intent(out) :: best_value(*)  ! (ndraw); NaN where every source of the draw is excluded
+            integer(c_int), intent(out) :: best_group(*), best_cand(*)    ! (ndraw): 0-based, -1 if none
+            integer(c_int), intent(out) :: best_shift(*)  ! (nrec, ndraw): the winner's shifts in samples
+            integer(c_int), intent(out) :: status(*)      ! (ngroup)
+            type(c_ptr), value :: group_value             ! c_loc of real(c_double) (ndraw, ngroup), or c_null_ptr
+            type(c_ptr), value :: group_cand              ! c_loc of integer(c_int) (ndraw, ngroup)
+            type(c_ptr), value :: group_shift             ! c_loc of integer(c_int) (nrec, ndraw, ngroup); all three or none
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_floating_bootstrap_params( ctx, sourcetype, ngroup, k, params, piece, &
+                ncand, candidates, outer_norm, receiver_weight, anarchy, ndraw, draw_weights, best_value, best_group, best_cand, &
+                best_shift, status, group_value, group_cand, group_shift ) &
+                bind(C, name='kiwi_hip_linear_fit_candidates_floating_bootstrap_params')
+            import :: c_int, c_ptr, c_float, c_double
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: sourcetype, ngroup, k, piece, ncand, outer_norm, anarchy, ndraw
+            real(c_float), intent(in) :: params(*)        ! (nparams, k, ngroup)
+            real(c_double), intent(in) :: candidates(*), draw_weights(*)
+            type(c_ptr), value :: receiver_weight
+            real(c_double), intent(out) :: best_value(*)
+            integer(c_int), intent(out) :: best_group(*), best_cand(*), best_shift(*), status(*)
+            type(c_ptr), value :: group_value, group_cand, group_shift    ! as in kiwi_hip_linear_fit_candidates_floating_bootstrap
+        end function
+
+        integer(c_int) function kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms( ctx, ms ) &
+                bind(C, name='kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms')
+            import :: c_int, c_ptr, c_float
+            type(c_ptr), value :: ctx
+            real(c_float), intent(out) :: ms(4)                 ! evaluation, Gram + xcorr kernels, bootstrap kernels, downloads
+        end function
+
+        integer(c_int) function kiwi_hip_linear_fit_candidates_floating_bootstrap_shape( k, candidates_per_workgroup, draws_per_tile, &
+                max_receivers ) bind(C, name='kiwi_hip_linear_fit_candidates_floating_bootstrap_shape')
+            import :: c_int
+            integer(c_int), value :: k
+            integer(c_int), intent(out) :: candidates_per_workgroup, draws_per_tile, max_receivers
+        end function
+
         ! the candidate evaluation under the amplitude-spectrum norms from the spectra of the basis sources
         integer(c_int) function kiwi_hip_spectral_candidates( ctx, isrc0, ngroup, k, ncand, candidates, outer_norm, receiver_weight, &
                 anarchy, free_scale, best_index, best_misfit, status, misfit, scale, slot_misfit, slot_norm, spectra_bins, spectra, &

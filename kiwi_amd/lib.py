@@ -199,6 +199,14 @@ def load():
                                                            C.POINTER(C.c_short), c_float_p, c_float_p],
         "kiwi_hip_get_linear_fit_candidates_floating_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_floating_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
+        "kiwi_hip_linear_fit_candidates_floating_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int,
+                                                              C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p,
+                                                              c_int_p, c_int_p],
+        "kiwi_hip_linear_fit_candidates_floating_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p,
+                                                                     C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p,
+                                                                     c_int_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p],
+        "kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms": [vp, c_float_p],
+        "kiwi_hip_linear_fit_candidates_floating_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_spectral_candidates": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, c_int_p,
                                          c_double_p, c_int_p, c_double_p, c_double_p, c_float_p, c_float_p, C.c_int, c_float_p, c_int_p,
                                          c_float_p],

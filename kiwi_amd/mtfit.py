@@ -285,6 +285,38 @@ def scan_double_couples_floating(engine, sourcetype, params, strikes, dips, rake
     return out
 
 
+def bootstrap_double_couples_floating(engine, sourcetype, rows, strikes, dips, rakes, draw_weights, moment=1e18, outer_norm="l1norm",
+                                      unit=1e18, receiver_weights=None, anarchy=False, piece=0, per_group=False):
+    """The bootstrap over the receivers of `scan_double_couples_floating`, joint over the rows of rows[N, nparams] (locations) and
+    the grid strikes x dips x rakes, in ONE call on the device (`Engine.linear_fit_candidates_floating_bootstrap_params`): the
+    engine's misfit method is floating_l2norm and every receiver has its own range of whole-sample shifts.  draw_weights
+    [ndraw, nrec] as `engine.bootstrap_draw_weights` makes them; put a row of ones in front to get the plain winner as draw 0.
+    All mechanisms have the scalar moment `moment` [N m].  Returns a dict of arrays [ndraw]: row (index into `rows`), strike, dip,
+    rake, moment, index (the mechanism's row in the grid) and misfit of the best (row, mechanism) of every draw -- -1 and NaN for
+    a draw that excludes everything --; shifts [ndraw, nrec]: that winner's shift of every receiver in SECONDS (0 for receivers
+    that do not count): how stable each station's delay is under resampling; status [N]; boot: the `CandidateFloatingBootstrap`.
+    per_group=True adds rows_strike, rows_dip, rows_rake, rows_index, rows_misfit [N, ndraw] and rows_shifts [N, ndraw, nrec]: the
+    same per row, the depth profile under resampling."""
+    p = np.atleast_2d(np.asarray(rows, np.float32))
+    cand, sdr = double_couple_candidates(list(strikes), list(dips), list(rakes), float(moment) / float(unit))
+    boot = engine.linear_fit_candidates_floating_bootstrap_params(sourcetype, elementary_params(sourcetype, p, unit), 6, cand, draw_weights,
+                                                                  outer_norm=outer_norm, receiver_weights=receiver_weights, anarchy=anarchy,
+                                                                  per_group=per_group, piece=piece)
+
+    def angles(cand_index):
+        has = cand_index >= 0
+        return np.where(has[..., None], sdr[np.where(has, cand_index, 0)], np.nan)
+    pick = angles(boot.best_cand)
+    out = dict(row=boot.best_group, strike=pick[:, 0], dip=pick[:, 1], rake=pick[:, 2],
+               moment=np.where(boot.best_cand >= 0, float(moment), np.nan), index=boot.best_cand, misfit=boot.best_value,
+               shifts=boot.best_shift * float(engine.dt), status=boot.status, boot=boot)
+    if per_group:
+        pick = angles(boot.group_cand)
+        out.update(rows_strike=pick[..., 0], rows_dip=pick[..., 1], rows_rake=pick[..., 2], rows_index=boot.group_cand,
+                   rows_misfit=boot.group_value, rows_shifts=boot.group_shift * float(engine.dt))
+    return out
+
+
 def scan_double_couples_spectral(engine, sourcetype, params, strikes, dips, rakes, moment=None, outer_norm="l1norm", unit=1e18,
                                  receiver_weights=None, anarchy=False, piece=0, cube=False, slot_misfit=False):
     """`scan_double_couples` under the amplitude-spectrum norms (`Engine.spectral_candidates_params`): the engine's misfit method
