@@ -1567,6 +1567,7 @@ int eval_impl(kiwi_hip_ctx *c, int isrc0, int nsrc, int proc_which)
 #include "kiwi_timescan.hpp"
 #include "kiwi_linfit_timescan.hpp"
 #include "kiwi_linfit_candidates_timescan.hpp"
+#include "kiwi_candidates_bootstrap.hpp"
 #include "kiwi_linfit_candidates_bootstrap.hpp"
 #include "kiwi_linfit_candidates_floating_bootstrap.hpp"
 #include "kiwi_spectral_candidates.hpp"
@@ -3658,11 +3659,11 @@ int kiwi_hip_waveform_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngrou
     zero_ms(c, &kiwi_hip_ctx::wavecand_boot_ms);
     zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms);
     if (const std::string bad = bad_basis(kWaveBootBasis, K, waveform_candidates_timescan::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
-    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
-                                                status, group_value, group_offset, group_cand, 0, nullptr };
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, best_offset, group_offset, nullptr, nullptr, 0, nullptr };
     const timescan::Offsets of{ k0, kstep, nk };
     waveform_candidates_bootstrap::check_setup(c, K, of, receiver_weight, bt);
-    bt.begin();
+    bt.begin(c->recv.size());
     waveform_candidates_bootstrap::run(c, isrc0, ngroup, K, of, receiver_weight, anarchy, bt);
     return 0;
     GUARD_END(c)
@@ -3679,9 +3680,9 @@ int kiwi_hip_waveform_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetyp
     zero_ms(c, &kiwi_hip_ctx::wavecand_boot_ms, true);
     zero_ms(c, &kiwi_hip_ctx::wavecand_scan_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
-                                                status, group_value, group_offset, group_cand, 0, &mu };
-    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin();      // (what is missing is refused below)
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, best_offset, group_offset, nullptr, nullptr, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin(c->recv.size());      // (what is missing is refused below)
     return for_params_impl(c, sourcetype, ngroup * K, params, piece,
                            waveform_candidates_bootstrap::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, bt));
 }
@@ -3695,26 +3696,14 @@ int kiwi_hip_waveform_candidates_bootstrap_shape(int K, int *candidates_per_work
 {
     if (K < 1 || K > waveform_candidates_timescan::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
     *candidates_per_workgroup = waveform_candidates_bootstrap::kThreads;
-    *draws_per_tile = waveform_candidates_bootstrap::kTileD;
+    *draws_per_tile = candidates_bootstrap::kTileD;
     *max_receivers = waveform_candidates_bootstrap::kMaxRec;
     return 0;
 }
 
 // The joint bootstrap of a candidate search under the amplitude-spectrum norms over group and candidate
-// (kiwi_spectral_candidates_bootstrap.hpp).  The siblings' Boot has arrays for an origin-time offset; here they are the entry's own
+// (kiwi_spectral_candidates_bootstrap.hpp)
 static const char *const kSpecBootBasis = "spectral_candidates_bootstrap: K = ";
-struct SpecBootOffsets {
-    std::vector<int> best, group;
-    SpecBootOffsets(int ngroup, int ndraw, bool per_group)
-        : best((size_t)std::max(ndraw, 1), -1), group(per_group ? (size_t)std::max(ngroup, 0) * (size_t)std::max(ndraw, 0) + 1 : 0, -1) {}
-    linfit_candidates_bootstrap::Boot boot(int ncand, const double *candidates, int outer_norm, int ndraw, const double *draw_weights,
-                                           double *best_value, int *best_group, int *best_cand, int *status, double *group_value,
-                                           int *group_cand, std::mutex *mu)
-    {
-        return linfit_candidates_bootstrap::Boot{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best.data(), best_cand,
-                                                  status, group_value, group.empty() ? nullptr : group.data(), group_cand, 0, mu };
-    }
-};
 
 int kiwi_hip_spectral_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, int ncand, const double *candidates, int outer_norm,
                                            const double *receiver_weight, int anarchy, int ndraw, const double *draw_weights,
@@ -3726,13 +3715,11 @@ int kiwi_hip_spectral_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngrou
     zero_ms(c, &kiwi_hip_ctx::speccand_boot_ms);
     zero_ms(c, &kiwi_hip_ctx::speccand_ms);
     if (const std::string bad = bad_basis(kSpecBootBasis, K, spectral_candidates::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
-    SpecBootOffsets ofs(ngroup, ndraw, group_value && group_cand);
-    const linfit_candidates_bootstrap::Boot bt = ofs.boot(ncand, candidates, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
-                                                          status, group_value, group_cand, nullptr);
-    const timescan::Offsets none{ 0, 1, 1 };
-    spectral_candidates_bootstrap::check_setup(c, K, none, receiver_weight, bt);
-    bt.begin();
-    spectral_candidates_bootstrap::run(c, isrc0, ngroup, K, none, receiver_weight, anarchy, bt);
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, nullptr, nullptr, nullptr, nullptr, 0, nullptr };
+    spectral_candidates_bootstrap::check_setup(c, K, receiver_weight, bt);
+    bt.begin(c->recv.size());
+    spectral_candidates_bootstrap::run(c, isrc0, ngroup, K, receiver_weight, anarchy, bt);
     return 0;
     GUARD_END(c)
 }
@@ -3747,10 +3734,9 @@ int kiwi_hip_spectral_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcetyp
     zero_ms(c, &kiwi_hip_ctx::speccand_boot_ms, true);
     zero_ms(c, &kiwi_hip_ctx::speccand_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    SpecBootOffsets ofs(ngroup, ndraw, group_value && group_cand);
-    const linfit_candidates_bootstrap::Boot bt = ofs.boot(ncand, candidates, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
-                                                          status, group_value, group_cand, &mu);
-    if (ndraw >= 1 && best_value && best_group && best_cand) bt.begin();      // (what is missing is refused below)
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, nullptr, nullptr, nullptr, nullptr, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_cand) bt.begin(c->recv.size());      // (what is missing is refused below)
     return for_params_impl(c, sourcetype, ngroup * K, params, piece, spectral_candidates_bootstrap::piece_call(K, receiver_weight, anarchy, bt));
 }
 
@@ -3763,7 +3749,7 @@ int kiwi_hip_spectral_candidates_bootstrap_shape(int K, int *candidates_per_work
 {
     if (K < 1 || K > spectral_candidates::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
     *candidates_per_workgroup = spectral_candidates_bootstrap::kThreads;
-    *draws_per_tile = spectral_candidates_bootstrap::kTileD;
+    *draws_per_tile = candidates_bootstrap::kTileD;
     *max_receivers = spectral_candidates_bootstrap::kMaxRec;
     return 0;
 }
@@ -3850,11 +3836,11 @@ int kiwi_hip_linear_fit_candidates_bootstrap(kiwi_hip_ctx *c, int isrc0, int ngr
     GUARD_BEGIN_DEV(c)
     zero_ms(c, &kiwi_hip_ctx::linfit_cand_boot_ms);
     if (const std::string bad = bad_basis(kCandBootBasis, K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
-    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
-                                                status, group_value, group_offset, group_cand, 0, nullptr };
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, best_offset, group_offset, nullptr, nullptr, 0, nullptr };
     const timescan::Offsets of{ k0, kstep, nk };
     linfit_candidates_bootstrap::check_setup(c, K, of, receiver_weight, bt);
-    bt.begin();
+    bt.begin(c->recv.size());
     linfit_candidates_bootstrap::run(c, isrc0, ngroup, K, of, receiver_weight, anarchy, bt);
     return 0;
     GUARD_END(c)
@@ -3870,9 +3856,9 @@ int kiwi_hip_linear_fit_candidates_bootstrap_params(kiwi_hip_ctx *c, int sourcet
     if (const std::string bad = bad_basis(kCandBootBasis, K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
     zero_ms(c, &kiwi_hip_ctx::linfit_cand_boot_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    const linfit_candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_offset, best_cand,
-                                                status, group_value, group_offset, group_cand, 0, &mu };
-    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin();      // (what is missing is refused below)
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, best_offset, group_offset, nullptr, nullptr, 0, &mu };
+    if (ndraw >= 1 && best_value && best_group && best_offset && best_cand) bt.begin(c->recv.size());      // (what is missing is refused below)
     return for_params_impl(c, sourcetype, ngroup * K, params, piece,
                            linfit_candidates_bootstrap::piece_call(K, timescan::Offsets{ k0, kstep, nk }, receiver_weight, anarchy, bt));
 }
@@ -3886,7 +3872,7 @@ int kiwi_hip_linear_fit_candidates_bootstrap_shape(int K, int *candidates_per_wo
 {
     if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
     *candidates_per_workgroup = linfit_candidates_bootstrap::kCandThreads;
-    *draws_per_tile = linfit_candidates_bootstrap::kTileD;
+    *draws_per_tile = candidates_bootstrap::kTileD;
     *max_receivers = linfit_candidates_bootstrap::kMaxRec;
     return 0;
 }
@@ -3904,8 +3890,8 @@ int kiwi_hip_linear_fit_candidates_floating_bootstrap(kiwi_hip_ctx *c, int isrc0
     GUARD_BEGIN_DEV(c)
     zero_ms(c, &kiwi_hip_ctx::linfit_cand_float_boot_ms);
     if (const std::string bad = bad_basis(kCandFloatBootBasis, K, linfit::kMaxBasis); !bad.empty()) throw std::runtime_error(bad);
-    const linfit_candidates_floating_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
-                                                         best_shift, status, group_value, group_cand, group_shift, 0, nullptr };
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, nullptr, nullptr, best_shift, group_shift, 0, nullptr };
     linfit_candidates_floating_bootstrap::check_setup(c, K, receiver_weight, bt);
     bt.begin(c->recv.size());
     linfit_candidates_floating_bootstrap::run(c, isrc0, ngroup, K, receiver_weight, anarchy, bt);
@@ -3923,8 +3909,8 @@ int kiwi_hip_linear_fit_candidates_floating_bootstrap_params(kiwi_hip_ctx *c, in
     if (const std::string bad = bad_basis(kCandFloatBootBasis, K, linfit::kMaxBasis, &ngroup); !bad.empty()) return fail(c, bad);
     zero_ms(c, &kiwi_hip_ctx::linfit_cand_float_boot_ms, true);
     std::mutex mu;                                          // (the devices' runs fold their bests into the same arrays)
-    const linfit_candidates_floating_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand,
-                                                         best_shift, status, group_value, group_cand, group_shift, 0, &mu };
+    const candidates_bootstrap::Boot bt{ candidates, ncand, outer_norm, ndraw, draw_weights, best_value, best_group, best_cand, status,
+                                         group_value, group_cand, nullptr, nullptr, best_shift, group_shift, 0, &mu };
     if (ndraw >= 1 && best_value && best_group && best_cand && best_shift) bt.begin(c->recv.size());      // (what is missing is refused below)
     return for_params_impl(c, sourcetype, ngroup * K, params, piece,
                            linfit_candidates_floating_bootstrap::piece_call(K, receiver_weight, anarchy, bt));
@@ -3939,7 +3925,7 @@ int kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(int K, int *candidat
 {
     if (K < 1 || K > linfit::kMaxBasis || !candidates_per_workgroup || !draws_per_tile || !max_receivers) return 1;
     *candidates_per_workgroup = linfit_candidates_floating_bootstrap::kThreads;
-    *draws_per_tile = linfit_candidates_floating_bootstrap::kTileD;
+    *draws_per_tile = candidates_bootstrap::kTileD;
     *max_receivers = linfit_candidates_floating_bootstrap::kMaxRec;
     return 0;
 }

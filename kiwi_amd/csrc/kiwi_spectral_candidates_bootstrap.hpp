@@ -23,22 +23,21 @@
 //       (profiles/spectral_candidates_bootstrap_kernel_resources.json).
 //   wavecand_bootstrap_prepare_kernel, wavecand_bootstrap_kernel   kiwi_waveform_candidates_bootstrap.hpp's, unchanged, with
 //       nk = 1: the norm side from the chunk's slot norms (SlotRec::norm) as a float [group][nmis] array, then the slab folded per
-//       receiver and the draw loop.  bootstrap_fold_kernel and bootstrap_best_kernel of kiwi_linfit_candidates_bootstrap.hpp behind.
+//       receiver and the draw walk; the fold kernels and the run's arrays of kiwi_candidates_bootstrap.hpp behind, through the
+//       waveform sibling's Hook.
 //   speccand_boot_status_kernel   one thread per group: ns = 0; ns = ns + b_r 1.0, r ascending, with the prepare kernel's b -- the
 //       denominator of speccand_kernel's fold --; status 0 where ns > 0, else 1.  The host sets 2 for a failed group.
-// The order of "best" is total -- excluded last, then the smaller value, then the lowest (g, c) --, so no answer depends on tiles,
-// draw passes, chunks (KIWI_HIP_CHUNK_MB), isrc0, pieces or devices.  A draw with every source excluded: NaN, -1, -1 -- the one
-// difference from the host route, which answers NaN and index 0.  The receiver limit is the waveform sibling's kMaxRec.
+// A draw with every source excluded: NaN, -1, -1 -- the one difference from the host route, which answers NaN and index 0.  There are
+// no origin times: Boot's offset arrays are null.  The receiver limit is the waveform sibling's kMaxRec.
 
 namespace spectral_candidates_bootstrap {
 
-using linfit_candidates_bootstrap::Boot;
+using candidates_bootstrap::Boot;
 using spectral_candidates::kThreads;
 using spectral_candidates::kStage;
 using spectral_candidates::SlotRec;
 using spectral_candidates::SlotInfo;
 using spectral_candidates::amp_rn;
-using waveform_candidates_bootstrap::kTileD;
 using waveform_candidates_bootstrap::kMaxRec;
 
 static const char *const kName = "spectral_candidates_bootstrap";
@@ -114,27 +113,12 @@ static spectral_candidates::Call parent_call(const Boot &bt, int *best_index, do
 }
 
 // what the call cannot do is refused before anything runs: everything kiwi_hip_spectral_candidates refuses of the set-up, and what
-// the draws add.  (The offsets are the siblings' argument of linfit_candidates_bootstrap::piece_call; there are none here, and
-// bt.best_offset and bt.group_offset are arrays of the entry, not of the caller)
-static void check_setup(kiwi_hip_ctx *c, int K, const timescan::Offsets &, const double *receiver_weight, const Boot &bt)
+// the draws add
+static void check_setup(kiwi_hip_ctx *c, int K, const double *receiver_weight, const Boot &bt)
 {
-    refusing(kName, [&] {
-        if (bt.ndraw < 1) throw std::runtime_error("ndraw = " + std::to_string(bt.ndraw) + "; at least one draw is needed");
-        if (!bt.draw_weights || !bt.best_value || !bt.best_group || !bt.best_cand || !bt.status)
-            throw std::runtime_error("null draw_weights, best_value, best_group, best_cand or status array");
-        if ((bt.group_value == nullptr) != (bt.group_cand == nullptr)) throw std::runtime_error("group_value and group_cand are given both or not at all");
+    candidates_bootstrap::check_draws(kName, c, candidates_bootstrap::Extra::none, kMaxRec, receiver_weight, bt, [&] {
         int idummy = 0; double ddummy = 0.0;               // (the parent's arrays: checked for null only)
         spectral_candidates::check_setup(c, K, parent_call(bt, &idummy, &ddummy));
-        const size_t nrec = c->recv.size();
-        if (nrec > (size_t)kMaxRec)
-            throw std::runtime_error(std::to_string(nrec) + " receivers; a candidate's misfits of all receivers stay in LDS, which holds at most " +
-                                     std::to_string(kMaxRec));
-        if (receiver_weight)
-            for (size_t r = 0; r < nrec; r++)
-                if (!std::isfinite(receiver_weight[r])) throw std::runtime_error("receiver_weight of receiver " + std::to_string(r + 1) + " is not finite");
-        for (size_t p = 0; p < (size_t)bt.ndraw * nrec; p++)
-            if (!std::isfinite(bt.draw_weights[p]))
-                throw std::runtime_error("draw_weights of draw " + std::to_string(p / nrec) + ", receiver " + std::to_string(p % nrec + 1) + " is not finite");
     });
 }
 
@@ -144,14 +128,18 @@ struct Hook : spectral_candidates::ChunkHook {
     waveform_candidates_bootstrap::Hook wb;
     std::vector<float> norm_h;
     DevBuf<float> slab_d, norm_d;
-    Hook(kiwi_hip_ctx *ctx, const Boot &bt, int k) : c(ctx), K(k), wb(ctx, bt) {}
+    Hook(kiwi_hip_ctx *ctx, const Boot &bt, int isrc0, int k, int anarchy) : c(ctx), K(k), wb(ctx, bt, isrc0, k, 1, anarchy)
+    {
+        // per group: the slab of slot misfits and the norm row, and what the waveform hook counts
+        per_group = (size_t)bt.ncand * wb.nmis * sizeof(float) + (size_t)wb.nmis * sizeof(float) + wb.per_group;
+    }
 
     void candidates(int ng, const float2 *spec, const SlotRec *slots, const SlotInfo *info, const float *x) override
     {
-        const int nmis = wb.nmis, ncand = wb.bt.ncand;
+        const int nmis = wb.nmis, ncand = wb.st.bt.ncand;
         slab_d.ensure(std::max<size_t>(1, (size_t)ng * nmis * ncand), &c->dev_bytes);
         if (nmis == 0) return;
-        const dim3 grid((unsigned)wb.ntile, (unsigned)nmis, (unsigned)ng);
+        const dim3 grid((unsigned)wb.st.ntile, (unsigned)nmis, (unsigned)ng);
         by_basis(K, [&](auto k) {
             hipLaunchKernelGGL((speccand_slot_kernel<k.value>), grid, dim3(kThreads), 0, c->stream, spec, slots, info, c->refamp_d.p, c->filtw_d.p,
                                nmis, c->method, c->syn_factor, x, ncand, slab_d.p);
@@ -167,35 +155,21 @@ struct Hook : spectral_candidates::ChunkHook {
         norm_d.ensure(std::max<size_t>(1, norm_h.size()), &c->dev_bytes);
         if (!norm_h.empty()) HIPCHECK(hipMemcpyAsync(norm_d.p, norm_h.data(), norm_h.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
         wb.after_fold(g0, ng, slab_d.p, norm_d.p);
-        hipLaunchKernelGGL(speccand_boot_status_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, c->stream, wb.b_d.p, wb.nrec, ng, status);
+        hipLaunchKernelGGL(speccand_boot_status_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, c->stream, wb.st.b.p, wb.st.nrec, ng, status);
         HIPCHECK(hipGetLastError());
     }
 };
 
 // the groups [isrc0, isrc0 + ngroup K) of the uploaded batch: spectral_candidates::run's chunk loop with the slot kernel in the place
 // of its candidate kernels and the bootstrap kernels behind.  Adds its HIP-event times to c->speccand_boot_ms
-static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::Offsets &of, const double *receiver_weight, int anarchy,
-                const Boot &bt)
+static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const double *receiver_weight, int anarchy, const Boot &bt)
 {
-    spectral_candidates_bootstrap::check_setup(c, K, of, receiver_weight, bt);     // (qualified: Boot is the Gram sibling's)
+    check_setup(c, K, receiver_weight, bt);
     check_group_range(kName, c, isrc0, ngroup, K);
     if (ngroup == 0) return;
-    const int nrec = (int)c->recv.size(), nmis = c->nmis, ndraw = bt.ndraw;
-    const int ntile = (bt.ncand + kThreads - 1) / kThreads;
-    if (nmis > 65535) throw std::runtime_error(std::string(kName) + ": " + std::to_string(nmis) + " misfit slots exceed a launch");
-    // the draws of one pass: all of them, unless the slab of ONE group would exceed the chunk bound; then whole tiles of draws
-    const size_t slab_per_draw = (size_t)ntile * (sizeof(double) + sizeof(int));
-    int ndp = ndraw;
-    if (slab_per_draw * (size_t)ndraw > c->chunk_bytes_limit)
-        ndp = (int)std::min<size_t>((size_t)ndraw, std::max<size_t>(c->chunk_bytes_limit / slab_per_draw / kTileD, 1) * kTileD);
+    if (c->nmis > 65535) throw std::runtime_error(std::string(kName) + ": " + std::to_string(c->nmis) + " misfit slots exceed a launch");
 
-    Hook h(c, bt, K);
-    h.wb.isrc0 = isrc0; h.wb.K = K; h.wb.nk = 1; h.wb.nrec = nrec; h.wb.nmis = nmis; h.wb.ntile = ntile; h.wb.ndp = ndp;
-    h.wb.anarchy = anarchy ? 1 : 0; h.wb.l2 = bt.outer_norm == 2 ? 1 : 0;
-    // per group: the slab of slot misfits and the norm row, and what the waveform hook counts: the tiles' bests of one pass, ns and the
-    // group's bests per draw, rw and b, the flag
-    h.per_group = (size_t)bt.ncand * nmis * sizeof(float) + (size_t)nmis * sizeof(float) + slab_per_draw * (size_t)ndp +
-                  (size_t)ndraw * (2 * sizeof(double) + 2 * sizeof(int)) + (size_t)nrec * 2 * sizeof(double) + sizeof(int);
+    Hook h(c, bt, isrc0, K, anarchy);
     float boot_ms = 0.f;
     h.ms = &boot_ms;
     h.wb.begin(receiver_weight);
@@ -209,13 +183,15 @@ static void run(kiwi_hip_ctx *c, int isrc0, int ngroup, int K, const timescan::O
     for (int i = 0; i < 3; i++) c->speccand_boot_ms[i] += c->speccand_ms[i] - parent_ms[i];
     c->speccand_boot_ms[3] += boot_ms;
     c->speccand_boot_ms[4] += c->speccand_ms[3] - parent_ms[3];
-    h.wb.finish(c->speccand_boot_ms + 4);
+    h.wb.st.finish(c->speccand_boot_ms + 4);
 }
 
-// kiwi_hip_spectral_candidates_bootstrap_params piece by piece: the Gram sibling's PieceCall with this header's check_setup and run
+// kiwi_hip_spectral_candidates_bootstrap_params piece by piece
 static PieceCall piece_call(int K, const double *receiver_weight, int anarchy, const Boot &bt)
 {
-    return linfit_candidates_bootstrap::piece_call(K, timescan::Offsets{ 0, 1, 1 }, receiver_weight, anarchy, bt, &check_setup, &run);
+    return candidates_bootstrap::piece_call(K, bt,
+        [=](kiwi_hip_ctx *c, const Boot &b) { check_setup(c, K, receiver_weight, b); },
+        [=](kiwi_hip_ctx *c, int ng, const Boot &b) { run(c, 0, ng, K, receiver_weight, anarchy, b); });
 }
 
 } // namespace spectral_candidates_bootstrap

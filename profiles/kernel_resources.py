@@ -3,15 +3,16 @@
 kernels (kiwi_outer.hpp), the misfit-band kernels (kiwi_bands.hpp), the time-scan kernels (kiwi_timescan.hpp), the kernels of the
 linear fit's time scan (kiwi_linfit_timescan.hpp), of its candidate evaluation, plain and as the candidate
 evaluation's time scan (both kiwi_linfit_candidates_timescan.hpp), with per-receiver shifts (kiwi_linfit_candidates_floating.hpp), of
-its joint bootstrap (kiwi_linfit_candidates_bootstrap.hpp) and
+its joint bootstrap (kiwi_linfit_candidates_bootstrap.hpp; with the shifts kiwi_linfit_candidates_floating_bootstrap.hpp) and
 under the amplitude-spectrum norms (kiwi_spectral_candidates.hpp), the time-domain norms (kiwi_waveform_candidates.hpp) and the
 floating time-domain norms (kiwi_waveform_candidates_floating.hpp) and the time-domain norms at many origin times
 (kiwi_waveform_candidates_timescan.hpp) and their joint bootstrap (kiwi_waveform_candidates_bootstrap.hpp) and the joint bootstrap
-under the amplitude-spectrum norms (kiwi_spectral_candidates_bootstrap.hpp), from the
+under the amplitude-spectrum norms (kiwi_spectral_candidates_bootstrap.hpp) -- the fold kernels that the bootstraps share
+(kiwi_candidates_bootstrap.hpp) are listed with each of them --, from the
 compiler's own
 report (hipcc -Rpass-analysis=kernel-resource-usage; `make -C kiwi_amd/csrc asm FAMILY=n ARITH=exact|fused`).
 --text adds the kernels' text sizes in bytes (accumulate families: `make co`, the symbol sizes of the device code object).
-Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating|waveform_candidates_timescan|waveform_candidates_bootstrap|spectral_candidates_bootstrap]"""
+Runs on the build machine (no GPU needed):   python profiles/kernel_resources.py [--json out.json] [--text] [--only=multi|bands|timescan|linfit_timescan|linfit_candidates_timescan|linfit_candidates_floating|linfit_candidates_bootstrap|linfit_candidates_floating_bootstrap|spectral_candidates|waveform_candidates|waveform_candidates_floating|waveform_candidates_timescan|waveform_candidates_bootstrap|spectral_candidates_bootstrap]"""
 import json
 import os
 import re
@@ -25,7 +26,7 @@ FAMILIES = {1: "direct", 2: "grouped", 3: "multi", 4: "cell"}
 
 def demangle(names):
     out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::").replace("void linfit_candidates_bootstrap::", "linfit_candidates_bootstrap::").replace("void spectral_candidates::", "spectral_candidates::").replace("void waveform_candidates::", "waveform_candidates::").replace("void waveform_candidates_floating::", "waveform_candidates_floating::").replace("void waveform_candidates_timescan::", "waveform_candidates_timescan::") for o in out]
+    return [re.sub(r"\(.*", "", o).replace("void kiwi::", "").replace("void outer::", "outer::").replace("void bands::", "bands::").replace("void timescan::", "timescan::").replace("void linfit_timescan::", "linfit_timescan::").replace("void linfit::", "linfit::").replace("void linfit_candidates_timescan::", "linfit_candidates_timescan::").replace("void linfit_candidates_floating::", "linfit_candidates_floating::").replace("void linfit_candidates_bootstrap::", "linfit_candidates_bootstrap::").replace("void linfit_candidates_floating_bootstrap::", "linfit_candidates_floating_bootstrap::").replace("void candidates_bootstrap::", "candidates_bootstrap::").replace("void spectral_candidates::", "spectral_candidates::").replace("void waveform_candidates::", "waveform_candidates::").replace("void waveform_candidates_floating::", "waveform_candidates_floating::").replace("void waveform_candidates_timescan::", "waveform_candidates_timescan::") for o in out]
 
 
 KEYS = (("sgpr", r"TotalSGPRs: (\d+)"), ("vgpr", r"\bVGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"),
@@ -47,6 +48,8 @@ def collect_outer():
                                 ("_ZN26linfit_candidates_timescan", "linfit_candidates_timescan"),
                                 ("_ZN26linfit_candidates_floating", "linfit_candidates_floating"),
                                 ("_ZN27linfit_candidates_bootstrap", "linfit_candidates_bootstrap"),
+                                ("_ZN36linfit_candidates_floating_bootstrap", "linfit_candidates_floating_bootstrap"),
+                                ("_ZN20candidates_bootstrap", "candidates_bootstrap"),
                                 ("_ZN19spectral_candidates", "spectral_candidates"), ("_ZN19waveform_candidates", "waveform_candidates"),
                                 ("_ZN28waveform_candidates_floating", "waveform_candidates_floating"),
                                 ("_ZN28waveform_candidates_timescan", "waveform_candidates_timescan"),
@@ -100,7 +103,8 @@ def collect(only=None, text=False):
                     if m:
                         cur[key] = int(m.group(1))
     if only not in FAMILIES.values():
-        rows += [r for r in collect_outer() if not only or r["family"] == only]
+        shared = "candidates_bootstrap" if only and only.endswith("_bootstrap") else None       # (what every bootstrap launches)
+        rows += [r for r in collect_outer() if not only or r["family"] in (only, shared)]
     names = demangle([r["mangled"] for r in rows])
     for r, n in zip(rows, names):
         r["kernel"] = n

@@ -381,6 +381,57 @@ def test_one_receiver_more_than_the_layout_holds_is_refused():
         p.close()
 
 
+def test_most_receivers_the_lds_layout_holds():
+    """as many receivers of one component as the candidate kernel's LDS layout holds (the Gram sibling's
+    test_receivers_against_the_lds_layout): ranges of one shift (every receiver but three), of shifts on one side only and of S + 1
+    shifts, one more than an LDS stage -- on the LAST receiver, which alone decides draw 3; two groups, 70 candidates, 2 T + 1 draws,
+    bits as in case 1"""
+    from tests.test_linfit_candidates_bootstrap_gpu import wide_scenario
+    import ctypes
+    from kiwi_amd import lib as klib
+    K = 6
+    c, t, r = (ctypes.c_int() for _ in range(3))
+    assert klib.load().kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(K, ctypes.byref(c), ctypes.byref(t), ctypes.byref(r)) == 0
+    nrec = r.value
+    sc = wide_scenario(nrec)
+    p = sc.product()
+    sc.apply_setup(p, False)
+    try:
+        C, T, Rmax = p.linear_fit_candidates_floating_bootstrap_shape(K)
+        S = p.linear_fit_candidates_floating_shape(K)[2]
+        assert nrec == Rmax == 131
+        ranges = {1: (1, 4), 4: (-2, 2), nrec - 1: (-(S // 2), S // 2)}
+        assert ranges[nrec - 1][1] - ranges[nrec - 1][0] + 1 == S + 1
+        p.switch_receiver(3, False)
+        rng = np.random.default_rng(nrec)
+        p.set_source_params("moment_tensor", scattered_groups(rng, 2, K))
+        p.set_misfit_method("floating_l2norm")
+        p.set_floating_shiftrange(0, 0.0, 0.0)
+        for ir, (lo, hi) in ranges.items():
+            p.set_floating_shiftrange(ir + 1, lo * sc.gf["dt"], hi * sc.gf["dt"])
+        w = rng.uniform(0.5, 2.0, nrec)
+        w[nrec - 2] = 0.0
+        cand = rng.uniform(-2.0, 2.0, (70, K))
+        counted = [i for i in range(nrec) if i not in (2, nrec - 2)]
+        dw = fc.draw_rows(nrec, 2 * T + 1, counted, [2, nrec - 2], seed=1)
+        dw[3] = 0.0
+        dw[3, nrec - 1] = 1.0                                 # the last receiver alone decides
+        for norm in ("l1norm", "l2norm"):
+            for anarchy in (False, True):
+                what = "%d receivers %s anarchy=%s" % (nrec, norm, anarchy)
+                want = fc.host_route(p, 0, 2, K, cand, dw, norm, w, anarchy)
+                excluded = np.isnan(want["best_value"])
+                assert np.array_equal(np.nonzero(excluded)[0], [1, 2]) and np.all(want["status"] == 0), what
+                assert np.all(want["best_shift"][~excluded, 1] >= 1) and np.all(want["best_shift"][~excluded, 1] <= 4), what
+                assert not np.any(want["best_shift"][:, [2, nrec - 2]]), what
+                got = p.linear_fit_candidates_floating_bootstrap(0, 2, K, cand, dw, outer_norm=norm, receiver_weights=w, anarchy=anarchy,
+                                                                 per_group=True)
+                assert got.best_shift.shape == (2 * T + 1, nrec) and got.group_shift.shape == (2, 2 * T + 1, nrec), what
+                fc.assert_boot(got, want, what, same_batch=True)
+    finally:
+        p.close()
+
+
 # ------------------------------------------------------------------------------------------------ 6: the helper and the example
 def test_planted_double_couple_depth_and_delays_through_the_helper():
     """data of a planted double couple at 11 km, every station late by its own whole number of samples, noise-free: every draw that
