@@ -223,6 +223,12 @@ __global__ __launch_bounds__(64) void linfit_solve_kernel(const double *__restri
     pivot_min[g] = pmin;
 }
 
+} // namespace linfit
+
+// A host build of the kernels above (tests/host_kernels) stops here: what follows launches them from a kiwi_hip_ctx
+#ifndef KIWI_LINFIT_KERNELS_ONLY
+namespace linfit {
+
 template <int K>
 static void launch_gram(kiwi_hip_ctx *c, int ng, const FftPair *pairs, double *nbr)
 {
@@ -523,3 +529,4 @@ static PieceCall piece_call(int K, const double *receiver_weight, int anarchy, c
 }
 
 } // namespace linfit
+#endif // KIWI_LINFIT_KERNELS_ONLY

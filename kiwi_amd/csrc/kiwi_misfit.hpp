@@ -5,6 +5,12 @@
 #pragma once
 #include "kiwi_common.hpp"
 
+// the dynamic LDS of a kernel (sized at the launch).  A host build of this text (tests/host_kernels) brings its own form: there
+// `__shared__` is `static`, which `extern` excludes
+#ifndef KIWI_DYNAMIC_SHARED
+#define KIWI_DYNAMIC_SHARED(T, name) extern __shared__ __attribute__((aligned(16))) T name[]
+#endif
+
 namespace kiwi {
 
 // ------------------------------------------------------------------------------------------------
@@ -118,7 +124,11 @@ __device__ __forceinline__ float folded_scaled_sample(const float *__restrict__ 
             float wl = 1.f - wr;
             wr = wr * fw[k]; wl = wl * fw[k];
             v = v + wl * sy[i - fs[k]];
-            v = v + wr * sy[i - fs[k] - 1];
+            // a right-hand weight of exactly zero adds + 0 to v (never - 0: it starts at + 0) whatever finite value lies there, so
+            // that sample is not read.  It need not exist: a rise time that rounds to ONE tap (shift 0, fraction 0) has no fold
+            // halo (prepare(): half width 0), and sy[i - 1] at i = 0 then lies in front of the slot -- for the first slot of the
+            // first source in front of the allocation
+            v = v + wr * (wr != 0.f ? sy[i - fs[k] - 1] : 0.f);
         }
     } else {
         v = sy[i];
@@ -581,7 +591,7 @@ __global__ __launch_bounds__(256) void spec_fft_norm_kernel(
     const float *__restrict__ refamp, const float *__restrict__ filtw, SpecParams sp, float *__restrict__ misfit_out,
     float *__restrict__ amp_out, SynRows sr)
 {
-    extern __shared__ __attribute__((aligned(16))) float2 zf[];
+    KIWI_DYNAMIC_SHARED(float2, zf);
     __shared__ double red[256];
     const int tid = threadIdx.x;
     // (modes 0, 2: source index fastest -- the workgroups in flight share the reference and filter rows of a few slots)
@@ -676,7 +686,7 @@ __global__ __launch_bounds__(256) void spec_fft_filter_norm_kernel(
     const float *__restrict__ filtw, const float *__restrict__ ref_filt, const float *__restrict__ zmask, SpecParams sp,
     float *__restrict__ misfit_out, float *__restrict__ filt_out, SynRows sr)
 {
-    extern __shared__ __attribute__((aligned(16))) float2 zf[];
+    KIWI_DYNAMIC_SHARED(float2, zf);
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int m = MODE == 0 ? (int)blockIdx.y : 0, s = MODE == 0 ? (int)blockIdx.x : 0;

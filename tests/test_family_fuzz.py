@@ -104,7 +104,9 @@ def test_the_set_up_at_which_linear_fit_faulted_on_the_device_is_on_record():
     the window is 261 samples, two accumulate tiles of 256 of which the second holds five samples and lies wholly behind the end
     of every basis synthetic's data (held end values of a `static` database only); the one receiver has no vertical component, so
     with bilinear interpolation and centroids that are points of their own it is not a cell pair and goes through
-    accumulate_grouped_kernel's cell-mode route.  Whoever finds the cause turns this into the regression test."""
+    accumulate_grouped_kernel's cell-mode route.  tests/test_host_kernels.py runs every plain-C++ kernel of the path at this set-up on
+    the host under AddressSanitizer and audits that kernel's addresses: clean, so the cause is not there.  Whoever finds it turns this
+    into the regression test."""
     import ctypes as C
     from oracle import ko
     case = ff.recorded_fault_case()
