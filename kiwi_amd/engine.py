@@ -46,12 +46,21 @@ GEOREC = np.dtype([("row", np.int32, 4), ("w", np.float32, 4), ("ishift", np.int
                    ("pad", np.int32)])
 
 
-def _fp(a):
-    return a.ctypes.data_as(c_float_p)
+def _pointer(ctype):
+    """array -> pointer of that type for a call; None -> None (NULL: an input left out, an output not asked for)"""
+    return lambda a: None if a is None else a.ctypes.data_as(ctype)
 
 
-def _ip(a):
-    return a.ctypes.data_as(c_int_p)
+_fp, _ip, _dp, _sp = _pointer(c_float_p), _pointer(c_int_p), _pointer(c_double_p), _pointer(C.POINTER(C.c_short))
+
+_K_RANGE = "%s: K = %d basis sources per group; 1 to %d are supported"
+
+
+def _outer_code(outer_norm):
+    code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
+    if code is None:
+        raise KiwiHipError("unknown norm method: %s" % outer_norm)
+    return code
 
 
 def discretize(sourcetype, params, effective_dt):
@@ -308,8 +317,7 @@ class Engine:
         lon = np.ascontiguousarray(lon_deg, np.float64)
         dep = np.ascontiguousarray(np.zeros(n) if depth is None else depth, np.float32)
         arr = (C.c_char_p * n)(*[c.encode() for c in components])
-        self._ck(self.L.kiwi_hip_set_receivers(self.h, n, lat.ctypes.data_as(c_double_p),
-                                               lon.ctypes.data_as(c_double_p), _fp(dep), arr), "set_receivers")
+        self._ck(self.L.kiwi_hip_set_receivers(self.h, n, _dp(lat), _dp(lon), _fp(dep), arr), "set_receivers")
         self.components = list(components)
         self.enabled = [len(c) > 0 for c in components]
 
@@ -646,9 +654,7 @@ class Engine:
 
     def band_misfits_ms(self):
         """HIP-event durations [ms] of the last band call: (evaluation, band kernels, downloads)."""
-        ms = np.zeros(3, np.float32)
-        self._ck(self.L.kiwi_hip_get_band_misfits_ms(self.h, _fp(ms)), "band_misfits")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_band_misfits_ms, 3, "band_misfits")
 
     # ------------------------------------------------------------------ time scan (kiwi_timescan.hpp)
     def time_scan(self, isrc0=0, nsrc=None, k0=0, kstep=1, nk=1):
@@ -688,9 +694,7 @@ class Engine:
 
     def time_scan_ms(self):
         """HIP-event durations [ms] of the last scan call: (evaluation, scan kernels, downloads)."""
-        ms = np.zeros(3, np.float32)
-        self._ck(self.L.kiwi_hip_get_time_scan_ms(self.h, _fp(ms)), "time_scan")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_time_scan_ms, 3, "time_scan")
 
     def make_misfits_for_sources(self, sourcetype=None, params=None, piece=0):
         """seismosizer.py:682-722: returns (misfits_by_src[N_s,N_r,N_k], norms_by_src[...], failings) -- float64 arrays,
@@ -732,9 +736,7 @@ class Engine:
         every receiver in every draw (None: one draw of ones).  Returns (best_value[B] float64, best_index[B] int32,
         global_of_draw[N_s] float64 or None): the lowest global misfit of each draw and its source -- among equal values the
         lowest index; NaN, 0 where every source is excluded -- and the global misfits of all sources under draw `which_draw`."""
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
+        code = _outer_code(outer_norm)
         m = np.ascontiguousarray(misfit, np.float32)
         n = np.ascontiguousarray(norm, np.float32)
         sr = np.ascontiguousarray(slot_receiver, np.int32)
@@ -750,17 +752,14 @@ class Engine:
         nd = len(dw)
         bv, bi = np.zeros(nd, np.float64), np.zeros(nd, np.int32)
         g = None if which_draw is None else np.zeros(len(m), np.float64)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        self._ck(self.L.kiwi_hip_outer_misfits(self.h, len(m), m.shape[1], nrec, _ip(sr), _fp(m), _fp(n), code, dp(w),
-                                               1 if anarchy else 0, nd, dp(dw), dp(bv), _ip(bi),
-                                               0 if which_draw is None else int(which_draw), dp(g)), "outer_misfits")
+        self._ck(self.L.kiwi_hip_outer_misfits(self.h, len(m), m.shape[1], nrec, _ip(sr), _fp(m), _fp(n), code, _dp(w),
+                                               1 if anarchy else 0, nd, _dp(dw), _dp(bv), _ip(bi),
+                                               0 if which_draw is None else int(which_draw), _dp(g)), "outer_misfits")
         return bv, bi, g
 
     def outer_ms(self):
         """HIP-event durations [ms] of the last outer_misfits: (uploads, kernels, downloads)."""
-        ms = np.zeros(3, np.float32)
-        self._ck(self.L.kiwi_hip_get_outer_ms(self.h, _fp(ms)), "get_outer_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_outer_ms, 3, "get_outer_ms")
 
     def outer_misfits(self, misfits_by_src, norms_by_src, outer_norm="l2norm", receiver_weights=None, anarchy=False,
                       draw_weights=None, which_draw=None, ncomponents=None):
@@ -785,60 +784,72 @@ class Engine:
         return self.outer_misfits_slots(mf, nf, slot_receiver, nrec, outer_norm, receiver_weights, anarchy, draw_weights,
                                         which_draw)
 
-    # ------------------------------------------------------------------ linear fit (kiwi_hip_linear_fit)
-    def linear_fit_max_basis(self):
-        """The most basis sources per group `linear_fit` takes."""
-        return int(self.L.kiwi_hip_linear_fit_max_basis())
+    # ------------------------------------------------------------------ what the group families share
+    def _read_ms(self, fn, n, what):
+        """the n HIP-event durations [ms] a `kiwi_hip_get_*_ms` call answers, as floats"""
+        ms = np.zeros(n, np.float32)
+        self._ck(fn(self.h, _fp(ms)), what)
+        return tuple(float(x) for x in ms)
 
-    def _linear_fit_arrays(self, ngroup, K, receiver_weights, normal, by_receiver):
-        K, ngroup = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        nrec, nn = len(self.components), K * (K + 1) // 2 + K + 1
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
-        out = LinearFit(np.zeros((ngroup, K)), np.zeros(ngroup), np.zeros(ngroup, np.int32), np.zeros(ngroup),
-                        np.zeros((ngroup, nn)) if normal else None, np.zeros((ngroup, nrec, nn)) if by_receiver else None)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        return w, out, dp
+    def _basis_count(self, K, name, kmax=None):
+        K, kmax = int(K), self.linear_fit_max_basis() if kmax is None else kmax
+        if not 1 <= K <= kmax:
+            raise KiwiHipError(_K_RANGE % (name, K, kmax))
+        return K
 
-    def linear_fit(self, isrc0, ngroup, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False):
-        """Least-squares coefficients of K basis sources per group under l2norm (kiwi_hip_linear_fit): sources
-        [isrc0, isrc0 + ngroup K) of the uploaded batch are `ngroup` groups of K consecutive basis sources.  Returns a
-        `LinearFit`: coef[ngroup, K], misfit[ngroup] (the global misfit of the fitted combination), status[ngroup] (0 solved,
-        1 no solution, 2 a basis source failed to discretise), pivot_min[ngroup] (smallest Cholesky pivot of the unit-diagonal
-        normal matrix: judge near-dependence by it), and on request normal[ngroup, NN] (G upper triangle by rows, b, R --
-        weighted sums) and by_receiver[ngroup, nrec, NN] (unweighted, zeros for disabled receivers)."""
-        w, out, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, normal, by_receiver)
-        self._ck(self.L.kiwi_hip_linear_fit(self.h, int(isrc0), int(ngroup), int(K), dp(w), 1 if anarchy else 0, dp(out.coef),
-                                            dp(out.misfit), _ip(out.status), dp(out.pivot_min), dp(out.normal), dp(out.by_receiver)),
-                 "linear_fit")
-        return out
+    def _read_shape(self, fn, lead, count, name):
+        """the `count` ints a `_shape` call answers for the leading arguments `lead`, the last of which is K; `name` signs the refusal"""
+        v = [np.zeros(1, np.int32) for _ in range(count)]
+        if fn(*lead, *[_ip(a) for a in v]):
+            raise KiwiHipError(_K_RANGE % (name, lead[-1], self.linear_fit_max_basis()))
+        return tuple(int(a[0]) for a in v)
 
-    def linear_fit_params(self, sourcetype, params, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False, piece=0):
-        """`linear_fit` for a parameter list of any length (kiwi_hip_linear_fit_params): params[ngroup * K, nparams], every K
-        consecutive rows a group; discretised and uploaded in pieces of `piece` sources (rounded down to a multiple of K;
-        0: the default of misfits_for_params), the host discretiser of one piece running while the device works on another.
-        Piece size does not change a bit.  Afterwards the engine holds the head of the list."""
+    def _receiver_weights(self, receiver_weights):
+        if receiver_weights is None:
+            return None
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (len(self.components),)))
+
+    def _nslots(self):
+        return sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+
+    def _candidate_inputs(self, name, outer_norm, K, candidates, receiver_weights, draw_weights=None, krange=None):
+        """What a candidate family takes in, checked and as the library wants it: the code of the outer norm, the candidates as
+        float64 [ncand, K], the receiver weights as float64 [nrec] or None and, where there are draws, their weights as float64
+        [ndraw, nrec].  `name` signs the refusals, `krange` that of K where it is signed otherwise."""
+        code = _outer_code(outer_norm)
+        K = self._basis_count(K, krange or name)
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
+        if x.ndim != 2 or x.shape[1] != K:
+            raise KiwiHipError("%s: candidates must be [ncand, K = %d]" % (name, K))
+        w = self._receiver_weights(receiver_weights)
+        if draw_weights is None:
+            return code, x, w
+        dw = np.ascontiguousarray(np.asarray(draw_weights, np.float64))
+        if dw.ndim != 2 or dw.shape[1] != len(self.components):
+            raise KiwiHipError("%s: draw_weights must be [ndraw, %d]" % (name, len(self.components)))
+        return code, x, w, dw
+
+    def _list_head(self, sourcetype, params, K, piece, name=None):
+        """The arguments (sourcetype, ngroup, K, params, piece) a `_params` call takes where the uploaded call takes (isrc0, ngroup,
+        K), checked, and the number of rows.  `name` signs the two refusals; None: as set_source_params and linear_fit_params."""
+        count, whole = (name, name) if name else ("set_source_params", "linear_fit_params")
         p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
         st = SOURCE_TYPES.get(sourcetype, sourcetype)
         K = int(K)
         if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
+            raise KiwiHipError("%s: wrong number of source parameters" % count)
         if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        w, out, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, normal, by_receiver)
+            raise KiwiHipError("%s: %d parameter rows are not whole groups of K = %d" % (whole, p.shape[0], K))
+        return (st, p.shape[0] // K, K, _fp(p), int(piece)), len(p)
+
+    def _list_call(self, fn, head, rows, args, what):
+        """a `_params` call: afterwards the engine holds the head of the list -- after a call that failed, nothing"""
         try:
-            self._ck(self.L.kiwi_hip_linear_fit_params(self.h, st, ngroup, K, _fp(p), int(piece), dp(w), 1 if anarchy else 0,
-                                                       dp(out.coef), dp(out.misfit), _ip(out.status), dp(out.pivot_min),
-                                                       dp(out.normal), dp(out.by_receiver)), "linear_fit")
+            self._ck(fn(self.h, *head, *args), what)
         except KiwiHipError:
             self.nsrc = 0
             raise
-        self.nsrc = self._uploaded_sources(len(p))
-        return out
+        self.nsrc = self._uploaded_sources(rows)
 
     def _uploaded_sources(self, nlist):
         """how many sources the context holds after a list call of `nlist` rows: its first piece (list order) that uploaded
@@ -854,27 +865,60 @@ class Engine:
                 hi = mid - 1
         return lo
 
+    # ------------------------------------------------------------------ linear fit (kiwi_hip_linear_fit)
+    def linear_fit_max_basis(self):
+        """The most basis sources per group `linear_fit` takes."""
+        return int(self.L.kiwi_hip_linear_fit_max_basis())
+
+    def _linear_fit_arrays(self, ngroup, K, receiver_weights, anarchy, normal, by_receiver):
+        """what every `_..._arrays` returns: (the arguments of the call after (isrc0, ngroup, K) or (sourcetype, ngroup, K, params,
+        piece), the tuple they fill)"""
+        K, ngroup = self._basis_count(K, "linear_fit"), int(ngroup)
+        nrec, nn = len(self.components), K * (K + 1) // 2 + K + 1
+        w = self._receiver_weights(receiver_weights)
+        out = LinearFit(np.zeros((ngroup, K)), np.zeros(ngroup), np.zeros(ngroup, np.int32), np.zeros(ngroup),
+                        np.zeros((ngroup, nn)) if normal else None, np.zeros((ngroup, nrec, nn)) if by_receiver else None)
+        return (_dp(w), 1 if anarchy else 0, _dp(out.coef), _dp(out.misfit), _ip(out.status), _dp(out.pivot_min), _dp(out.normal),
+                _dp(out.by_receiver)), out
+
+    def linear_fit(self, isrc0, ngroup, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False):
+        """Least-squares coefficients of K basis sources per group under l2norm (kiwi_hip_linear_fit): sources
+        [isrc0, isrc0 + ngroup K) of the uploaded batch are `ngroup` groups of K consecutive basis sources.  Returns a
+        `LinearFit`: coef[ngroup, K], misfit[ngroup] (the global misfit of the fitted combination), status[ngroup] (0 solved,
+        1 no solution, 2 a basis source failed to discretise), pivot_min[ngroup] (smallest Cholesky pivot of the unit-diagonal
+        normal matrix: judge near-dependence by it), and on request normal[ngroup, NN] (G upper triangle by rows, b, R --
+        weighted sums) and by_receiver[ngroup, nrec, NN] (unweighted, zeros for disabled receivers)."""
+        args, out = self._linear_fit_arrays(ngroup, K, receiver_weights, anarchy, normal, by_receiver)
+        self._ck(self.L.kiwi_hip_linear_fit(self.h, int(isrc0), int(ngroup), int(K), *args), "linear_fit")
+        return out
+
+    def linear_fit_params(self, sourcetype, params, K, receiver_weights=None, anarchy=False, normal=False, by_receiver=False, piece=0):
+        """`linear_fit` for a parameter list of any length (kiwi_hip_linear_fit_params): params[ngroup * K, nparams], every K
+        consecutive rows a group; discretised and uploaded in pieces of `piece` sources (rounded down to a multiple of K;
+        0: the default of misfits_for_params), the host discretiser of one piece running while the device works on another.
+        Piece size does not change a bit.  Afterwards the engine holds the head of the list."""
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._linear_fit_arrays(head[1], K, receiver_weights, anarchy, normal, by_receiver)
+        self._list_call(self.L.kiwi_hip_linear_fit_params, head, rows, args, "linear_fit")
+        return out
+
     def linear_fit_ms(self):
         """HIP-event durations [ms] of the last linear fit: (evaluation, fit kernels, downloads)."""
-        ms = np.zeros(3, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_ms(self.h, _fp(ms)), "get_linear_fit_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_ms, 3, "get_linear_fit_ms")
 
     # ------------------------------------------------------------------ linear fit at many origin times (kiwi_hip_linear_fit_time_scan)
     def linear_fit_time_scan_shape(self, K):
         """(offsets per workgroup, window samples per LDS tile) of the Gram-scan kernel for K basis sources."""
-        j, t = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_time_scan_shape(int(K), _ip(j), _ip(t)):
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(j[0]), int(t[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_time_scan_shape, (int(K),), 2, "linear_fit")
 
-    def _scan_fit_arrays(self, ngroup, K, nk, receiver_weights, normal):
-        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        ngroup, K, nk_ = int(ngroup), int(K), max(int(nk), 0)
+    def _scan_fit_arrays(self, ngroup, K, k0, kstep, nk, receiver_weights, anarchy, normal):
+        K, ngroup, nk_ = self._basis_count(K, "linear_fit"), int(ngroup), max(int(nk), 0)
         nn = K * (K + 1) // 2 + K + 1
+        w = self._receiver_weights(receiver_weights)
         out = ScanFit(np.zeros((ngroup, nk_, K)), np.zeros((ngroup, nk_)), np.zeros((ngroup, nk_), np.int32), np.zeros((ngroup, nk_)),
                       np.zeros(ngroup, np.int32), np.zeros((ngroup, nk_, nn)) if normal else None)
-        return w, out, dp
+        return (int(k0), int(kstep), int(nk), _dp(w), 1 if anarchy else 0, _dp(out.coef), _dp(out.misfit), _ip(out.status),
+                _dp(out.pivot_min), _ip(out.best), _dp(out.normal)), out
 
     def linear_fit_time_scan(self, isrc0, ngroup, K, k0=0, kstep=1, nk=1, receiver_weights=None, anarchy=False, normal=False):
         """`linear_fit` at the origin-time offsets (k0 + j kstep) dt, j < nk, from ONE synthesis of the basis sources
@@ -882,68 +926,38 @@ class Engine:
         places.  Returns a `ScanFit`: coef[ngroup, nk, K], misfit[ngroup, nk], status[ngroup, nk], pivot_min[ngroup, nk],
         best[ngroup] (the offset index of the smallest misfit among the solved offsets, -1 if there is none) and on request
         normal[ngroup, nk, NN].  Offset 0 is `linear_fit` bit for bit."""
-        w, out, dp = self._scan_fit_arrays(ngroup, K, nk, receiver_weights, normal)
-        self._ck(self.L.kiwi_hip_linear_fit_time_scan(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), dp(w),
-                                                      1 if anarchy else 0, dp(out.coef), dp(out.misfit), _ip(out.status),
-                                                      dp(out.pivot_min), _ip(out.best), dp(out.normal)), "linear_fit_time_scan")
+        args, out = self._scan_fit_arrays(ngroup, K, k0, kstep, nk, receiver_weights, anarchy, normal)
+        self._ck(self.L.kiwi_hip_linear_fit_time_scan(self.h, int(isrc0), int(ngroup), int(K), *args), "linear_fit_time_scan")
         return out
 
     def linear_fit_time_scan_params(self, sourcetype, params, K, k0=0, kstep=1, nk=1, receiver_weights=None, anarchy=False, normal=False,
                                     piece=0):
         """`linear_fit_time_scan` for a parameter list of any length, cut into pieces and over the devices at group boundaries as
         `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        w, out, dp = self._scan_fit_arrays(ngroup, K, nk, receiver_weights, normal)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep), int(nk),
-                                                                 dp(w), 1 if anarchy else 0, dp(out.coef), dp(out.misfit),
-                                                                 _ip(out.status), dp(out.pivot_min), _ip(out.best), dp(out.normal)),
-                     "linear_fit_time_scan")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._scan_fit_arrays(head[1], K, k0, kstep, nk, receiver_weights, anarchy, normal)
+        self._list_call(self.L.kiwi_hip_linear_fit_time_scan_params, head, rows, args, "linear_fit_time_scan")
         return out
 
     def linear_fit_time_scan_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_time_scan`: (evaluation, Gram-scan kernel, solve kernels, downloads)."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_time_scan_ms(self.h, _fp(ms)), "get_linear_fit_time_scan_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_time_scan_ms, 4, "get_linear_fit_time_scan_ms")
 
     # ------------------------------------------------------------------ candidate coefficient vectors (kiwi_hip_linear_fit_candidates)
     def linear_fit_candidates_shape(self, K):
         """(candidates per workgroup, receivers per LDS stage) of the candidate kernel for K basis sources."""
-        c, s = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_candidates_shape(int(K), _ip(c), _ip(s)):
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(s[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_candidates_shape, (int(K),), 2, "linear_fit")
 
-    def _candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        w, fit, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != int(K):
-            raise KiwiHipError("linear_fit_candidates: candidates must be [ncand, K = %d]" % int(K))
-        ng, nc, nrec = int(ngroup), len(x), len(self.components)
+    def _candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit, receiver_misfit):
+        code, x, w = self._candidate_inputs("linear_fit_candidates", outer_norm, K, candidates, receiver_weights, krange="linear_fit")
+        ng, K, nc, nrec = int(ngroup), int(K), len(x), len(self.components)
         out = CandidateScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nc)) if misfit else None,
                             np.zeros((ng, nc)) if free_scale else None,
                             np.zeros((ng, nc, nrec), np.float32) if receiver_misfit else None,
-                            np.zeros((ng, nrec), np.float32) if receiver_misfit else None, fit.coef, fit.misfit)
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.misfit), dp(out.scale),      # noqa: E731
-                        None if out.receiver_misfit is None else _fp(out.receiver_misfit),
-                        None if out.receiver_norm is None else _fp(out.receiver_norm), dp(out.fit_coef), dp(out.fit_misfit))
-        return tail, out, outs
+                            np.zeros((ng, nrec), np.float32) if receiver_misfit else None, np.zeros((ng, K)), np.zeros(ng))
+        return (nc, _dp(x), code, _dp(w), 1 if anarchy else 0, 1 if free_scale else 0, _ip(out.best_index), _dp(out.best_misfit),
+                _ip(out.status), _dp(out.misfit), _dp(out.scale), _fp(out.receiver_misfit), _fp(out.receiver_norm), _dp(out.fit_coef),
+                _dp(out.fit_misfit)), out
 
     def linear_fit_candidates(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                               free_scale=False, misfit=True, receiver_misfit=False):
@@ -955,76 +969,41 @@ class Engine:
         ncand] (misfit=True), scale[ngroup, ncand] (free_scale), receiver_misfit[ngroup, ncand, nrec] and receiver_norm[ngroup,
         nrec] float32 (receiver_misfit=True: what `outer_misfits` takes with one slot per receiver), fit_coef[ngroup, K] and
         fit_misfit[ngroup]: `linear_fit` of the same groups."""
-        tail, out, outs = self._candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit)
-        self._ck(self.L.kiwi_hip_linear_fit_candidates(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
-                                                       1 if free_scale else 0, *outs()), "linear_fit_candidates")
+        args, out = self._candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit, receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates(self.h, int(isrc0), int(ngroup), int(K), *args), "linear_fit_candidates")
         return out
 
     def linear_fit_candidates_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                                      free_scale=False, misfit=True, receiver_misfit=False, piece=0):
         """`linear_fit_candidates` for a parameter list of any length (kiwi_hip_linear_fit_candidates_params), cut into pieces
         and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs = self._candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, receiver_misfit)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_candidates_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail, 1 if anarchy else 0,
-                                                                  1 if free_scale else 0, *outs()), "linear_fit_candidates")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._candidate_arrays(head[1], K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit, receiver_misfit)
+        self._list_call(self.L.kiwi_hip_linear_fit_candidates_params, head, rows, args, "linear_fit_candidates")
         return out
 
     def linear_fit_candidates_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_candidates`: (evaluation, Gram and solve kernels, candidate kernels,
         downloads)."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_ms(self.h, _fp(ms)), "get_linear_fit_candidates_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_candidates_ms, 4, "get_linear_fit_candidates_ms")
 
     # ------------------------------------------------------------------ candidates with per-receiver shifts (kiwi_hip_linear_fit_candidates_floating)
     def linear_fit_candidates_floating_shape(self, K):
         """(candidates per workgroup, shifts per pass of the cross-correlation kernel, shifts per LDS stage of the candidate
         kernel) for K basis sources."""
-        c, j, s = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_candidates_floating_shape(int(K), _ip(c), _ip(j), _ip(s)):
-            raise KiwiHipError("linear_fit_candidates_floating: K = %d basis sources per group; 1 to %d are supported"
-                               % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(j[0]), int(s[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_candidates_floating_shape, (int(K),), 3, "linear_fit_candidates_floating")
 
-    def _candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift, receiver_misfit):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        K, ng = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("linear_fit_candidates_floating: K = %d basis sources per group; 1 to %d are supported"
-                               % (K, self.linear_fit_max_basis()))
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != K:
-            raise KiwiHipError("linear_fit_candidates_floating: candidates must be [ncand, K = %d]" % K)
-        nc, nrec = len(x), len(self.components)
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+    def _candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit, cand_shift,
+                                   receiver_misfit):
+        code, x, w = self._candidate_inputs("linear_fit_candidates_floating", outer_norm, K, candidates, receiver_weights)
+        ng, nc, nrec = int(ngroup), len(x), len(self.components)
         out = CandidateFloatingScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nrec), np.int32),
                                     np.zeros((ng, nc)) if misfit else None, np.zeros((ng, nc, nrec), np.int16) if cand_shift else None,
                                     np.zeros((ng, nc, nrec), np.float32) if receiver_misfit else None,
                                     np.zeros((ng, nrec), np.float32) if receiver_misfit else None)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), _ip(out.best_shift), dp(out.misfit),      # noqa: E731
-                        None if out.cand_shift is None else out.cand_shift.ctypes.data_as(C.POINTER(C.c_short)),
-                        None if out.receiver_misfit is None else _fp(out.receiver_misfit),
-                        None if out.receiver_norm is None else _fp(out.receiver_norm))
-        return tail, out, outs, (x, w)
+        return (nc, _dp(x), code, _dp(w), 1 if anarchy else 0, 1 if free_scale else 0, _ip(out.best_index), _dp(out.best_misfit),
+                _ip(out.status), _ip(out.best_shift), _dp(out.misfit), _sp(out.cand_shift), _fp(out.receiver_misfit),
+                _fp(out.receiver_norm)), out
 
     def linear_fit_candidates_floating(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                                        free_scale=False, misfit=True, cand_shift=False, receiver_misfit=False):
@@ -1036,10 +1015,10 @@ class Engine:
         misfit[ngroup, ncand] (misfit=True), cand_shift[ngroup, ncand, nrec] int16 (cand_shift=True; needs misfit),
         receiver_misfit[ngroup, ncand, nrec] and receiver_norm[ngroup, nrec] float32 (receiver_misfit=True: what
         `outer_misfits` takes with one slot per receiver)."""
-        tail, out, outs, keep = self._candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift,
-                                                                receiver_misfit)
-        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
-                                                                1 if free_scale else 0, *outs()), "linear_fit_candidates_floating")
+        args, out = self._candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit,
+                                                    cand_shift, receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *args),
+                 "linear_fit_candidates_floating")
         return out
 
     def linear_fit_candidates_floating_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None,
@@ -1047,66 +1026,35 @@ class Engine:
                                               piece=0):
         """`linear_fit_candidates_floating` for a parameter list of any length (kiwi_hip_linear_fit_candidates_floating_params),
         cut into pieces and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs, keep = self._candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift,
-                                                                receiver_misfit)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
-                                                                           1 if anarchy else 0, 1 if free_scale else 0, *outs()),
-                     "linear_fit_candidates_floating")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._candidate_floating_arrays(head[1], K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit,
+                                                    cand_shift, receiver_misfit)
+        self._list_call(self.L.kiwi_hip_linear_fit_candidates_floating_params, head, rows, args, "linear_fit_candidates_floating")
         return out
 
     def linear_fit_candidates_floating_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_candidates_floating`: (evaluation, Gram and cross-correlation kernels,
         candidate kernels, downloads)."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_ms(self.h, _fp(ms)), "get_linear_fit_candidates_floating_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_candidates_floating_ms, 4, "get_linear_fit_candidates_floating_ms")
 
     # ------------------------------------------------------------------ joint bootstrap of a candidate search with shifts (kiwi_hip_linear_fit_candidates_floating_bootstrap)
     def linear_fit_candidates_floating_bootstrap_shape(self, K):
         """(candidates per workgroup, draws per tile, the most receivers) of the bootstrap kernel under floating_l2norm for K basis
         sources; no device needed."""
-        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
-            raise KiwiHipError("linear_fit_candidates_floating_bootstrap: K = %d basis sources per group; 1 to %d are supported"
-                               % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(t[0]), int(r[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_shape, (int(K),), 3,
+                                "linear_fit_candidates_floating_bootstrap")
 
-    def _candidate_floating_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group):
-        name = "linear_fit_candidates_floating_bootstrap"
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != int(K):
-            raise KiwiHipError("%s: candidates must be [ncand, K = %d]" % (name, int(K)))
-        nrec = len(self.components)
-        dw = np.ascontiguousarray(np.asarray(draw_weights, np.float64))
-        if dw.ndim != 2 or dw.shape[1] != nrec:
-            raise KiwiHipError("%s: draw_weights must be [ndraw, %d]" % (name, nrec))
-        ng, nd = int(ngroup), len(dw)
+    def _candidate_floating_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group):
+        code, x, w, dw = self._candidate_inputs("linear_fit_candidates_floating_bootstrap", outer_norm, K, candidates, receiver_weights,
+                                                draw_weights, krange="linear_fit")
+        ng, nd, nrec = int(ngroup), len(dw), len(self.components)
         grp = (ng, nd) if per_group else None
         out = CandidateFloatingBootstrap(np.zeros(nd), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros((nd, nrec), np.int32),
                                          np.zeros(ng, np.int32), np.zeros(grp) if grp else None, np.zeros(grp, np.int32) if grp else None,
                                          np.zeros(grp + (nrec,), np.int32) if grp else None)
-        ipn = lambda a: None if a is None else _ip(a)                                  # noqa: E731
-        head = (len(x), dp(x), code, dp(w))
-        tail = lambda: (nd, dp(dw), dp(out.best_value), _ip(out.best_group), _ip(out.best_cand), _ip(out.best_shift), _ip(out.status),      # noqa: E731
-                        dp(out.group_value), ipn(out.group_cand), ipn(out.group_shift))
-        return head, out, tail
+        return (len(x), _dp(x), code, _dp(w), 1 if anarchy else 0, nd, _dp(dw), _dp(out.best_value), _ip(out.best_group),
+                _ip(out.best_cand), _ip(out.best_shift), _ip(out.status), _dp(out.group_value), _ip(out.group_cand),
+                _ip(out.group_shift)), out
 
     def linear_fit_candidates_floating_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, outer_norm="l1norm",
                                                  receiver_weights=None, anarchy=False, per_group=False):
@@ -1117,10 +1065,9 @@ class Engine:
         (NaN and -1 where every source of a draw is excluded), best_shift[ndraw, nrec] (the winner's shifts in SAMPLES, 0 for
         receivers that do not count), status[ngroup]; per_group=True adds group_value, group_cand[ngroup, ndraw] and
         group_shift[ngroup, ndraw, nrec], the same per group.  A row of ones as draw 0 gives the plain winner."""
-        head, out, tail = self._candidate_floating_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights,
-                                                                    per_group)
-        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *head,
-                                                                          1 if anarchy else 0, *tail()),
+        args, out = self._candidate_floating_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy,
+                                                              per_group)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *args),
                  "linear_fit_candidates_floating_bootstrap")
         return out
 
@@ -1129,60 +1076,30 @@ class Engine:
         """`linear_fit_candidates_floating_bootstrap` for a parameter list of any length, cut into pieces and over the devices at
         group boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine
         holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        head, out, tail = self._candidate_floating_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights,
-                                                                    per_group)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), *head,
-                                                                                     1 if anarchy else 0, *tail()),
-                     "linear_fit_candidates_floating_bootstrap")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._candidate_floating_bootstrap_arrays(head[1], K, candidates, draw_weights, outer_norm, receiver_weights, anarchy,
+                                                              per_group)
+        self._list_call(self.L.kiwi_hip_linear_fit_candidates_floating_bootstrap_params, head, rows, args,
+                        "linear_fit_candidates_floating_bootstrap")
         return out
 
     def linear_fit_candidates_floating_bootstrap_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_candidates_floating_bootstrap`: (evaluation, Gram and cross-correlation
         kernels, bootstrap kernels, downloads)."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms(self.h, _fp(ms)),
-                 "get_linear_fit_candidates_floating_bootstrap_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms, 4,
+                             "get_linear_fit_candidates_floating_bootstrap_ms")
 
     # ------------------------------------------------------------------ candidates under the amplitude-spectrum norms (kiwi_hip_spectral_candidates)
     def spectral_candidates_shape(self, K, context=True):
         """(candidates per workgroup, bins of spectra per LDS stage, spectra_bins) of `spectral_candidates` for K basis sources;
         spectra_bins is the row length of this engine's `spectra` arrays for the sources it holds -- the longest transform any of
         their slots needs, halved, plus one -- (0 with context=False, which needs no device)."""
-        c, b, n = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_spectral_candidates_shape(self.h if context else None, int(K), _ip(c), _ip(b), _ip(n)):
-            raise KiwiHipError("spectral_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(b[0]), int(n[0])
+        return self._read_shape(self.L.kiwi_hip_spectral_candidates_shape, (self.h if context else None, int(K)), 3, "spectral_candidates")
 
-    def _spectral_candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit, slot_misfit, spectra,
-                                   spectra_bins=None):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        K, ng = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("spectral_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != K:
-            raise KiwiHipError("spectral_candidates: candidates must be [ncand, K = %d]" % K)
-        nc, nrec = len(x), len(self.components)
-        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+    def _spectral_candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit, slot_misfit,
+                                   spectra, spectra_bins=None):
+        code, x, w = self._candidate_inputs("spectral_candidates", outer_norm, K, candidates, receiver_weights)
+        ng, K, nc, nmis = int(ngroup), int(K), len(x), self._nslots()
         nb = (self.spectral_candidates_shape(K)[2] if spectra_bins is None else int(spectra_bins)) if spectra else 0
         out = SpectralCandidateScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nc)) if misfit else None,
                                     np.zeros((ng, nc)) if free_scale and misfit else None,
@@ -1191,13 +1108,9 @@ class Engine:
                                     np.zeros((ng, nmis, nb, K, 2), np.float32) if spectra else None,
                                     np.zeros((ng, nmis, 3), np.int32) if spectra else None,
                                     np.zeros((ng, nmis, nb, 2), np.float32) if spectra else None)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.misfit), dp(out.scale), fp(out.slot_misfit),      # noqa: E731
-                        fp(out.slot_norm), nb, fp(out.spectra), None if out.spectra_range is None else _ip(out.spectra_range),
-                        fp(out.spectra_ref))
-        return tail, out, outs, (x, w)
+        return (nc, _dp(x), code, _dp(w), 1 if anarchy else 0, 1 if free_scale else 0, _ip(out.best_index), _dp(out.best_misfit),
+                _ip(out.status), _dp(out.misfit), _dp(out.scale), _fp(out.slot_misfit), _fp(out.slot_norm), nb, _fp(out.spectra),
+                _ip(out.spectra_range), _fp(out.spectra_ref)), out
 
     def spectral_candidates(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                             free_scale=False, misfit=True, slot_misfit=False, spectra=False, spectra_bins=None):
@@ -1210,10 +1123,9 @@ class Engine:
         `outer_misfits_slots` takes), spectra[ngroup, nmis, spectra_bins, K, 2], spectra_range[ngroup, nmis, 3] (klo, khi,
         ntrans) and spectra_ref[ngroup, nmis, spectra_bins, 2] (reference amplitude, filter weight) with spectra=True
         (spectra_bins: `spectral_candidates_shape`'s unless given)."""
-        tail, out, outs, keep = self._spectral_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit,
-                                                                slot_misfit, spectra, spectra_bins)
-        self._ck(self.L.kiwi_hip_spectral_candidates(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0,
-                                                     1 if free_scale else 0, *outs()), "spectral_candidates")
+        args, out = self._spectral_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit,
+                                                    slot_misfit, spectra, spectra_bins)
+        self._ck(self.L.kiwi_hip_spectral_candidates(self.h, int(isrc0), int(ngroup), int(K), *args), "spectral_candidates")
         return out
 
     def spectral_candidates_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
@@ -1221,59 +1133,37 @@ class Engine:
         """`spectral_candidates` for a parameter list of any length (kiwi_hip_spectral_candidates_params), cut into pieces and
         over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list.  spectra=True without
         spectra_bins: the first group is uploaded to size the rows; a later group that needs longer ones is refused by name."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("spectral_candidates: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("spectral_candidates: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
+        head, rows = self._list_head(sourcetype, params, K, piece, "spectral_candidates")
         if spectra and spectra_bins is None:
-            self.set_source_params(sourcetype, p[:K])
-        tail, out, outs, keep = self._spectral_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, free_scale, misfit,
-                                                                slot_misfit, spectra, spectra_bins)
-        try:
-            self._ck(self.L.kiwi_hip_spectral_candidates_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail, 1 if anarchy else 0,
-                                                                1 if free_scale else 0, *outs()), "spectral_candidates")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+            self.set_source_params(sourcetype, np.atleast_2d(params)[:head[2]])
+        args, out = self._spectral_candidate_arrays(head[1], K, candidates, outer_norm, receiver_weights, anarchy, free_scale, misfit,
+                                                    slot_misfit, spectra, spectra_bins)
+        self._list_call(self.L.kiwi_hip_spectral_candidates_params, head, rows, args, "spectral_candidates")
         return out
 
     def spectral_candidates_ms(self):
         """HIP-event durations [ms] of the last `spectral_candidates`: (evaluation, the spectra kernel alone, candidate kernels,
         downloads); the host's table of kept bins and its upload lie between the first two, in neither."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_spectral_candidates_ms(self.h, _fp(ms)), "get_spectral_candidates_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_spectral_candidates_ms, 4, "get_spectral_candidates_ms")
 
     # ------------------------------------------------------------------ joint bootstrap of a spectral candidate search (kiwi_hip_spectral_candidates_bootstrap)
     def spectral_candidates_bootstrap_shape(self, K):
         """(candidates per workgroup, draws per tile, the most receivers) of the spectral bootstrap kernels for K basis sources; no
         device needed."""
-        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_spectral_candidates_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
-            raise KiwiHipError("spectral_candidates_bootstrap: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(t[0]), int(r[0])
+        return self._read_shape(self.L.kiwi_hip_spectral_candidates_bootstrap_shape, (int(K),), 3, "spectral_candidates_bootstrap")
 
-    def _spectral_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group):
+    def _spectral_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group):
         """the siblings' arrays without the offsets, which this call does not have: best_offset and group_offset of the
         `CandidateBootstrap` are filled afterwards (0 where there is a best, else -1)"""
-        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
-                                                           "spectral_candidates_bootstrap")
-
-        def args():
-            nd, dw, bv, bg, _, bc, st, gv, _, gc = tail()
-            return nd, dw, bv, bg, bc, st, gv, gc
+        args, out = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group,
+                                                     "spectral_candidates_bootstrap")
 
         def done():
             out.best_offset[:] = np.where(out.best_cand >= 0, 0, -1)
             if out.group_offset is not None:
                 out.group_offset[:] = np.where(out.group_cand >= 0, 0, -1)
             return out
-        return head, args, done
+        return args[:9] + args[10:13] + args[14:], done          # (without best_offset and group_offset)
 
     def spectral_candidates_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, outer_norm="l1norm", receiver_weights=None,
                                       anarchy=False, per_group=False):
@@ -1283,8 +1173,8 @@ class Engine:
         array leaving the device.  Returns a `CandidateBootstrap`: best_value[ndraw], best_group, best_cand[ndraw] (NaN and -1
         where every source of a draw is excluded; best_offset is 0 or -1: there are no offsets), status[ngroup]; per_group=True
         adds group_value and group_cand[ngroup, ndraw], the same per group.  A row of ones as draw 0 gives the plain winner."""
-        head, args, done = self._spectral_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
-        self._ck(self.L.kiwi_hip_spectral_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *head, 1 if anarchy else 0, *args()),
+        args, done = self._spectral_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group)
+        self._ck(self.L.kiwi_hip_spectral_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), *args),
                  "spectral_candidates_bootstrap")
         return done()
 
@@ -1293,62 +1183,29 @@ class Engine:
         """`spectral_candidates_bootstrap` for a parameter list of any length, cut into pieces and over the devices at group
         boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine holds
         the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("spectral_candidates_bootstrap: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("spectral_candidates_bootstrap: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        head, args, done = self._spectral_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
-        try:
-            self._ck(self.L.kiwi_hip_spectral_candidates_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), *head,
-                                                                          1 if anarchy else 0, *args()), "spectral_candidates_bootstrap")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece, "spectral_candidates_bootstrap")
+        args, done = self._spectral_bootstrap_arrays(head[1], K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group)
+        self._list_call(self.L.kiwi_hip_spectral_candidates_bootstrap_params, head, rows, args, "spectral_candidates_bootstrap")
         return done()
 
     def spectral_candidates_bootstrap_ms(self):
         """HIP-event durations [ms] of the last `spectral_candidates_bootstrap`: (evaluation, the spectra kernel, the slot kernel,
         bootstrap kernels, downloads)."""
-        ms = np.zeros(5, np.float32)
-        self._ck(self.L.kiwi_hip_get_spectral_candidates_bootstrap_ms(self.h, _fp(ms)), "get_spectral_candidates_bootstrap_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_spectral_candidates_bootstrap_ms, 5, "get_spectral_candidates_bootstrap_ms")
 
     # ------------------------------------------------------------------ candidates under the time-domain l1norm / l2norm (kiwi_hip_waveform_candidates)
     def waveform_candidates_shape(self, K):
         """(candidates per workgroup, samples per LDS stage) of `waveform_candidates` for K basis sources; needs no device."""
-        c, s = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_waveform_candidates_shape(int(K), _ip(c), _ip(s)):
-            raise KiwiHipError("waveform_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(s[0])
+        return self._read_shape(self.L.kiwi_hip_waveform_candidates_shape, (int(K),), 2, "waveform_candidates")
 
-    def _waveform_candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, misfit, slot_misfit):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        K, ng = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("waveform_candidates: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != K:
-            raise KiwiHipError("waveform_candidates: candidates must be [ncand, K = %d]" % K)
-        nc, nrec = len(x), len(self.components)
-        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+    def _waveform_candidate_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, anarchy, misfit, slot_misfit):
+        code, x, w = self._candidate_inputs("waveform_candidates", outer_norm, K, candidates, receiver_weights)
+        ng, nc, nmis = int(ngroup), len(x), self._nslots()
         out = WaveformCandidateScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nc)) if misfit else None,
                                     np.zeros((ng, nc, nmis), np.float32) if slot_misfit else None,
                                     np.zeros((ng, nmis), np.float32) if slot_misfit else None)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.misfit), fp(out.slot_misfit), fp(out.slot_norm))      # noqa: E731
-        return tail, out, outs, (x, w)
+        return (nc, _dp(x), code, _dp(w), 1 if anarchy else 0, _ip(out.best_index), _dp(out.best_misfit), _ip(out.status), _dp(out.misfit),
+                _fp(out.slot_misfit), _fp(out.slot_norm)), out
 
     def waveform_candidates(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False, misfit=True,
                             slot_misfit=False):
@@ -1358,75 +1215,40 @@ class Engine:
         status[ngroup] (0 evaluated, 1 no receiver counts, 2 a basis source failed to discretise), misfit[ngroup, ncand]
         (misfit=True), slot_misfit[ngroup, ncand, nmis] and slot_norm[ngroup, nmis] float32 (slot_misfit=True: what
         `outer_misfits_slots` takes).  There is no free scale: the moment axis is more candidates."""
-        tail, out, outs, keep = self._waveform_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, slot_misfit)
-        self._ck(self.L.kiwi_hip_waveform_candidates(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0, *outs()),
-                 "waveform_candidates")
+        args, out = self._waveform_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, anarchy, misfit, slot_misfit)
+        self._ck(self.L.kiwi_hip_waveform_candidates(self.h, int(isrc0), int(ngroup), int(K), *args), "waveform_candidates")
         return out
 
     def waveform_candidates_params(self, sourcetype, params, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                                    misfit=True, slot_misfit=False, piece=0):
         """`waveform_candidates` for a parameter list of any length (kiwi_hip_waveform_candidates_params), cut into pieces and
         over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("waveform_candidates: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("waveform_candidates: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs, keep = self._waveform_candidate_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit, slot_misfit)
-        try:
-            self._ck(self.L.kiwi_hip_waveform_candidates_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail, 1 if anarchy else 0,
-                                                                *outs()), "waveform_candidates")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece, "waveform_candidates")
+        args, out = self._waveform_candidate_arrays(head[1], K, candidates, outer_norm, receiver_weights, anarchy, misfit, slot_misfit)
+        self._list_call(self.L.kiwi_hip_waveform_candidates_params, head, rows, args, "waveform_candidates")
         return out
 
     def waveform_candidates_ms(self):
         """HIP-event durations [ms] of the last `waveform_candidates`: (evaluation, the slot kernel, the fold kernels, downloads);
         the host's tables of a chunk and their upload lie between the first two, in neither."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_waveform_candidates_ms(self.h, _fp(ms)), "get_waveform_candidates_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_waveform_candidates_ms, 4, "get_waveform_candidates_ms")
 
     # ------------------------------------------------------------------ candidates under floating_l1norm / floating_l2norm (kiwi_hip_waveform_candidates_floating)
     def waveform_candidates_floating_shape(self, K):
         """(candidates per workgroup, samples per LDS stage, shifts per pass) of `waveform_candidates_floating` for K basis sources;
         needs no device."""
-        c, s, j = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_waveform_candidates_floating_shape(int(K), _ip(c), _ip(s), _ip(j)):
-            raise KiwiHipError("waveform_candidates_floating: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(s[0]), int(j[0])
+        return self._read_shape(self.L.kiwi_hip_waveform_candidates_floating_shape, (int(K),), 3, "waveform_candidates_floating")
 
-    def _waveform_candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, misfit, cand_shift, slot_misfit):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        K, ng = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("waveform_candidates_floating: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != K:
-            raise KiwiHipError("waveform_candidates_floating: candidates must be [ncand, K = %d]" % K)
-        nc, nrec = len(x), len(self.components)
-        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+    def _waveform_candidate_floating_arrays(self, ngroup, K, candidates, outer_norm, receiver_weights, anarchy, misfit, cand_shift,
+                                            slot_misfit):
+        code, x, w = self._candidate_inputs("waveform_candidates_floating", outer_norm, K, candidates, receiver_weights)
+        ng, nc, nrec, nmis = int(ngroup), len(x), len(self.components), self._nslots()
         out = WaveformCandidateFloatingScan(np.zeros(ng, np.int32), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, nrec), np.int32),
                                             np.zeros((ng, nc)) if misfit else None, np.zeros((ng, nc, nrec), np.int16) if cand_shift else None,
                                             np.zeros((ng, nc, nmis), np.float32) if slot_misfit else None,
                                             np.zeros((ng, nmis), np.float32) if slot_misfit else None)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
-        sp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_short))      # noqa: E731
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_index), dp(out.best_misfit), _ip(out.status), _ip(out.best_shift), dp(out.misfit), sp(out.cand_shift),      # noqa: E731
-                        fp(out.slot_misfit), fp(out.slot_norm))
-        return tail, out, outs, (x, w)
+        return (nc, _dp(x), code, _dp(w), 1 if anarchy else 0, _ip(out.best_index), _dp(out.best_misfit), _ip(out.status),
+                _ip(out.best_shift), _dp(out.misfit), _sp(out.cand_shift), _fp(out.slot_misfit), _fp(out.slot_norm)), out
 
     def waveform_candidates_floating(self, isrc0, ngroup, K, candidates, outer_norm="l1norm", receiver_weights=None, anarchy=False,
                                      misfit=True, cand_shift=False, slot_misfit=False):
@@ -1438,9 +1260,9 @@ class Engine:
         misfit[ngroup, ncand] (misfit=True), cand_shift[ngroup, ncand, nrec] int16 (cand_shift=True, needs misfit),
         slot_misfit[ngroup, ncand, nmis] and slot_norm[ngroup, nmis] float32 (slot_misfit=True: what `outer_misfits_slots`
         takes).  There is no free scale."""
-        tail, out, outs, keep = self._waveform_candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit,
-                                                                         cand_shift, slot_misfit)
-        self._ck(self.L.kiwi_hip_waveform_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0, *outs()),
+        args, out = self._waveform_candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, anarchy, misfit, cand_shift,
+                                                             slot_misfit)
+        self._ck(self.L.kiwi_hip_waveform_candidates_floating(self.h, int(isrc0), int(ngroup), int(K), *args),
                  "waveform_candidates_floating")
         return out
 
@@ -1448,66 +1270,36 @@ class Engine:
                                             anarchy=False, misfit=True, cand_shift=False, slot_misfit=False, piece=0):
         """`waveform_candidates_floating` for a parameter list of any length (kiwi_hip_waveform_candidates_floating_params), cut
         into pieces and over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("waveform_candidates_floating: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("waveform_candidates_floating: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs, keep = self._waveform_candidate_floating_arrays(ngroup, K, candidates, outer_norm, receiver_weights, misfit,
-                                                                         cand_shift, slot_misfit)
-        try:
-            self._ck(self.L.kiwi_hip_waveform_candidates_floating_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
-                                                                         1 if anarchy else 0, *outs()), "waveform_candidates_floating")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece, "waveform_candidates_floating")
+        args, out = self._waveform_candidate_floating_arrays(head[1], K, candidates, outer_norm, receiver_weights, anarchy, misfit, cand_shift,
+                                                             slot_misfit)
+        self._list_call(self.L.kiwi_hip_waveform_candidates_floating_params, head, rows, args, "waveform_candidates_floating")
         return out
 
     def waveform_candidates_floating_ms(self):
         """HIP-event durations [ms] of the last `waveform_candidates_floating`: (evaluation, the floating slot kernel, the fold
         kernels, downloads); the host's tables of a chunk and their upload lie between the first two, in neither."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_waveform_candidates_floating_ms(self.h, _fp(ms)), "get_waveform_candidates_floating_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_waveform_candidates_floating_ms, 4, "get_waveform_candidates_floating_ms")
 
     # ------------------------------------------------------------------ l1norm / l2norm candidates at many origin times (kiwi_hip_waveform_candidates_time_scan)
     def waveform_candidates_time_scan_shape(self, K):
         """(candidates per workgroup, extended samples per LDS stage, offsets per pass) of `waveform_candidates_time_scan` for K
         basis sources; needs no device."""
-        c, s, j = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_waveform_candidates_time_scan_shape(int(K), _ip(c), _ip(s), _ip(j)):
-            raise KiwiHipError("waveform_candidates_time_scan: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(s[0]), int(j[0])
+        return self._read_shape(self.L.kiwi_hip_waveform_candidates_time_scan_shape, (int(K),), 3, "waveform_candidates_time_scan")
 
     def waveform_candidates_time_scan_rows(self, k0, kstep, nk):
         """The layout of the `rows` array of `waveform_candidates_time_scan` for these offsets: (S = max |k|, floats per basis
         source, row_offset[nmis]); extended sample e of slot m lies at row_offset[m] + S + e."""
-        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
+        nmis = self._nslots()
         S, stride, ofs = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(max(nmis, 1), np.int32)
         self._ck(self.L.kiwi_hip_waveform_candidates_time_scan_rows(self.h, int(k0), int(kstep), int(nk), _ip(S), _ip(stride), _ip(ofs)),
                  "waveform_candidates_time_scan")
         return int(S[0]), int(stride[0]), ofs[:nmis].copy()
 
-    def _waveform_candidate_time_scan_arrays(self, ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, cand_misfit, cand_offset,
-                                             misfit, slot_misfit, rows):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        K, ng, nk = int(K), int(ngroup), int(nk)
-        if not 1 <= K <= self.linear_fit_max_basis():
-            raise KiwiHipError("waveform_candidates_time_scan: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != K:
-            raise KiwiHipError("waveform_candidates_time_scan: candidates must be [ncand, K = %d]" % K)
-        nc, nrec = len(x), len(self.components)
-        nmis = sum(len(c) for ir, c in enumerate(self.components) if self.enabled[ir])
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+    def _waveform_candidate_time_scan_arrays(self, ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy, cand_misfit,
+                                             cand_offset, misfit, slot_misfit, rows):
+        code, x, w = self._candidate_inputs("waveform_candidates_time_scan", outer_norm, K, candidates, receiver_weights)
+        ng, K, nk, nc, nmis = int(ngroup), int(K), int(nk), len(x), self._nslots()
         nj = max(nk, 0)                              # (a bad nk is refused by the library, by name)
         S, row_offset, rows_a = 0, None, None
         if rows:
@@ -1518,13 +1310,9 @@ class Engine:
                                         np.zeros((ng, nj, nc)) if misfit else None,
                                         np.zeros((ng, nj, nc, nmis), np.float32) if slot_misfit else None,
                                         np.zeros((ng, nmis), np.float32) if slot_misfit else None, rows_a, S, row_offset)
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
-        fp = lambda a: None if a is None else _fp(a)                            # noqa: E731
-        ip = lambda a: None if a is None else _ip(a)                            # noqa: E731
-        tail = (int(k0), int(kstep), nk, nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_offset), _ip(out.best_index), dp(out.best_misfit), _ip(out.status), dp(out.cand_misfit),      # noqa: E731
-                        ip(out.cand_offset), dp(out.misfit), fp(out.slot_misfit), fp(out.slot_norm), fp(out.rows))
-        return tail, out, outs, (x, w)
+        return (int(k0), int(kstep), nk, nc, _dp(x), code, _dp(w), 1 if anarchy else 0, _ip(out.best_offset), _ip(out.best_index),
+                _dp(out.best_misfit), _ip(out.status), _dp(out.cand_misfit), _ip(out.cand_offset), _dp(out.misfit), _fp(out.slot_misfit),
+                _fp(out.slot_norm), _fp(out.rows)), out
 
     def waveform_candidates_time_scan(self, isrc0, ngroup, K, k0, kstep, nk, candidates, outer_norm="l1norm", receiver_weights=None,
                                       anarchy=False, cand_misfit=True, cand_offset=True, misfit=False, slot_misfit=False, rows=False):
@@ -1537,9 +1325,9 @@ class Engine:
         what `outer_misfits_slots` takes), rows[ngroup, K, row_stride] with shift_halo and row_offset (rows=True: the folded, scaled,
         untapered rows of the basis sources, `waveform_candidates_time_scan_rows`).  Offset 0 agrees with `waveform_candidates` to
         rounding, not bit for bit (this call combines, then tapers)."""
-        tail, out, outs, keep = self._waveform_candidate_time_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights,
-                                                                          cand_misfit, cand_offset, misfit, slot_misfit, rows)
-        self._ck(self.L.kiwi_hip_waveform_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), *tail, 1 if anarchy else 0, *outs()),
+        args, out = self._waveform_candidate_time_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy,
+                                                              cand_misfit, cand_offset, misfit, slot_misfit, rows)
+        self._ck(self.L.kiwi_hip_waveform_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), *args),
                  "waveform_candidates_time_scan")
         return out
 
@@ -1548,40 +1336,22 @@ class Engine:
                                              slot_misfit=False, rows=False, piece=0):
         """`waveform_candidates_time_scan` for a parameter list of any length (kiwi_hip_waveform_candidates_time_scan_params), cut
         into pieces and over devices as `waveform_candidates_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("waveform_candidates_time_scan: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("waveform_candidates_time_scan: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs, keep = self._waveform_candidate_time_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights,
-                                                                          cand_misfit, cand_offset, misfit, slot_misfit, rows)
-        try:
-            self._ck(self.L.kiwi_hip_waveform_candidates_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), *tail,
-                                                                          1 if anarchy else 0, *outs()), "waveform_candidates_time_scan")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, nrow = self._list_head(sourcetype, params, K, piece, "waveform_candidates_time_scan")
+        args, out = self._waveform_candidate_time_scan_arrays(head[1], K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy,
+                                                              cand_misfit, cand_offset, misfit, slot_misfit, rows)
+        self._list_call(self.L.kiwi_hip_waveform_candidates_time_scan_params, head, nrow, args, "waveform_candidates_time_scan")
         return out
 
     def waveform_candidates_time_scan_ms(self):
         """HIP-event durations [ms] of the last `waveform_candidates_time_scan`: (evaluation, the rows and scan kernels, the fold
         kernels, downloads); the host's tables of a chunk and their upload lie between the first two, in neither."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_waveform_candidates_time_scan_ms(self.h, _fp(ms)), "get_waveform_candidates_time_scan_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_waveform_candidates_time_scan_ms, 4, "get_waveform_candidates_time_scan_ms")
 
     # ------------------------------------------------------------------ joint bootstrap of a waveform candidate search (kiwi_hip_waveform_candidates_bootstrap)
     def waveform_candidates_bootstrap_shape(self, K):
         """(candidates per workgroup, draws per tile, the most receivers) of the waveform bootstrap kernel for K basis sources; no
         device needed."""
-        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_waveform_candidates_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
-            raise KiwiHipError("waveform_candidates_bootstrap: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(t[0]), int(r[0])
+        return self._read_shape(self.L.kiwi_hip_waveform_candidates_bootstrap_shape, (int(K),), 3, "waveform_candidates_bootstrap")
 
     def waveform_candidates_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, k0=0, kstep=1, nk=1, outer_norm="l1norm",
                                       receiver_weights=None, anarchy=False, per_group=False):
@@ -1592,10 +1362,10 @@ class Engine:
         best_value[ndraw], best_group, best_offset, best_cand[ndraw] (NaN and -1 where every source of a draw is excluded),
         status[ngroup]; per_group=True adds group_value, group_offset and group_cand[ngroup, ndraw], the same per group.  A row of
         ones as draw 0 gives the plain winner."""
-        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
-                                                           "waveform_candidates_bootstrap")
-        self._ck(self.L.kiwi_hip_waveform_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *head,
-                                                               1 if anarchy else 0, *tail()), "waveform_candidates_bootstrap")
+        args, out = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group,
+                                                     "waveform_candidates_bootstrap")
+        self._ck(self.L.kiwi_hip_waveform_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *args),
+                 "waveform_candidates_bootstrap")
         return out
 
     def waveform_candidates_bootstrap_params(self, sourcetype, params, K, candidates, draw_weights, k0=0, kstep=1, nk=1,
@@ -1603,49 +1373,27 @@ class Engine:
         """`waveform_candidates_bootstrap` for a parameter list of any length, cut into pieces and over the devices at group
         boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine holds
         the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("waveform_candidates_bootstrap: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("waveform_candidates_bootstrap: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
-                                                           "waveform_candidates_bootstrap")
-        try:
-            self._ck(self.L.kiwi_hip_waveform_candidates_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep),
-                                                                          int(nk), *head, 1 if anarchy else 0, *tail()),
-                     "waveform_candidates_bootstrap")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece, "waveform_candidates_bootstrap")
+        args, out = self._candidate_bootstrap_arrays(head[1], K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group,
+                                                     "waveform_candidates_bootstrap")
+        self._list_call(self.L.kiwi_hip_waveform_candidates_bootstrap_params, head, rows, (int(k0), int(kstep), int(nk)) + args,
+                        "waveform_candidates_bootstrap")
         return out
 
     def waveform_candidates_bootstrap_ms(self):
         """HIP-event durations [ms] of the last `waveform_candidates_bootstrap`: (evaluation, the rows and scan kernels, the fold
         kernels, bootstrap kernels, downloads)."""
-        ms = np.zeros(5, np.float32)
-        self._ck(self.L.kiwi_hip_get_waveform_candidates_bootstrap_ms(self.h, _fp(ms)), "get_waveform_candidates_bootstrap_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_waveform_candidates_bootstrap_ms, 5, "get_waveform_candidates_bootstrap_ms")
 
     # ------------------------------------------------------------------ candidates at many origin times (kiwi_hip_linear_fit_candidates_time_scan)
     def linear_fit_candidates_time_scan_shape(self, K):
         """(candidates per workgroup, receivers per LDS stage) of the candidate-scan kernel for K basis sources."""
-        c, s = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_candidates_time_scan_shape(int(K), _ip(c), _ip(s)):
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(s[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_candidates_time_scan_shape, (int(K),), 2, "linear_fit")
 
-    def _candidate_scan_arrays(self, ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit, receiver_misfit):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != int(K):
-            raise KiwiHipError("linear_fit_candidates_time_scan: candidates must be [ncand, K = %d]" % int(K))
+    def _candidate_scan_arrays(self, ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy, free_scale, marginal, misfit,
+                               receiver_misfit):
+        code, x, w = self._candidate_inputs("linear_fit_candidates_time_scan", outer_norm, K, candidates, receiver_weights,
+                                            krange="linear_fit")
         ng, K, nj, nc, nrec = int(ngroup), int(K), max(int(nk), 0), len(x), len(self.components)
         free = bool(free_scale)
         out = CandidateTimeScan(np.zeros(ng, np.int32), np.zeros((ng, nj), np.int32), np.zeros((ng, nj)),
@@ -1656,13 +1404,10 @@ class Engine:
                                 np.zeros((ng, nj, nc, nrec), np.float32) if receiver_misfit else None,
                                 np.zeros((ng, nrec), np.float32) if receiver_misfit else None,
                                 np.zeros((ng, nj, K)), np.zeros((ng, nj)), np.zeros((ng, nj), np.int32))
-        ipn = lambda a: None if a is None else _ip(a)                                  # noqa: E731
-        fpn = lambda a: None if a is None else _fp(a)                                  # noqa: E731
-        tail = (nc, dp(x), code, dp(w))
-        outs = lambda: (_ip(out.best_offset), _ip(out.best_index), dp(out.best_misfit), dp(out.best_scale), _ip(out.status),      # noqa: E731
-                        dp(out.cand_misfit), ipn(out.cand_offset), dp(out.cand_scale), dp(out.misfit), dp(out.scale),
-                        fpn(out.receiver_misfit), fpn(out.receiver_norm), dp(out.fit_coef), dp(out.fit_misfit), _ip(out.fit_status))
-        return tail, out, outs
+        return (int(k0), int(kstep), int(nk), nc, _dp(x), code, _dp(w), 1 if anarchy else 0, 1 if free_scale else 0, _ip(out.best_offset),
+                _ip(out.best_index), _dp(out.best_misfit), _dp(out.best_scale), _ip(out.status), _dp(out.cand_misfit), _ip(out.cand_offset),
+                _dp(out.cand_scale), _dp(out.misfit), _dp(out.scale), _fp(out.receiver_misfit), _fp(out.receiver_norm), _dp(out.fit_coef),
+                _dp(out.fit_misfit), _ip(out.fit_status)), out
 
     def linear_fit_candidates_time_scan(self, isrc0, ngroup, K, candidates, k0=0, kstep=1, nk=1, outer_norm="l1norm", receiver_weights=None,
                                         anarchy=False, free_scale=False, marginal=True, misfit=False, receiver_misfit=False):
@@ -1674,10 +1419,9 @@ class Engine:
         misfit[ngroup, nk, ncand] (misfit=True) and scale (free_scale); receiver_misfit[ngroup, nk, ncand, nrec] and
         receiver_norm[ngroup, nrec] float32 (receiver_misfit=True); fit_coef[ngroup, nk, K], fit_misfit and fit_status[ngroup, nk]:
         `linear_fit_time_scan` of the same groups.  Arrays not asked for are None."""
-        tail, out, outs = self._candidate_scan_arrays(ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit,
-                                                      receiver_misfit)
-        self._ck(self.L.kiwi_hip_linear_fit_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *tail,
-                                                                 1 if anarchy else 0, 1 if free_scale else 0, *outs()),
+        args, out = self._candidate_scan_arrays(ngroup, K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy, free_scale,
+                                                marginal, misfit, receiver_misfit)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_time_scan(self.h, int(isrc0), int(ngroup), int(K), *args),
                  "linear_fit_candidates_time_scan")
         return out
 
@@ -1686,65 +1430,34 @@ class Engine:
                                                receiver_misfit=False, piece=0):
         """`linear_fit_candidates_time_scan` for a parameter list of any length, cut into pieces and over the devices at group
         boundaries as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        tail, out, outs = self._candidate_scan_arrays(ngroup, K, nk, candidates, outer_norm, receiver_weights, free_scale, marginal, misfit,
-                                                      receiver_misfit)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_candidates_time_scan_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep),
-                                                                            int(nk), *tail, 1 if anarchy else 0, 1 if free_scale else 0,
-                                                                            *outs()), "linear_fit_candidates_time_scan")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._candidate_scan_arrays(head[1], K, k0, kstep, nk, candidates, outer_norm, receiver_weights, anarchy, free_scale,
+                                                marginal, misfit, receiver_misfit)
+        self._list_call(self.L.kiwi_hip_linear_fit_candidates_time_scan_params, head, rows, args, "linear_fit_candidates_time_scan")
         return out
 
     def linear_fit_candidates_time_scan_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_candidates_time_scan`: (evaluation, Gram-scan kernel, solve kernels,
         candidate-scan kernels, downloads)."""
-        ms = np.zeros(5, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_time_scan_ms(self.h, _fp(ms)), "get_linear_fit_candidates_time_scan_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_candidates_time_scan_ms, 5, "get_linear_fit_candidates_time_scan_ms")
 
     # ------------------------------------------------------------------ joint bootstrap of a candidate search (kiwi_hip_linear_fit_candidates_bootstrap)
     def linear_fit_candidates_bootstrap_shape(self, K):
         """(candidates per workgroup, draws per tile, the most receivers) of the bootstrap kernel for K basis sources; no device
         needed."""
-        c, t, r = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        if self.L.kiwi_hip_linear_fit_candidates_bootstrap_shape(int(K), _ip(c), _ip(t), _ip(r)):
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_max_basis()))
-        return int(c[0]), int(t[0]), int(r[0])
+        return self._read_shape(self.L.kiwi_hip_linear_fit_candidates_bootstrap_shape, (int(K),), 3, "linear_fit")
 
-    def _candidate_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group,
+    def _candidate_bootstrap_arrays(self, ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group,
                                     name="linear_fit_candidates_bootstrap"):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        w, _, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        x = np.ascontiguousarray(np.atleast_2d(np.asarray(candidates, np.float64)))
-        if x.ndim != 2 or x.shape[1] != int(K):
-            raise KiwiHipError("%s: candidates must be [ncand, K = %d]" % (name, int(K)))
-        nrec = len(self.components)
-        dw = np.ascontiguousarray(np.asarray(draw_weights, np.float64))
-        if dw.ndim != 2 or dw.shape[1] != nrec:
-            raise KiwiHipError("%s: draw_weights must be [ndraw, %d]" % (name, nrec))
+        code, x, w, dw = self._candidate_inputs(name, outer_norm, K, candidates, receiver_weights, draw_weights, krange="linear_fit")
         ng, nd = int(ngroup), len(dw)
         grp = (ng, nd) if per_group else None
         out = CandidateBootstrap(np.zeros(nd), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros(nd, np.int32), np.zeros(ng, np.int32),
                                  np.zeros(grp) if grp else None, np.zeros(grp, np.int32) if grp else None,
                                  np.zeros(grp, np.int32) if grp else None)
-        ipn = lambda a: None if a is None else _ip(a)                                  # noqa: E731
-        head = (len(x), dp(x), code, dp(w))
-        tail = lambda: (nd, dp(dw), dp(out.best_value), _ip(out.best_group), _ip(out.best_offset), _ip(out.best_cand), _ip(out.status),      # noqa: E731
-                        dp(out.group_value), ipn(out.group_offset), ipn(out.group_cand))
-        return head, out, tail
+        return (len(x), _dp(x), code, _dp(w), 1 if anarchy else 0, nd, _dp(dw), _dp(out.best_value), _ip(out.best_group),
+                _ip(out.best_offset), _ip(out.best_cand), _ip(out.status), _dp(out.group_value), _ip(out.group_offset),
+                _ip(out.group_cand)), out
 
     def linear_fit_candidates_bootstrap(self, isrc0, ngroup, K, candidates, draw_weights, k0=0, kstep=1, nk=1, outer_norm="l1norm",
                                         receiver_weights=None, anarchy=False, per_group=False):
@@ -1754,9 +1467,9 @@ class Engine:
         matrix.  Returns a `CandidateBootstrap`: best_value[ndraw], best_group, best_offset, best_cand[ndraw] (NaN and -1 where
         every source of a draw is excluded), status[ngroup]; per_group=True adds group_value, group_offset and
         group_cand[ngroup, ndraw], the same per group.  A row of ones as draw 0 gives the plain winner."""
-        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
-        self._ck(self.L.kiwi_hip_linear_fit_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *head,
-                                                                 1 if anarchy else 0, *tail()), "linear_fit_candidates_bootstrap")
+        args, out = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group)
+        self._ck(self.L.kiwi_hip_linear_fit_candidates_bootstrap(self.h, int(isrc0), int(ngroup), int(K), int(k0), int(kstep), int(nk), *args),
+                 "linear_fit_candidates_bootstrap")
         return out
 
     def linear_fit_candidates_bootstrap_params(self, sourcetype, params, K, candidates, draw_weights, k0=0, kstep=1, nk=1,
@@ -1764,40 +1477,25 @@ class Engine:
         """`linear_fit_candidates_bootstrap` for a parameter list of any length, cut into pieces and over the devices at group
         boundaries as `linear_fit_params` cuts it; best_group counts the groups of the whole list.  Afterwards the engine holds
         the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        head, out, tail = self._candidate_bootstrap_arrays(ngroup, K, candidates, draw_weights, outer_norm, receiver_weights, per_group)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_candidates_bootstrap_params(self.h, st, ngroup, K, _fp(p), int(piece), int(k0), int(kstep),
-                                                                            int(nk), *head, 1 if anarchy else 0, *tail()),
-                     "linear_fit_candidates_bootstrap")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._candidate_bootstrap_arrays(head[1], K, candidates, draw_weights, outer_norm, receiver_weights, anarchy, per_group)
+        self._list_call(self.L.kiwi_hip_linear_fit_candidates_bootstrap_params, head, rows, (int(k0), int(kstep), int(nk)) + args,
+                        "linear_fit_candidates_bootstrap")
         return out
 
     def linear_fit_candidates_bootstrap_ms(self):
         """HIP-event durations [ms] of the last `linear_fit_candidates_bootstrap`: (evaluation, Gram-scan kernel, solve kernels,
         bootstrap kernels, downloads)."""
-        ms = np.zeros(5, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_candidates_bootstrap_ms(self.h, _fp(ms)), "get_linear_fit_candidates_bootstrap_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_candidates_bootstrap_ms, 5, "get_linear_fit_candidates_bootstrap_ms")
 
     # ------------------------------------------------------------------ robust linear fit (kiwi_hip_linear_fit_robust)
-    def _robust_fit_arrays(self, ngroup, K, outer_norm, receiver_weights, niter, eps):
-        code = {"l1norm": 1, "l2norm": 2}.get(outer_norm)
-        if code is None:
-            raise KiwiHipError("unknown norm method: %s" % outer_norm)
-        w, fit, dp = self._linear_fit_arrays(ngroup, K, receiver_weights, False, False)
-        out = RobustFit(fit.coef, fit.misfit, fit.status, np.zeros((int(ngroup), max(int(niter), 0) + 1, 2)))
-        return code, w, out, dp
+    def _robust_fit_arrays(self, ngroup, K, outer_norm, receiver_weights, anarchy, niter, eps):
+        code = _outer_code(outer_norm)
+        K, ng = self._basis_count(K, "linear_fit"), int(ngroup)
+        w = self._receiver_weights(receiver_weights)
+        out = RobustFit(np.zeros((ng, K)), np.zeros(ng), np.zeros(ng, np.int32), np.zeros((ng, max(int(niter), 0) + 1, 2)))
+        return (code, _dp(w), 1 if anarchy else 0, int(niter), float(eps), _dp(out.coef), _dp(out.misfit), _ip(out.status),
+                _dp(out.trace)), out
 
     def linear_fit_robust(self, isrc0, ngroup, K, outer_norm="l1norm", receiver_weights=None, anarchy=False, niter=8, eps=1e-3):
         """`linear_fit` under an l1 outer norm by iteratively reweighted least squares on the device
@@ -1807,40 +1505,22 @@ class Engine:
         `RobustFit`: coef[ngroup, K], misfit[ngroup] (the global misfit under the two norms), status[ngroup] (0 solved, 1 no
         l2 start, 2 a basis source failed to discretise, 3 a reweighted system broke down: coef and misfit of the iterate
         before), trace[ngroup, niter + 1, 2] ((smoothed objective, misfit) per iterate)."""
-        code, w, out, dp = self._robust_fit_arrays(ngroup, K, outer_norm, receiver_weights, niter, eps)
-        self._ck(self.L.kiwi_hip_linear_fit_robust(self.h, int(isrc0), int(ngroup), int(K), code, dp(w), 1 if anarchy else 0, int(niter),
-                                                   float(eps), dp(out.coef), dp(out.misfit), _ip(out.status), dp(out.trace)),
-                 "linear_fit_robust")
+        args, out = self._robust_fit_arrays(ngroup, K, outer_norm, receiver_weights, anarchy, niter, eps)
+        self._ck(self.L.kiwi_hip_linear_fit_robust(self.h, int(isrc0), int(ngroup), int(K), *args), "linear_fit_robust")
         return out
 
     def linear_fit_robust_params(self, sourcetype, params, K, outer_norm="l1norm", receiver_weights=None, anarchy=False, niter=8,
                                  eps=1e-3, piece=0):
         """`linear_fit_robust` for a parameter list of any length (kiwi_hip_linear_fit_robust_params), cut into pieces and
         over devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        code, w, out, dp = self._robust_fit_arrays(ngroup, K, outer_norm, receiver_weights, niter, eps)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_robust_params(self.h, st, ngroup, K, _fp(p), int(piece), code, dp(w), 1 if anarchy else 0,
-                                                              int(niter), float(eps), dp(out.coef), dp(out.misfit), _ip(out.status),
-                                                              dp(out.trace)), "linear_fit_robust")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._robust_fit_arrays(head[1], K, outer_norm, receiver_weights, anarchy, niter, eps)
+        self._list_call(self.L.kiwi_hip_linear_fit_robust_params, head, rows, args, "linear_fit_robust")
         return out
 
     def linear_fit_robust_ms(self):
         """HIP-event durations [ms] of the last linear fit of either kind: (evaluation, l2 start, reweighting passes, downloads)."""
-        ms = np.zeros(4, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_robust_ms(self.h, _fp(ms)), "get_linear_fit_robust_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_robust_ms, 4, "get_linear_fit_robust_ms")
 
     # ------------------------------------------------------------------ wide linear fit (kiwi_hip_linear_fit_wide)
     def linear_fit_wide_max_basis(self):
@@ -1849,18 +1529,12 @@ class Engine:
 
     def linear_fit_wide_ms(self):
         """HIP-event durations [ms] of the last wide linear fit: (Gram kernels, solve kernel); `linear_fit_ms` has their sum."""
-        ms = np.zeros(2, np.float32)
-        self._ck(self.L.kiwi_hip_get_linear_fit_wide_ms(self.h, _fp(ms)), "get_linear_fit_wide_ms")
-        return tuple(float(x) for x in ms)
+        return self._read_ms(self.L.kiwi_hip_get_linear_fit_wide_ms, 2, "get_linear_fit_wide_ms")
 
-    def _wide_fit_arrays(self, ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver):
-        K, ngroup = int(K), int(ngroup)
-        if not 1 <= K <= self.linear_fit_wide_max_basis():
-            raise KiwiHipError("linear_fit: K = %d basis sources per group; 1 to %d are supported" % (K, self.linear_fit_wide_max_basis()))
+    def _wide_fit_arrays(self, ngroup, K, receiver_weights, anarchy, nonneg, penalty, penalty_relative, normal, by_receiver):
+        K, ngroup = self._basis_count(K, "linear_fit", self.linear_fit_wide_max_basis()), int(ngroup)
         nrec, ng, nn = len(self.components), K * (K + 1) // 2, K * (K + 1) // 2 + K + 1
-        w = None
-        if receiver_weights is not None:
-            w = np.ascontiguousarray(np.broadcast_to(np.asarray(receiver_weights, np.float64), (nrec,)))
+        w = self._receiver_weights(receiver_weights)
         pen = None
         if penalty is not None:
             pen = np.ascontiguousarray(penalty, np.float64)
@@ -1873,9 +1547,9 @@ class Engine:
         out = WideFit(np.zeros((ngroup, K)), np.zeros(ngroup), np.zeros(ngroup, np.int32), np.zeros(ngroup),
                       np.zeros((ngroup, nn)) if normal else None, np.zeros((ngroup, nrec, nn)) if by_receiver else None,
                       np.zeros(ngroup, np.int32), np.zeros(ngroup, np.int32))
-        dp = lambda a: None if a is None else a.ctypes.data_as(c_double_p)      # noqa: E731
         code = nonneg if isinstance(nonneg, (int, np.integer)) and not isinstance(nonneg, bool) else (1 if nonneg else 0)
-        return w, pen, int(code), out, dp
+        return (_dp(w), 1 if anarchy else 0, int(code), _dp(pen), 1 if penalty_relative else 0, _dp(out.coef), _dp(out.misfit),
+                _ip(out.status), _dp(out.pivot_min), _ip(out.npositive), _ip(out.nsolves), _dp(out.normal), _dp(out.by_receiver)), out
 
     def linear_fit_wide(self, isrc0, ngroup, K, receiver_weights=None, anarchy=False, nonneg=False, penalty=None,
                         penalty_relative=False, normal=False, by_receiver=False):
@@ -1885,37 +1559,18 @@ class Engine:
         Hanson, on the device).  Returns a `WideFit`: the fields of `LinearFit` (misfit: the DATA misfit; normal: the sums
         without the penalty; status additionally 4: the cap of 3 K solves was reached) plus npositive[ngroup] (coefficients
         > 0) and nsolves[ngroup] (Cholesky solves made)."""
-        w, pen, code, out, dp = self._wide_fit_arrays(ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver)
-        self._ck(self.L.kiwi_hip_linear_fit_wide(self.h, int(isrc0), int(ngroup), int(K), dp(w), 1 if anarchy else 0, code, dp(pen),
-                                                 1 if penalty_relative else 0, dp(out.coef), dp(out.misfit), _ip(out.status),
-                                                 dp(out.pivot_min), _ip(out.npositive), _ip(out.nsolves), dp(out.normal),
-                                                 dp(out.by_receiver)), "linear_fit_wide")
+        args, out = self._wide_fit_arrays(ngroup, K, receiver_weights, anarchy, nonneg, penalty, penalty_relative, normal, by_receiver)
+        self._ck(self.L.kiwi_hip_linear_fit_wide(self.h, int(isrc0), int(ngroup), int(K), *args), "linear_fit_wide")
         return out
 
     def linear_fit_wide_params(self, sourcetype, params, K, receiver_weights=None, anarchy=False, nonneg=False, penalty=None,
                                penalty_relative=False, normal=False, by_receiver=False, piece=0):
         """`linear_fit_wide` for a parameter list of any length (kiwi_hip_linear_fit_wide_params), cut into pieces and over
         devices as `linear_fit_params` cuts it.  Afterwards the engine holds the head of the list."""
-        p = np.ascontiguousarray(np.atleast_2d(params), np.float32)
-        st = SOURCE_TYPES.get(sourcetype, sourcetype)
-        K = int(K)
-        if p.shape[1] != self.L.kiwi_hip_source_nparams(st):
-            raise KiwiHipError("set_source_params: wrong number of source parameters")
-        if K < 1 or p.shape[0] % K or p.shape[0] == 0:
-            raise KiwiHipError("linear_fit_params: %d parameter rows are not whole groups of K = %d" % (p.shape[0], K))
-        ngroup = p.shape[0] // K
-        w, pen, code, out, dp = self._wide_fit_arrays(ngroup, K, receiver_weights, nonneg, penalty, normal, by_receiver)
-        try:
-            self._ck(self.L.kiwi_hip_linear_fit_wide_params(self.h, st, ngroup, K, _fp(p), int(piece), dp(w), 1 if anarchy else 0, code,
-                                                            dp(pen), 1 if penalty_relative else 0, dp(out.coef), dp(out.misfit),
-                                                            _ip(out.status), dp(out.pivot_min), _ip(out.npositive), _ip(out.nsolves),
-                                                            dp(out.normal), dp(out.by_receiver)), "linear_fit_wide")
-        except KiwiHipError:
-            self.nsrc = 0
-            raise
-        self.nsrc = self._uploaded_sources(len(p))
+        head, rows = self._list_head(sourcetype, params, K, piece)
+        args, out = self._wide_fit_arrays(head[1], K, receiver_weights, anarchy, nonneg, penalty, penalty_relative, normal, by_receiver)
+        self._list_call(self.L.kiwi_hip_linear_fit_wide_params, head, rows, args, "linear_fit_wide")
         return out
-
 
 def bootstrap_draw_weights(nrec, ndraw, rng, receiver_mask=None, receiver_weights=None):
     """The resampling counts of `ndraw` bootstrap draws over the enabled receivers, [ndraw, nrec] float64: row d is the

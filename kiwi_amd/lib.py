@@ -21,6 +21,14 @@ class KiwiHipError(RuntimeError):
 
 
 # kiwi_hip_residual_fn: (user, k, m, n, xs[k][n], fv[k][m]) -> int
+# The group families: kiwi_hip_<family>(ctx, isrc0, ngroup, K, ...) works on uploaded sources, kiwi_hip_<family>_params on a parameter
+# list of any length -- (sourcetype, ngroup, K, params, piece) where the former has (isrc0, ngroup, K), the rest alike --, and
+# kiwi_hip_get_<family>_ms(ctx, ms) answers the durations of the last of either.  load() types out the first and derives the others.
+GROUP_FAMILIES = ("linear_fit", "linear_fit_time_scan", "linear_fit_robust", "linear_fit_wide", "linear_fit_candidates",
+                  "linear_fit_candidates_time_scan", "linear_fit_candidates_bootstrap", "linear_fit_candidates_floating",
+                  "linear_fit_candidates_floating_bootstrap", "spectral_candidates", "spectral_candidates_bootstrap", "waveform_candidates",
+                  "waveform_candidates_floating", "waveform_candidates_time_scan", "waveform_candidates_bootstrap")
+
 RESIDUAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float))
 
 
@@ -131,22 +139,12 @@ def load():
         "kiwi_hip_get_outer_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit": [vp, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p,
                                 c_double_p, c_double_p],
-        "kiwi_hip_linear_fit_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p,
-                                       c_int_p, c_double_p, c_double_p, c_double_p],
         "kiwi_hip_linear_fit_max_basis": [],
-        "kiwi_hip_get_linear_fit_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_robust": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, C.c_double, c_double_p,
                                        c_double_p, c_int_p, c_double_p],
-        "kiwi_hip_linear_fit_robust_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int,
-                                              C.c_double, c_double_p, c_double_p, c_int_p, c_double_p],
-        "kiwi_hip_get_linear_fit_robust_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_wide": [vp, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
                                      c_double_p, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, c_double_p],
-        "kiwi_hip_linear_fit_wide_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p,
-                                            C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
-                                            c_double_p],
         "kiwi_hip_linear_fit_wide_max_basis": [],
-        "kiwi_hip_get_linear_fit_wide_ms": [vp, c_float_p],
         "kiwi_hip_misfit_bands_max": [],
         "kiwi_hip_set_misfit_bands": [vp, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p],
         "kiwi_hip_get_misfit_bands": [vp, c_int_p],
@@ -161,96 +159,49 @@ def load():
         "kiwi_hip_get_time_scan_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_time_scan": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
                                           c_double_p, c_int_p, c_double_p, c_int_p, c_double_p],
-        "kiwi_hip_linear_fit_time_scan_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p,
-                                                 C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_int_p, c_double_p],
-        "kiwi_hip_get_linear_fit_time_scan_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_time_scan_shape": [C.c_int, c_int_p, c_int_p],
         "kiwi_hip_linear_fit_candidates": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int,
                                            c_int_p, c_double_p, c_int_p, c_double_p, c_double_p, c_float_p, c_float_p, c_double_p,
                                            c_double_p],
-        "kiwi_hip_linear_fit_candidates_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int,
-                                                  c_double_p, C.c_int, C.c_int, c_int_p, c_double_p, c_int_p, c_double_p, c_double_p,
-                                                  c_float_p, c_float_p, c_double_p, c_double_p],
-        "kiwi_hip_get_linear_fit_candidates_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_shape": [C.c_int, c_int_p, c_int_p],
         "kiwi_hip_linear_fit_candidates_time_scan": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
                                                      c_double_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_double_p, c_int_p,
                                                      c_double_p, c_int_p, c_double_p, c_double_p, c_double_p, c_float_p, c_float_p,
                                                      c_double_p, c_double_p, c_int_p],
-        "kiwi_hip_linear_fit_candidates_time_scan_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                            C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, c_int_p, c_int_p,
-                                                            c_double_p, c_double_p, c_int_p, c_double_p, c_int_p, c_double_p, c_double_p,
-                                                            c_double_p, c_float_p, c_float_p, c_double_p, c_double_p, c_int_p],
-        "kiwi_hip_get_linear_fit_candidates_time_scan_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_time_scan_shape": [C.c_int, c_int_p, c_int_p],
         "kiwi_hip_linear_fit_candidates_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
                                                      c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p,
                                                      c_double_p, c_int_p, c_int_p],
-        "kiwi_hip_linear_fit_candidates_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                            C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
-                                                            c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p],
-        "kiwi_hip_get_linear_fit_candidates_bootstrap_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_linear_fit_candidates_floating": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int,
                                                     c_int_p, c_double_p, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_short), c_float_p,
                                                     c_float_p],
-        "kiwi_hip_linear_fit_candidates_floating_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int,
-                                                           c_double_p, C.c_int, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
-                                                           C.POINTER(C.c_short), c_float_p, c_float_p],
-        "kiwi_hip_get_linear_fit_candidates_floating_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_floating_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_linear_fit_candidates_floating_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int,
                                                               C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p,
                                                               c_int_p, c_int_p],
-        "kiwi_hip_linear_fit_candidates_floating_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p,
-                                                                     C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p,
-                                                                     c_int_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p],
-        "kiwi_hip_get_linear_fit_candidates_floating_bootstrap_ms": [vp, c_float_p],
         "kiwi_hip_linear_fit_candidates_floating_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_spectral_candidates": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, c_int_p,
                                          c_double_p, c_int_p, c_double_p, c_double_p, c_float_p, c_float_p, C.c_int, c_float_p, c_int_p,
                                          c_float_p],
-        "kiwi_hip_spectral_candidates_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
-                                                C.c_int, C.c_int, c_int_p, c_double_p, c_int_p, c_double_p, c_double_p, c_float_p, c_float_p,
-                                                C.c_int, c_float_p, c_int_p, c_float_p],
-        "kiwi_hip_get_spectral_candidates_ms": [vp, c_float_p],
         "kiwi_hip_spectral_candidates_shape": [vp, C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_waveform_candidates": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, c_int_p, c_double_p,
                                          c_int_p, c_double_p, c_float_p, c_float_p],
-        "kiwi_hip_waveform_candidates_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p,
-                                                C.c_int, c_int_p, c_double_p, c_int_p, c_double_p, c_float_p, c_float_p],
-        "kiwi_hip_get_waveform_candidates_ms": [vp, c_float_p],
         "kiwi_hip_waveform_candidates_shape": [C.c_int, c_int_p, c_int_p],
         "kiwi_hip_waveform_candidates_floating": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, c_int_p,
                                                   c_double_p, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_short), c_float_p, c_float_p],
-        "kiwi_hip_waveform_candidates_floating_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int,
-                                                         c_double_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
-                                                         C.POINTER(C.c_short), c_float_p, c_float_p],
-        "kiwi_hip_get_waveform_candidates_floating_ms": [vp, c_float_p],
         "kiwi_hip_waveform_candidates_floating_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_waveform_candidates_time_scan": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
                                                    c_double_p, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p, c_double_p, c_int_p, c_double_p,
                                                    c_float_p, c_float_p, c_float_p],
-        "kiwi_hip_waveform_candidates_time_scan_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                          c_double_p, C.c_int, c_double_p, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p,
-                                                          c_double_p, c_int_p, c_double_p, c_float_p, c_float_p, c_float_p],
-        "kiwi_hip_get_waveform_candidates_time_scan_ms": [vp, c_float_p],
         "kiwi_hip_waveform_candidates_time_scan_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_waveform_candidates_time_scan_rows": [vp, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_waveform_candidates_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int,
                                                    c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_int_p,
                                                    c_double_p, c_int_p, c_int_p],
-        "kiwi_hip_waveform_candidates_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                          C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p,
-                                                          c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p],
-        "kiwi_hip_get_waveform_candidates_bootstrap_ms": [vp, c_float_p],
         "kiwi_hip_waveform_candidates_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_spectral_candidates_bootstrap": [vp, C.c_int, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, C.c_int, C.c_int,
                                                    c_double_p, c_double_p, c_int_p, c_int_p, c_int_p, c_double_p, c_int_p],
-        "kiwi_hip_spectral_candidates_bootstrap_params": [vp, C.c_int, C.c_int, C.c_int, c_float_p, C.c_int, C.c_int, c_double_p, C.c_int,
-                                                          c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p, c_int_p,
-                                                          c_double_p, c_int_p],
-        "kiwi_hip_get_spectral_candidates_bootstrap_ms": [vp, c_float_p],
         "kiwi_hip_spectral_candidates_bootstrap_shape": [C.c_int, c_int_p, c_int_p, c_int_p],
         "kiwi_hip_get_geometry": [vp, C.c_int, C.c_int, C.c_int, c_int_p, vp],
         "kiwi_hip_get_receiver_geometry": [vp, C.c_int, c_double_p, c_double_p, c_double_p],
@@ -265,6 +216,10 @@ def load():
         "kiwi_hip_lmdif": [RESIDUAL_FN, vp, C.c_int, C.c_int, c_float_p, c_float_p, C.c_float, C.c_float, C.c_float, C.c_int,
                            C.c_float, c_float_p, C.c_int, C.c_float, c_int_p, c_int_p],
     }
+    for family in GROUP_FAMILIES:
+        uploaded = sig["kiwi_hip_" + family]
+        sig["kiwi_hip_%s_params" % family] = uploaded[:1] + [C.c_int, C.c_int, C.c_int, c_float_p, C.c_int] + uploaded[4:]
+        sig["kiwi_hip_get_%s_ms" % family] = [vp, c_float_p]
     L.kiwi_hip_principal_axes.argtypes = [C.c_int, c_float_p, c_float_p, c_float_p]
     L.kiwi_hip_principal_axes.restype = C.c_int
     for name, argtypes in sig.items():
