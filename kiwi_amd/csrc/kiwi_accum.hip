@@ -81,9 +81,9 @@ void launch_multi(const AccumArgs &a, dim3 grid, int NS, int ntiles, const int *
 void launch_multi_plan(const AccumArgs &a, int NS, int ngroups, const int *mate, const int *wider, PlanSrc *plan)
 {
     const dim3 grid((unsigned)ngroups, (unsigned)((a.nrec + 63) / 64));
-    if (NS == 4) hipLaunchKernelGGL(multi_plan_kernel<4>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.recv, a.tab, a.pairflag, mate, wider,
+    if (NS == 4) hipLaunchKernelGGL(multi_plan_kernel<4>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.pitch, a.recv, a.tab, a.pairflag, mate, wider,
                                     a.plan_ofs, (int4 *)plan, a.plan_regular, a.plan_repeat, a.plan_count);
-    else         hipLaunchKernelGGL(multi_plan_kernel<2>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.recv, a.tab, a.pairflag, mate, wider,
+    else         hipLaunchKernelGGL(multi_plan_kernel<2>, grid, dim3(64), 0, a.stream, a.recs, a.cent_ofs, a.isrc0, a.nrec, a.pitch, a.recv, a.tab, a.pairflag, mate, wider,
                                     a.plan_ofs, (int4 *)plan, a.plan_regular, a.plan_repeat, a.plan_count);
 }
 #endif

@@ -386,6 +386,7 @@ struct HaloRegs { f4u v[4]; };
 // DescLanes: the lane-distributed descriptor row (write_tab's layout, or desc_expand's copy of it): read-lanes and, for the halo,
 // ds_bpermute.
 struct DescLanes {
+    static constexpr bool linear = false;
     int ta, tb;
     __device__ __forceinline__ int a(int ig, int k) const { return REC_I(ta, 4 * ig + k); }
     __device__ __forceinline__ int b(int ig, int k) const { return REC_I(tb, 4 * ig + k); }
@@ -398,9 +399,14 @@ struct DescLanes {
         return __builtin_amdgcn_ballot_w64(lane_ok) == ~0ull;
     }
 };
+// maximum / minimum of wave-uniform integers on the scalar unit (left to itself the compiler moves them to the vector pipe
+// for its three-operand forms)
+__device__ __forceinline__ int smax_u(int a, int b) { int r; asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
+__device__ __forceinline__ int smin_u(int a, int b) { int r; asm("s_min_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
 // DescPlan: compact descriptors held in scalar registers (PlanSrc::row, o): what desc_expand lays out in lanes, tb = (row_k + ig -
 // row_0) pitch and ta = tb + o_k, as scalar arithmetic (the same 32-bit sums); `hoff`: the halo lane's component times pitch.
 struct DescPlan {
+    static constexpr bool linear = true;            // a(ig, k) = a(0, k) + ig pitch
     int b0[4], o[4], pitch, hoff;
     __device__ __forceinline__ int b(int ig, int k) const { return b0[k] + ig * pitch; }
     __device__ __forceinline__ int a(int ig, int k) const { return b0[k] + ig * pitch + o[k]; }
@@ -409,7 +415,8 @@ struct DescPlan {
     __device__ __forceinline__ bool fast(int jb, int lds_tile, int pitch_, int, int) const
     {
         // (ta - tb = o_k in every lane below 4 ng: the lanes' test is that of the smallest and the largest o_k)
-        const int omin = min(min(o[0], o[1]), min(o[2], o[3])), omax = max(max(o[0], o[1]), max(o[2], o[3]));
+        // (on the scalar unit: the compiler's three-operand minimum and maximum are vector instructions, five moves to feed them)
+        const int omin = smin_u(smin_u(o[0], o[1]), smin_u(o[2], o[3])), omax = smax_u(smax_u(o[0], o[1]), smax_u(o[2], o[3]));
         return omin + jb >= 0 && omax + jb + lds_tile <= pitch_;
     }
 };
@@ -1424,6 +1431,19 @@ __device__ __forceinline__ void one_issue_hidden(f4u (&v)[4], int ig, int p, int
         asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v[k]) : "v"(voff), "s"(rs), "s"(soff));
     }
 }
+// The same for descriptors that are linear in the component (DescPlan): t[k] = a(0, k) + jb, formed once per group and kept from the
+// compiler's reassociation by the caller, leaves an add and a shift per load (three scalar instructions as the sum of four terms).
+__device__ __forceinline__ void one_issue_hidden_linear(f4u (&v)[4], int igp /* ig pitch */, int p, const float *__restrict__ G, const int (&t)[4])
+{
+    const size_t gi = (size_t)G;
+    const v4i_t rs = { (int)(unsigned)gi, (int)((unsigned)(gi >> 32) & 0xffffu), -1, 0x00020000 };      // (= gf_rsrc(G))
+    const int voff = (int)(4u * (unsigned)p);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int soff = (int)(4u * (unsigned)(t[k] + igp));
+        asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v[k]) : "v"(voff), "s"(rs), "s"(soff));
+    }
+}
 // (ONE statement per task, the choice between the two counts inside it: two statements on the two sides of a branch would each be a
 // definition of the task's registers, and the compiler joins them through copies placed in FRONT of the wait -- copies of
 // registers whose loads are still in flight)
@@ -1526,6 +1546,23 @@ __device__ __forceinline__ void mfma_finish(const RowsDw &v, float *__restrict__
 // bank = dword address mod 32: lanes 4 b + j of a group cover banks 8 j + 4 (b & 1) .. + 3)
 template <int NG, int NS> __host__ __device__ constexpr int multi_set_stride() { return NG * (1024 / NS + kHalo) + ((NS == 4 && KIWI_MFMA_BLEND) ? 8 : 0); }
 
+// (A/B: -DKIWI_MULTI_COEF_WARM=1 warms the coefficient lines of a group with plans too, as the record path does: measured as worth
+// nothing, DESIGN 3.3)
+#ifndef KIWI_MULTI_COEF_WARM
+#define KIWI_MULTI_COEF_WARM 0
+#endif
+
+// whether wave `wv` has the last wave-task of multi_build (1) or not (0)
+template <int NG, int NS> __device__ __forceinline__ int multi_last_task(int wv)
+{
+    // (wv is 0 .. 3: two sources per workgroup, or four and a multiple of four components, and every wave has every task)
+    if constexpr (NS == 2 || NG % 4 == 0) return 1;
+    constexpr int N = (NG + 3) / 4;                      // (NS = 4: tasks per wave at most)
+    // (the sign bit of component - NG, not a comparison: a select on a wave-uniform condition is a vector instruction to the
+    // compiler, and its result reaches an assembly statement's scalar operand in a vector register)
+    return (int)((unsigned)(wv + 4 * (N - 1) - NG) >> 31);          // (NS = 4: the last task's component is wv + 4 (N - 1))
+}
+
 // Build of accumulate_multi_kernel: NS tile sets of TILE = 1024 / NS samples (+ halo).  A wave-task = one component's 64 main
 // chunks (chunk = 4 samples) of one 256-sample slab; NS = 2: wave w takes components 2 i + (w >> 1), slab w & 1; NS = 4: wave w
 // components w + 4 i (one slab); the halo chunks go to the LAST threads, chunk-major (thread 255 - q: chunk q / NG of component
@@ -1534,20 +1571,46 @@ template <int NG, int NS> __host__ __device__ constexpr int multi_set_stride() {
 // blended with the weights of each source into its tile set (gfdb.f90:946-949, summed in this order) -- `only` >= 0: into that
 // source's set alone.  A centroid exactly on a node carries the weights (1, 0, 0, 0) over four copies of its row:
 // 1 v + 0 v + 0 v + 0 v is v bit for bit, so there is no unblended variant.
-template <int NG, bool FAST, int NS, typename D, typename Shadow>
+// `reweigh(gl)`: the blend weights once more (gl[].w), for the halo's blend.  It stands on the far side of a branch; weights it shares
+// with the tasks in front of it reach it as 64-bit (w, w) pairs which the compiler lays out in the common block, two scalar moves per
+// weight in EVERY wave, whereas weights that arrive inside the block are broadcast by the packed instructions' operand selects.  With
+// plans (RW) reweigh() is NS scalar loads from lines the shadow's loads have just brought in, in the one wave that has halo lanes and
+// the fewest tasks; without, the halo takes gw as before.  (The same for the last wave-task of the waves that have one was measured
+// and costs time: those waves are the ones the barrier waits for, and the loads' round trip stands in their way -- DESIGN 3.3.)
+// The lanes' halo test -- which lanes hold a halo chunk of this group -- comes from the caller as `hact` WITHOUT plans (!RW: it
+// made `whalo` from it by a ballot; `hq`, `npos` and `reweigh` are unused) and is formed here, inside the halo's block, from `hq`, `hph`
+// and `npos` WITH plans (RW: `hact` is unused, `whalo` is the caller's scalar compare): halo_lanes() below, the one place that knows.
+template <int NG, bool FAST, int NS, bool RW, typename D, typename Shadow, typename Reweigh>
 __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, int lane, int tid, int jb, const float *__restrict__ G,
                                             int pitch, const D &d, const GeoRec (&gw)[NS], int only, bool hact, bool whalo, int hig, int hph,
-                                            Shadow shadow)
+                                            int lastf /* multi_last_task(wv), in a scalar register */, int hq, int npos /* RW: hact is formed here */,
+                                            Shadow shadow, Reweigh reweigh)
 {
     constexpr int TILE = 1024 / NS, LDS_TILE = TILE + kHalo, DEPTH = 3, SET = multi_set_stride<NG, NS>();
     constexpr int N = (NS == 2) ? NG / 2 : (NG + 3) / 4;           // wave-tasks per wave at most
     const int p = (NS == 2) ? 4 * (64 * (wv & 1) + lane) : 4 * lane;
     auto comp = [&](int i) { return (NS == 2) ? 2 * i + (wv >> 1) : wv + 4 * i; };
+    // (linear descriptors: the group's four row positions once, see one_issue_hidden_linear; opaque, or the compiler spreads the sum
+    // over the loads again)
+    int t[4] = { 0, 0, 0, 0 };
+    if constexpr (FAST && D::linear) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) { t[k] = d.a(0, k) + jb; asm("" : "+s"(t[k])); }
+    }
     HaloRegs hv;
     // (a wave without a halo lane skips the halo; in the others inactive lanes load a valid chunk too: no merge of registers)
     if (whalo) hv = halo_issue<true, FAST>(true, hig, hph, jb, G, pitch, d);
+    // (RW: formed HERE, in the one wave that has any halo lane, from a copy of `npos` the compiler cannot move: as a value of the
+    // group's top it is a compare and two lane reads in every wave)
+    auto halo_lanes = [&]() __attribute__((always_inline)) {
+        if constexpr (RW) {
+            int npos_o = npos;
+            asm volatile("" : "+s"(npos_o));
+            return hq < 16 * NG && hph < npos_o;
+        } else return hact;
+    };
     // (tasks 0 .. N - 2 exist in every wave, the last one only where its component does: NS = 4, NG = 10: waves 0 and 1)
-    const bool last_ok = comp(N - 1) < NG;
+    const bool last_ok = lastf != 0;
     if constexpr (KIWI_MFMA_BLEND && FAST && NS == 4 && KIWI_ARITH == 0) {
         // ---- the products of the blend on the matrix pipe (see mfma_finish); `only` >= 0: every lane blends, the lanes of that source write
         RowsDw v[N];
@@ -1567,7 +1630,6 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
             if (i < N - 1 || last_ok) {
                 const int behind = (i + DEPTH < N ? i + DEPTH : N) - 1 - i;
                 const bool short_ = behind > 0 && i + DEPTH >= N;
-                const int lastf = __builtin_amdgcn_readfirstlane(last_ok ? 1 : 0);
                 switch (behind) {
                 case 0: vm_wait16<0, 0>(v[i], 1); break;
                 case 1: if (short_) vm_wait16<16, 0>(v[i], lastf); else vm_wait16<16, 16>(v[i], 1); break;
@@ -1578,15 +1640,17 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
             if (i + DEPTH < N && (i + DEPTH < N - 1 || last_ok)) rows_issue_dw(v[i + DEPTH], comp(i + DEPTH), lane, jb, G, d);
         }
         if (whalo) {
+            const bool hact_l = halo_lanes();
 #pragma unroll
             for (int s = 0; s < NS; s++)
-                if (only < 0 || only == s) halo_finish<true>(hact, hv, tile0 + s * SET, LDS_TILE, hig, hph, gw[s]);
+                if (only < 0 || only == s) halo_finish<true>(hact_l, hv, tile0 + s * SET, LDS_TILE, hig, hph, gw[s]);
         }
         return;
     }
     f4u v[N][4];
     auto issue = [&](int i) __attribute__((always_inline)) {
-        if constexpr (FAST) one_issue_hidden(v[i], comp(i), p, jb, G, d);
+        if constexpr (FAST && D::linear) one_issue_hidden_linear(v[i], comp(i) * pitch, p, G, t);
+        else if constexpr (FAST) one_issue_hidden(v[i], comp(i), p, jb, G, d);
         else one_issue<true, false>(v[i], comp(i), p, jb, G, pitch, d);
     };
 #pragma unroll
@@ -1607,7 +1671,6 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
                 // (i is a constant once the loop is unrolled: the switch folds to one statement)
                 const int behind = (i + DEPTH < N ? i + DEPTH : N) - 1 - i;
                 const bool short_ = behind > 0 && i + DEPTH >= N;         // (the window reaches the last task: one less where it is missing)
-                const int lastf = __builtin_amdgcn_readfirstlane(last_ok ? 1 : 0);       // (in a scalar register, also where it is a constant)
                 switch (behind) {
                 case 0: vm_wait<0, 0>(v[i], 1); break;
                 case 1: if (short_) vm_wait<4, 0>(v[i], lastf); else vm_wait<4, 4>(v[i], 1); break;
@@ -1621,9 +1684,18 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
         if (i + DEPTH < N && (i + DEPTH < N - 1 || last_ok)) issue(i + DEPTH);
     }
     if (whalo) {
+        if constexpr (RW) {
+            GeoRec gl[NS];
+            reweigh(gl);
+            const bool hact_l = halo_lanes();
 #pragma unroll
-        for (int s = 0; s < NS; s++)
-            if (only < 0 || only == s) halo_finish<true>(hact, hv, tile0 + s * SET, LDS_TILE, hig, hph, gw[s]);
+            for (int s = 0; s < NS; s++)
+                if (only < 0 || only == s) halo_finish<true>(hact_l, hv, tile0 + s * SET, LDS_TILE, hig, hph, gl[s]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+                if (only < 0 || only == s) halo_finish<true>(halo_lanes(), hv, tile0 + s * SET, LDS_TILE, hig, hph, gw[s]);
+        }
     }
 }
 
@@ -1650,11 +1722,6 @@ __device__ __forceinline__ void multi_build(float *__restrict__ tile0, int wv, i
 // `mate[k]` says so for group k.  Of those the kernel takes the (group, receiver) combinations where every source is "clean"
 // for the receiver (horizontal and vertical components, no missing trace, no tail rule: pairflag of geometry_kernel);
 // accumulate_grouped_kernel runs behind it for everything else (pairsel 3).
-// maximum / minimum of wave-uniform integers on the scalar unit (left to itself the compiler moves them to the vector pipe
-// for its three-operand forms)
-__device__ __forceinline__ int smax_u(int a, int b) { int r; asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
-__device__ __forceinline__ int smin_u(int a, int b) { int r; asm("s_min_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc"); return r; }
-
 template <int NS>
 __device__ __forceinline__ bool multi_taken(const RecvDev &rv, const int *__restrict__ pairflag, const int *__restrict__ mate,
                                             int s, int nrec, int r)
@@ -1675,7 +1742,7 @@ __device__ __forceinline__ bool multi_taken(const RecvDev &rv, const int *__rest
 // (source group, receiver), once per evaluation, and walks the pair's centroid groups; the decisions are those of the kernel's own
 // loop top (the !PLAN branch there), statement for statement.
 template <int NS>
-__global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict__ recs, const int *__restrict__ cent_ofs, int isrc0, int nrec,
+__global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict__ recs, const int *__restrict__ cent_ofs, int isrc0, int nrec, int pitch,
     const RecvDev *__restrict__ recv, const int *__restrict__ off4, const int *__restrict__ pairflag, const int *__restrict__ mate,
     const int *__restrict__ mate_wider, const int *__restrict__ plan_ofs, int4 *__restrict__ plan,
     int regular_on /* 0: no plan is marked regular (KIWI_HIP_MULTI_REGULAR=0) */, int repeat_on /* 0: no plan names repeated shifts (KIWI_HIP_MULTI_REPEAT=0) */,
@@ -1743,7 +1810,8 @@ __global__ __launch_bounds__(64) void multi_plan_kernel(const GeoRec *__restrict
             nrep += repeats ? 1u : 0u;
             const int head = (h[i]->flags & 0xffff) | (regular || repeats ? (e0 << kPlanE0Shift) | (regular ? kPlanRegularBit : 0) | (repeats << kPlanRepeatShift) : 0)
                              | (glen << 16) | ((shared ? 1 : 0) << 23) | ((npos - TILE) << 24);
-            out[4 * i + 0] = make_int4(h[i]->row[0], h[i]->row[1], h[i]->row[2], h[i]->row[3]);
+            // (rows 1 .. 3 as the kernel's build uses them, DescPlan::b0: the same 32-bit products it formed per group and wave)
+            out[4 * i + 0] = make_int4(h[i]->row[0], (h[i]->row[1] - h[i]->row[0]) * pitch, (h[i]->row[2] - h[i]->row[0]) * pitch, (h[i]->row[3] - h[i]->row[0]) * pitch);
             out[4 * i + 1] = o;
             out[4 * i + 2] = make_int4(__float_as_int(h[i]->w[0]), __float_as_int(h[i]->w[1]), __float_as_int(h[i]->w[2]), __float_as_int(h[i]->w[3]));
             out[4 * i + 3] = make_int4(smaxs[i], head, __float_as_int(h[i]->cl), __float_as_int(h[i]->sl));
@@ -1842,23 +1910,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
     const int pstep = nrec * kPlanStride;
     const int hoff = PLAN ? hig * pitch : 0;
     auto plan4 = [&](int byte) { return *(plan_cptr)(pcur + (size_t)(unsigned)byte); };
+    // this wave's coefficient lines (80 bytes per step, consecutive): a scalar pointer that advances by the group's length -- as
+    // (base_me + c) * kCoefLine it was a 64-bit product and a reload of `coefs` per group
+    const float *__restrict__ coef_cur = nullptr;
+    if constexpr (PLAN) {
+        const size_t a = (size_t)(coefs + base_me * kCoefLine);
+        coef_cur = (const float *)(((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a));
+    }
+    // halo lanes of this wave: thread 255 - q has chunk q / NG, so the wave's first halo chunk is that of its last thread,
+    // q = 64 (3 - wv) -- the wave has a halo lane in a group that reads more than 4 * (that chunk) positions behind the tile
+    const int lastf = PLAN ? __builtin_amdgcn_readfirstlane(multi_last_task<NG, NS>(wv)) : 0;      // (a scalar once: it was a lane read per wait)
+    const int hq_wave = 64 * (3 - wv);
+    const int hthr = hq_wave < 16 * NG ? 4 * (hq_wave / NG) : 0x7fffffff;
     while (c < nc) {
         GeoRec g[NS];
         int smaxs[NS], smins[NS], npos = 0;
         bool shared = true, same_rows = true;
         int glen_p = 0;
+        int flags = 0, smax = 0;
+        float gcl = 0.f, gsl = 0.f;
         DescPlan dp;
         if constexpr (PLAN) {
-            // rows, offsets and tile origin of the first source (of all of them where the build is shared) and the group's header:
-            // three scalar loads from lines multi_plan_kernel wrote and the previous group's shadow() brought into the scalar cache
-            const v4i_t rw = plan4(0), of = plan4(16), tl = plan4(48);
+            // (the plan's address as the loop's own value: derived from the induction variable the compiler keeps ONE pointer 240
+            // bytes into the plan and forms every line's address with an add and an add-with-carry in front of its load; an opaque
+            // base leaves the lines' offsets to the loads' immediate fields)
+            asm volatile("" : "+s"(pcur));
+            // rows and offsets of the first source (of all of them where the build is shared) and this wave's own source's line
+            // with the group's header (PlanSrc::head: glen, shared, npos are equal in all NS), its flags and rotation: three scalar
+            // loads from lines multi_plan_kernel wrote and the previous group's shadow() brought into the scalar cache
+            const v4i_t rw = plan4(0), of = plan4(16), me = plan4(64 * sh + 48);
             g[0].row[0] = rw.x;
-            dp = DescPlan{ { 0, (rw.y - rw.x) * pitch, (rw.z - rw.x) * pitch, (rw.w - rw.x) * pitch }, { of.x, of.y, of.z, of.w }, pitch, hoff };
-            const unsigned head = (unsigned)tl.y;
+            dp = DescPlan{ { 0, rw.y, rw.z, rw.w }, { of.x, of.y, of.z, of.w }, pitch, hoff };      // (PlanSrc::row: 1 .. 3 are offsets already)
+            const unsigned head = (unsigned)me.y;
             glen_p = (int)((head >> 16) & 0x7fu);
             shared = ((head >> 23) & 1u) != 0u;
             npos = TILE + (int)(head >> 24);
-            smaxs[0] = tl.x;
+            smax = me.x;
+            flags = me.y & 0xffff; gcl = __int_as_float(me.z); gsl = __int_as_float(me.w);
+            smaxs[0] = plan4(48).x;                          // (one dword: a branch around it for shared builds costs more than the load)
         }
         if constexpr (compact && !PLAN) desc_expand(ta, cur[0], lane, pitch, ta, tb);
         if constexpr (!PLAN) {
@@ -1897,25 +1986,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         const int cend = c + glen;
         // this wave's source: what its apply needs (equal for all centroids of the group: same point, same receiver) -- fetched
         // in the shadow of the build's loads, like the blend weights
-        int smax = smaxs[0];
-        if constexpr (PLAN) smax = plan4(64 * sh + 48).x;
-        else {
+        if constexpr (!PLAN) {
+            smax = smaxs[0];
 #pragma unroll
             for (int i = 1; i < NS; i++) if (sh == i) smax = smaxs[i];
         }
-        int flags = 0, ishv = 0, warm_ = 0, pwarm_ = 0;
-        float gcl = 0.f, gsl = 0.f;
-        const float *__restrict__ coef_grp = nullptr;
+        int ishv = 0, warm_ = 0, pwarm_ = 0;
+        const float *__restrict__ coef_grp = coef_cur;
         auto shadow = [&]() {
             if constexpr (PLAN) {
-                // the blend weights of every source and this wave's source's flags and rotation: scalar loads
+                // the blend weights of every source: scalar loads (this wave's source's flags and rotation came with the group's header:
+                // values the shadow defines reach the apply through vector registers, the build's variants being what they are)
 #pragma unroll
                 for (int i = 0; i < NS; i++) {
                     const v4i_t w = plan4(64 * i + 32);
                     g[i].w[0] = __int_as_float(w.x); g[i].w[1] = __int_as_float(w.y); g[i].w[2] = __int_as_float(w.z); g[i].w[3] = __int_as_float(w.w);
                 }
-                const v4i_t me = plan4(64 * sh + 48);
-                flags = me.y & 0xffff; gcl = __int_as_float(me.z); gsl = __int_as_float(me.w);
                 // the next group's plan on its way into the scalar cache (none behind the last group: nothing is read past the plans)
                 if (c + glen < nc) pwarm_ = plan_warm<NS>(pcur + (size_t)(unsigned)pstep);
             } else {
@@ -1929,23 +2015,43 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
             }
             // the group's integer shifts, lane k: step k -- not for a group the plan calls regular or whose repeats it names
             // (PlanSrc::head: its apply takes e0, the step count and those bits).  Wave-uniform: the waves of a workgroup may differ.
-            if (!(PLAN && (flags & (kPlanRegularBit | kPlanRepeatMask)))) { if (lane < glen) ishv = rc[c + lane].ishift; }
-            // this group's coefficient lines (80 bytes per step, consecutive) on their way into the scalar cache
-            const size_t crow = (base_me + c) * kCoefLine;
-            const unsigned clo = __builtin_amdgcn_readfirstlane((unsigned)crow), chi = __builtin_amdgcn_readfirstlane((unsigned)(crow >> 32));
-            coef_grp = coefs + (((size_t)chi << 32) | clo);
-            if constexpr (NG == 10) warm_ = coef_warm(coef_grp);
+            // (the empty statement keeps the wave-uniform test a scalar branch of its own: merged with the lanes' test it is six
+            // instructions of mask arithmetic in every group, also in those that skip the load)
+            if (!(PLAN && (flags & (kPlanRegularBit | kPlanRepeatMask)))) { if constexpr (PLAN) asm volatile(""); if (lane < glen) ishv = rc[c + lane].ishift; }
+            // this group's coefficient lines on their way into the scalar cache
+            if constexpr (!PLAN) {
+                const size_t crow = (base_me + c) * kCoefLine;
+                const unsigned clo = __builtin_amdgcn_readfirstlane((unsigned)crow), chi = __builtin_amdgcn_readfirstlane((unsigned)(crow >> 32));
+                coef_grp = coefs + (((size_t)chi << 32) | clo);
+            }
+            // (not with plans: measured as worth nothing there, DESIGN 3.3 -- eight scalar loads and a register held per group)
+            if constexpr (NG == 10 && (!PLAN || KIWI_MULTI_COEF_WARM)) warm_ = coef_warm(coef_grp);
         };
         auto noshadow = []() {};
+        // the blend weights once more for the halo's blend (see multi_build): from the plan through a copy of its address the compiler
+        // cannot match with the shadow's loads
+        auto reweigh = [&](GeoRec (&gl)[NS]) {
+            if constexpr (PLAN) {
+                size_t q = pcur;
+                asm volatile("" : "+s"(q));
+#pragma unroll
+                for (int i = 0; i < NS; i++) {
+                    const v4i_t w = *(plan_cptr)(q + (size_t)(unsigned)(64 * i + 32));
+                    gl[i].w[0] = __int_as_float(w.x); gl[i].w[1] = __int_as_float(w.y); gl[i].w[2] = __int_as_float(w.z); gl[i].w[3] = __int_as_float(w.w);
+                }
+            }
+        };
         // ---- build
+        // (whether this wave has a halo lane in this group: with plans a scalar compare, else a vector compare over the lanes and a ballot)
 #define KIWI_MULTI_BUILD(DESC, I0, ONLY, NPOS, SHADOW) do { \
             const int jb_ = t_tile0 - smaxs[I0] - 1;      /* LDS position p of a tile set holds its source's blended trace sample jb + p */ \
             const float *__restrict__ Gg = G + (size_t)g[I0].row[0] * (size_t)pitch; \
             const bool fast = (DESC).fast(jb_, LDS_TILE, pitch, lane, NG); \
-            const bool hact = hq < 16 * NG && hph < (NPOS); \
-            const bool whalo = __builtin_amdgcn_ballot_w64(hact) != 0ull; \
-            if (fast) multi_build<NG, true, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, SHADOW); \
-            else      multi_build<NG, false, NS>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, SHADOW); } while (0)
+            const bool hact = PLAN ? false : hq < 16 * NG && hph < (NPOS); \
+            const bool whalo = PLAN ? (NPOS) - TILE > hthr : __builtin_amdgcn_ballot_w64(hact) != 0ull; \
+            const int lastf_ = PLAN ? lastf : __builtin_amdgcn_readfirstlane(multi_last_task<NG, NS>(wv)); \
+            if (fast) multi_build<NG, true, NS, PLAN>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, lastf_, hq, NPOS, SHADOW, reweigh); \
+            else      multi_build<NG, false, NS, PLAN>(&tiles[0], wv, lane, tid, jb_, Gg, pitch, DESC, g, ONLY, hact, whalo, hig, hph, lastf_, hq, NPOS, SHADOW, reweigh); } while (0)
         // A workgroup in its build phase is waiting for memory most of the time: its waves go first whenever they have an
         // instruction to issue (loads out early, the blend done as soon as the rows arrive), the workgroups that are applying
         // fill the rest of the issue slots.  Measured: cfg3 133.5 -> 127.2 ms per 4096 sources, cfg3-100pt 55.2 -> 51.3 (the
@@ -1960,7 +2066,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                     const v4i_t rw = plan4(64 * i), of = plan4(64 * i + 16);
                     smaxs[i] = plan4(64 * i + 48).x;
                     g[i].row[0] = rw.x;
-                    const DescPlan di{ { 0, (rw.y - rw.x) * pitch, (rw.z - rw.x) * pitch, (rw.w - rw.x) * pitch }, { of.x, of.y, of.z, of.w }, pitch, hoff };
+                    const DescPlan di{ { 0, rw.y, rw.z, rw.w }, { of.x, of.y, of.z, of.w }, pitch, hoff };
                     KIWI_MULTI_BUILD(di, i, i, npos, noshadow);
                 }
             }
@@ -1995,10 +2101,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
         {
             const unsigned abase = (unsigned)(size_t)(lds_cfp)&tiles[sh * SET + u0];
             if constexpr (NG == 10 || NG == 8) {
-                asm volatile("" :: "s"(warm_));          // (the warming loads' target register stays allocated until here)
-                const float gcl_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gcl))), gsl_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gsl)));
-                const size_t cg_ = (size_t)coef_grp;
-                const float *__restrict__ coef_u = (const float *)(((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(cg_ >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)cg_));
+                if constexpr (!PLAN || KIWI_MULTI_COEF_WARM) asm volatile("" :: "s"(warm_));          // (the warming loads' target register stays allocated until here)
+                // (with plans the rotation, the header word and the coefficient pointer ARE scalars -- scalar loads and scalar
+                // arithmetic at the loop's top level; a read of the first lane would take them through a vector register)
+                float gcl_u = gcl, gsl_u = gsl;
+                if constexpr (!PLAN) { gcl_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gcl))); gsl_u = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(gsl))); }
+                const float *__restrict__ coef_u = coef_grp;
+                if constexpr (!PLAN) {
+                    const size_t cg_ = (size_t)coef_grp;
+                    coef_u = (const float *)(((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(cg_ >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)cg_));
+                }
                 // the whole group in ONE hand-allocated assembly routine (kiwi_apply_asm.inc): two register sets that swap roles, the LDS reads and
                 // the coefficient line of step k + 1 under the arithmetic of step k
                 // (eight-component databases -- far-field Green's functions, gfdb.f90:57 -- have routines of their own since round 6: the
@@ -2011,12 +2123,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                     // statement, the choice scalar bit tests inside it (apply_steps_asm_*, tools/gen_apply_asm.py routine_steps) -- a
                     // regular group takes the routine with neither the shifts nor a test per step (apply_regular_asm_*'s text), one with
                     // repeats that text with a bit test per step and no tile read for a step that stays
-                    const int head_u = __builtin_amdgcn_readfirstlane(flags);
+                    const int head_u = flags;
+                    // (rot or plain chosen by the lanes: on a scalar branch the compiler joins the two statements' accumulators
+                    // through six 64-bit copies in front of each -- DESIGN 3.3, Regular groups)
+                    int rot_v = flags & 2;
+                    asm("" : "+v"(rot_v));
                     if constexpr (NG == 10) {
-                        if (flags & 2) { if constexpr (K == 5) KIWI_APPLY_PLAN(10, 5, rot)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(10, 9, rot)(KIWI_PLAN_ARGS); }
+                        if (rot_v) { if constexpr (K == 5) KIWI_APPLY_PLAN(10, 5, rot)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(10, 9, rot)(KIWI_PLAN_ARGS); }
                         else           { if constexpr (K == 5) KIWI_APPLY_PLAN(10, 5, plain)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(10, 9, plain)(KIWI_PLAN_ARGS); }
                     } else {
-                        if (flags & 2) { if constexpr (K == 5) KIWI_APPLY_PLAN(8, 5, rot)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(8, 9, rot)(KIWI_PLAN_ARGS); }
+                        if (rot_v) { if constexpr (K == 5) KIWI_APPLY_PLAN(8, 5, rot)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(8, 9, rot)(KIWI_PLAN_ARGS); }
                         else           { if constexpr (K == 5) KIWI_APPLY_PLAN(8, 5, plain)(KIWI_PLAN_ARGS); else KIWI_APPLY_PLAN(8, 9, plain)(KIWI_PLAN_ARGS); }
                     }
                 } else
@@ -2049,6 +2165,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
 #undef KIWI_C2STEP
             }
         }
+        if constexpr (PLAN) coef_cur += (size_t)(unsigned)(glen * kCoefLine);
         c = cend;                                        // (the barrier in front of the next group's LDS writes: multi_build)
     }
     // ---- rotation to N/E, signs and store (or fused comparison) of this wave's source (seismogram.f90:256-283)

@@ -120,7 +120,8 @@ constexpr int kCoefLine = 20;      // floats per record in the coefficient array
 // kPlanStride bytes (NS = 2 uses the first half), 16-byte aligned: a PlanSrc per source.  The plans of a source group are consecutive,
 // [centroid group][receiver]; plan_ofs[k] (host, run_chunk) is the index of the first plan of source group k.
 struct PlanSrc {
-    int   row[4];     // GeoRec::row of the group's head record
+    int   row[4];     // GeoRec::row of the group's head record: row[0] itself, 1 .. 3 as (row[k] - row[0]) * pitch, the distance in samples
+                      // of node k's first row from node 0's (what the build adds to its addresses: DescPlan::b0, kiwi_accum.inc)
     int   o[4];       // compact descriptor of the head record (geometry_kernel's off4): sample 0 inside the rows of node k
     float w[4];       // GeoRec::w
     int   smax;       // tile origin of this source's tile set: its own largest shift, or the common one of a shared build
